@@ -13,8 +13,11 @@ A "step" is one pass of the hot path over one batch of synthetic input that is a
         an RCCL reduce_scatter(sum) of the per-frame spectra, asynchronous, overlapping the next chunk's transforms.
         Total work is fixed (8 channels) whatever N: strong scaling.  `--channels 8` runs the same graph on one GPU.
 
-After the timed region a self-check pulls sampled output frames back and compares them with the float64 oracle on the same
-device-generated input (checker only; exit code 3 above 1e-5).  Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times the --steps steps and prints ONE JSON line on rank 0.  `--dump-outputs DIR` writes what the
+last timed step computed (a fixed, seeded sample of its output frames) as DIR/*.npy.  `--full` adds everything beside the headline:
+a self-check that pulls sampled output frames back and compares them with the float64 oracle on the same device-generated input
+(checker only; exit code 3 above 1e-5), the rows of other windows, filters and configs, live PMC traffic, the CPU baseline and the
+8-channel graph on one GPU.
 """
 import argparse
 import json
@@ -30,6 +33,7 @@ ALGO_BYTES_PER_SAMPLE = 12.0  # 8 B complex<float> in + 4 B float mag2 out (SURV
 HBM_PEAK_GBS = 8000.0         # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 XGMI_LINK_GBS = 153.0         # per link and direction (7 links per GPU), nominal
 PARITY_TOL = 1e-5             # BASELINE.json north_star: <= 1e-5 rel for float32 FIR/FFT
+DUMP_FRAMES, DUMP_SEED = 1024, 0  # --dump-outputs: 1024 frames x 8192 bins x 4 B = 32 MiB in all ranks together (the limit is 64 MB)
 KERNEL_SYMBOLS = {1: "gr4::fir_poly_kernel + gr4::fft_fast_kernel (unfused)", 3: "gr4::chain_fd_kernel<0, 13>",
                   4: "gr4::fir_poly_kernel + gr4::fft_fast_kernel (time domain)"}
 
@@ -69,10 +73,11 @@ class Watchdog:
             msg = f"rank {self.rank} of {self.world}: no progress in phase '{phase}' within its deadline ({self.timeout:.0f} s budget per waiting phase); {time.time() - self.t0:.0f} s since start"
             print(f"[bench][watchdog] {msg}", file=sys.stderr, flush=True)
             if retryable and os.environ.get("GR4HIP_BENCH_RETRY") != "1":
+                import subprocess
                 print(f"[bench][watchdog] rank {self.rank}: retrying once with --fanin-impl torch --fanin-cus 0", file=sys.stderr, flush=True)
                 os.environ["GR4HIP_BENCH_RETRY"] = "1"
-                args = [a for a in self.argv]
-                os.execv(sys.executable, [sys.executable] + args + ["--fanin-impl", "torch", "--fanin-cus", "0"])
+                # a fresh child process, not an exec: this process has the GPU open
+                os._exit(subprocess.call([sys.executable] + self.argv + ["--fanin-impl", "torch", "--fanin-cus", "0"]))
             if self.rank == 0:
                 print(json.dumps({"metric": "Msamples/s through 256-tap cplx FIR->8192-pt FFT chain; %HBM roofline @1/2/4/8 GPU", "value": None, "n_gpus": self.world,
                                   "error": msg, "phase": phase, "retried": os.environ.get("GR4HIP_BENCH_RETRY") == "1"}), flush=True)
@@ -195,6 +200,20 @@ def live_traffic(kernel_symbol, log2_samples, log2_chunk):
             shutil.rmtree(out, ignore_errors=True)
     return int((2.0 * kib["FETCH_SIZE"] + kib["WRITE_SIZE"]) * 1024), (f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate counter-only passes over short runs of this script at the same "
                                                                       f"launch size: FETCH_SIZE {kib['FETCH_SIZE']:.0f} KiB x 2 (gfx950 16-byte/lane correction) + WRITE_SIZE {kib['WRITE_SIZE']:.0f} KiB per dispatch")
+
+
+def dump_outputs(dirname, spectra, rank, world):
+    """--dump-outputs: the |X|^2 frames of the last timed step that this rank's caller receives, a fixed seeded sample of DUMP_FRAMES of them (the whole output of
+    a 2^30-sample step is 4 GB), as float32 <dirname>/spectra.npy [frames, NFFT] with the frame numbers beside it (spectra_frame_index.npy, float64)"""
+    import numpy as np
+    import torch
+    nfr = spectra.shape[0]
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(nfr, min(nfr, DUMP_FRAMES // world), replace=False))
+    got = spectra.index_select(0, torch.from_numpy(idx).to(spectra.device)).cpu().numpy()
+    sfx = f"_rank{rank}" if world > 1 else ""
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, f"spectra{sfx}.npy"), got.astype(np.float32))
+    np.save(os.path.join(dirname, f"spectra_frame_index{sfx}.npy"), idx.astype(np.float64))
 
 
 def secondary_configs(G, verify):
@@ -387,9 +406,13 @@ def main():
     ap.add_argument("--fanin-impl", default="capi", choices=["capi", "torch"], help="N > 1 over RCCL: the collectives through the library's C entry points (gr4hip_fanin_*: the "
                     "communicator the C++ engine uses; torch.distributed only ships its id) or through torch.distributed's own communicator")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, the measured configuration) or gloo (functional check of the N > 1 path on a box with fewer GPUs than ranks)")
+    ap.add_argument("--full", action="store_true", help="also run everything beside the headline: the oracle self-check, the Hann and guard rows, configs[2] and configs[3], the "
+                    "host-fed row, the live PMC traffic passes, the CPU baseline and the 8-channel graph on one GPU; the --no-* options skip single parts of it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last one computed as DIR/*.npy (float32 spectra of a fixed, "
+                                                                          "seeded sample of frames, 32 MiB, and their frame numbers)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--detail-file", default=None, help="where rank 0 writes the long form of the result (every row with its workload text, timing notes, per-rank logs); "
-                                                        "default gpurun_out/bench_detail.json under the repo root; '' = nowhere.  The printed line stays under 2 000 characters")
+                                                        "default with --full: bench_out/bench_detail.json under the repo root, else nowhere; '' = nowhere.  The printed line stays under 2 000 characters")
     ap.add_argument("--no-verify", action="store_true", help="skip the oracle self-check of sampled output frames")
     ap.add_argument("--no-multi", action="store_true", help="several channels per GPU: one kernel per channel on its own stream + a separate math::Add fold (round 2's shape) "
                     "instead of ONE launch with the fold in registers (gr4hip_chain_process_multi)")
@@ -404,6 +427,8 @@ def main():
     ap.add_argument("--fanin-timeout", type=float, default=90.0, help="N > 1: seconds any phase that waits for another rank may take before the run gives up with a rank-tagged diagnostic "
                     "(exit code 4, an \"error\" key in the JSON line) instead of hanging; 0 = no watchdog")
     args = ap.parse_args()
+    if not args.full:  # a plain run does only what the headline needs
+        args.no_verify = args.no_hann_row = args.no_secondary = args.no_live_traffic = args.no_cpu_baseline = args.no_graph8 = True
 
     import numpy as np
     import torch
@@ -635,6 +660,8 @@ def main():
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
+    if args.dump_outputs:  # before the rows of --full, which reuse the output buffers
+        dump_outputs(args.dump_outputs, sum_out if sum_out is not None else (rs_out.reshape(-1, NFFT) if rs_out is not None else outs[0]), rank, world)
 
     # ---- self-check (outside the timed region): sampled frames of the last step against the float64 oracle on the same input
     verify = None
@@ -863,7 +890,7 @@ def main():
             torch.cuda.empty_cache()
             import subprocess
             try:
-                child = subprocess.run([sys.executable, os.path.abspath(__file__), "--channels", "8", "--log2-samples", "28", "--steps", "12", "--warmup", "4", "--no-cpu-baseline"],
+                child = subprocess.run([sys.executable, os.path.abspath(__file__), "--channels", "8", "--log2-samples", "28", "--steps", "12", "--warmup", "4", "--full", "--no-cpu-baseline"],
                                        capture_output=True, text=True, timeout=600, env={**os.environ, "GR4HIP_BENCH_CHILD": "1"})
                 g8 = json.loads(child.stdout.strip().splitlines()[-1])
                 res["eight_channel_graph_on_one_gpu"] = {"value": g8["value"], "unit": g8["unit"], "ms_per_step": g8["ms_per_step"], "samples_per_channel_and_step": 1 << 28,
@@ -872,7 +899,7 @@ def main():
                 res["eight_channel_graph_on_one_gpu"] = {"error": str(e)[:200]}
         detail = args.detail_file
         if detail is None:
-            detail = "" if os.environ.get("GR4HIP_BENCH_CHILD") == "1" else os.path.join(ROOT, "gpurun_out", "bench_detail.json")
+            detail = "" if os.environ.get("GR4HIP_BENCH_CHILD") == "1" or not args.full else os.path.join(ROOT, "bench_out", "bench_detail.json")
         print(json.dumps(_compact_line(res, detail)), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -39,22 +39,51 @@ def _run(cmd, timeout=900):
 
 
 def test_bench_single_channel_self_check():
-    r = _run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--log2-samples", "26", "--log2-chunk", "24", "--no-cpu-baseline", "--no-graph8", "--no-live-traffic", "--no-secondary"])
+    r = _run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--log2-samples", "26", "--log2-chunk", "24", "--no-cpu-baseline", "--no-graph8", "--no-live-traffic", "--no-secondary"])
     assert r["n_gpus"] == 1 and r["config"]["channels"] == 1 and r["scaling"] == "weak"
     assert r["roofline"]["kernel"] == "gr4::chain_fd_kernel<0, 13>"
     v = r["verify"]
     assert v["verified_frames"] >= 6 and v["max_rel_err"] <= 1e-5
 
 
+def test_bench_plain_run_times_steps_and_dumps_the_last_one(tmp_path):
+    """without --full the line holds the headline only (nothing beside it is run); --dump-outputs writes a seeded sample of the last timed step's spectra, float32,
+    within 64 MB, and those frames are the float64 oracle's"""
+    import numpy as np
+    import torch
+    import bench
+    import gnuradio4_amd as G
+    import oracle_lib as O
+    r = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--log2-samples", "26", "--log2-chunk", "24", "--dump-outputs", str(tmp_path)])
+    assert all(k in r for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step")), r
+    assert r["steps"] == 3 and r["roofline"]["timed_launches"] == 3 * 4 and r["ms_per_step"] > 0 and r["value"] > 0
+    assert not {"verify", "cpu_baseline", "hann_msamples", "guard_settled_msamples", "configs2_msamples", "graph8_msamples", "host_feed_msamples", "detail_file"} & set(r), r
+    spec, idx = np.load(tmp_path / "spectra.npy"), np.load(tmp_path / "spectra_frame_index.npy")
+    nfr = (1 << 26) // bench.NFFT
+    assert spec.dtype == np.float32 and spec.shape == (bench.DUMP_FRAMES, bench.NFFT) and idx.dtype == np.float64
+    assert np.array_equal(idx, np.unique(idx)) and idx[0] >= 0 and idx[-1] < nfr
+    assert sum(f.stat().st_size for f in tmp_path.iterdir()) <= 64e6
+    w = np.empty(bench.NTAPS, np.float32)  # bench.py's taps: Hamming windowed-sinc, fc = 0.1, DC gain 1
+    G.capi.check(G.capi.lib().gr4hip_window_create(2, w.ctypes.data, bench.NTAPS, 1.6), "window")
+    k = np.arange(bench.NTAPS, dtype=np.float64)
+    taps = w.astype(np.float64) * 0.2 * np.sinc(0.2 * (k - (bench.NTAPS - 1) / 2.0))
+    taps = (taps / taps.sum()).astype(np.float32)
+    x = G.synth_c32(1 << 26, seed=42)
+    for j in (0, 1, len(idx) // 2, len(idx) - 1):
+        assert bench._rel_err(spec[j], bench.oracle_frame(O, taps, x, int(idx[j]))) <= 1e-5, int(idx[j])
+    del x
+    torch.cuda.empty_cache()
+
+
 def test_bench_single_channel_line_carries_the_one_gpu_point_of_the_graph():
     """the N = 1 line also reports the 8-channel graph on this one GPU (own process, after the headline): the origin of the strong-scaling curve"""
-    r = _run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--log2-samples", "26", "--log2-chunk", "24", "--no-cpu-baseline", "--no-live-traffic", "--no-secondary"])
+    r = _run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--log2-samples", "26", "--log2-chunk", "24", "--no-cpu-baseline", "--no-live-traffic", "--no-secondary"])
     g8 = r["eight_channel_graph_on_one_gpu"]
     assert "error" not in g8 and g8["value"] > 0 and g8["verify"]["max_rel_err"] <= 1e-5 and r["config"]["channels"] == 1
 
 
 def test_bench_eight_channel_graph_one_gpu():
-    r = _run([sys.executable, "bench.py", "--channels", "8", "--steps", "2", "--warmup", "1", "--log2-samples", "24"])
+    r = _run([sys.executable, "bench.py", "--full", "--channels", "8", "--steps", "2", "--warmup", "1", "--log2-samples", "24"])
     assert r["config"]["channels"] == 8 and r["scaling"] == "strong" and "cpu_baseline" not in r
     assert r["verify"]["verified_frames"] >= 8 and r["verify"]["max_rel_err"] <= 1e-5
 
@@ -63,7 +92,7 @@ def test_bench_eight_channel_graph_one_gpu():
 def test_bench_two_ranks_share_the_gpu_gloo_fanin(algo):
     """auto: both fan-in algorithms are timed before the warm-up and the faster one runs (the choice is the same on every rank)"""
     r = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-              "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--dist-backend", "gloo", "--log2-samples", "24",
+              "--master-port", str(_free_port()), "bench.py", "--full", "--gpus", "2", "--dist-backend", "gloo", "--log2-samples", "24",
               "--steps", "2", "--warmup", "1", "--fanin-algo", algo])
     assert r["n_gpus"] == 2 and r["config"]["channels"] == 8 and r["scaling"] == "strong"
     assert "4 per GPU" in r["config"]["parallelism"]
@@ -94,7 +123,7 @@ def test_bench_stalled_rank_gives_a_diagnostic_not_a_hang():
 
 
 def test_bench_line_has_the_median_the_prewarm_the_hann_row_and_the_secondary_configs():
-    r = _run([sys.executable, "bench.py", "--steps", "5", "--warmup", "1", "--log2-samples", "26", "--log2-chunk", "24", "--no-cpu-baseline", "--no-graph8"])
+    r = _run([sys.executable, "bench.py", "--full", "--steps", "5", "--warmup", "1", "--log2-samples", "26", "--log2-chunk", "24", "--no-cpu-baseline", "--no-graph8"])
     assert r["prewarm_ms"] >= 40 and r["prewarm_steps"] >= 1 and r["median_ms_per_step"] > 0 and r["value_at_median_step"] > 0
     assert r["roofline"]["timed_launches"] == 5 * 4
     assert r["hann_msamples"] > 0 and r["configs2_msamples"] > 0 and r["configs3_msamples"] > 0 and r["guard_settled_msamples"] > 0  # the rows as top-level numbers of the printed line
