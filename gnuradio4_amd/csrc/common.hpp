@@ -39,6 +39,12 @@ enum DevSwitch {
 };
 int dev_switch(DevSwitch s);
 
+// The dynamic-range guard of the decimate-by-8 frequency-domain kernel (fir_decim_fd.hip; gr4hip_fir_process and gr4hip_fir_iir_process decide on it): output / input
+// power threshold.  The kernel's floor is one forward 4096-point and one inverse 1024-point transform -- measured (tools/decim_fd_floor.py) max 2.5e-7 .. 3.7e-7, rms 7e-8
+// of the INPUT rms per output sample, six times below the fused chain's -- so 1e-5 of the OUTPUT rms holds down to a power ratio of (4e-7 / 1e-5)^2 = 1.6e-3; 2.5e-3
+// (-26 dB) with margin.  White noise through a DC-gain-1 low-pass of cut-off fc passes 2 fc of its power: every anti-alias filter down to fc = 0.00125 stays on it.
+constexpr float kDecimFdMinPowerRatio = 2.5e-3f;
+
 #define GR4_HIP_TRY(expr)                                                                              \
     do {                                                                                               \
         hipError_t e_ = (expr);                                                                        \
@@ -150,8 +156,8 @@ struct DeviceBuffer {
 // call applies it on ITS stream, in front of its own launches and therefore behind everything that stream still has in flight for the handle.  That is the
 // reference's contract -- reset() / settingsChanged() run on the block's worker between two work() calls (Block.hpp:606, 916-917, 1296; Scheduler.hpp:1938-1951) --
 // without a device-wide wait, and it holds on hipStreamNonBlocking streams, which the NULL stream does not order against (round 5's race: a NULL-stream hipMemset
-// of the carried history overtaken by the previous launch's carry).  A host-to-device hipMemcpyAsync from pageable memory returns when the source has been
-// consumed (the runtime stages it), so host vectors may be locals.  tests/test_abi_host.py greps for bare hipMemset( / hipMemcpy( in this directory.
+// of the carried history overtaken by the previous launch's carry).  The host image a hipMemcpyAsync reads is owned by the handle (tp_host, row_host, ...), never a
+// local: the copy may still be reading it after the call returns.  tests/test_abi_host.py greps for bare hipMemset( / hipMemcpy( in this directory.
 inline hipError_t upload_fresh(void* dst, const void* src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); }
 
 // host-side restatement of gr::algorithm::window::create<float> (algorithm/.../fourier/window.hpp:69-183)

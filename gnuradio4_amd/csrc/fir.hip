@@ -341,6 +341,7 @@ constexpr size_t kFdFrame     = 8192;
 constexpr double kGuardSegmentRatio = 1.0 / 128.0;
 constexpr size_t kMfmaMinSamples = 1 << 16;
 constexpr size_t kFdMinFrames = 64; // below this the direct-form kernel is as fast (the persistent FD grid wants >= 1 frame per CU)
+constexpr size_t kDfHopS = 7168, kDfMinBlocks = 64; // the decimate-by-8 frequency-domain kernel (fir_decim_fd.hip): new samples per block, and the fewest blocks it takes
 
 struct gr4hip_fir {
     int                dtype = GR4HIP_F32;
@@ -368,22 +369,29 @@ struct gr4hip_fir {
     bool               fd_probed = false, fd_blocked = false;
     float              fd_ratio  = -1.f;
     gr4::FirDecimFd*   dfd = nullptr; // float, decim 8, <= 1024 taps: frequency-domain decimator (created on first use)
-    DeviceBuffer       d_band;        // float, decim >= 10: tap row of fir_decim_band_kernel (built on first use)
+    // tables built on first use, each with its host image (the stream rule, common.hpp: the copy on the call's stream may read it after the call returns)
+    DeviceBuffer       d_band;        // float, decim >= 10: tap row of fir_decim_band_kernel
+    std::vector<float> band_host;
     int                bandKp = 0;
-    DeviceBuffer       d_bfrag;       // float / complex, 65 .. 256 taps (float: slices of 256 up to 2048): the three bf16 tap-fragment tables of fir_mfma_bf16x3_kernel (built on first use)
+    DeviceBuffer       d_bfrag;       // 33 .. 256 taps (float: also slices of 256 for 384 .. 1024): the three bf16 tap-fragment tables of fir_mfma_bf16x3_kernel
+    std::vector<unsigned short> bfrag_host;
     int                bfKS = 0;
-    DeviceBuffer       d_hfrag;       // float, 33 .. 256 taps and the 256-tap slices of 384 .. 1024: the two-term f16 tables of fir_mfma_f16x2_kernel (fir_f16.hip; built on first use)
+    DeviceBuffer       d_hfrag;       // 33 .. 256 taps and the 256-tap slices beyond (float: up to 3840, complex: up to 1792): the two-term f16 tables of fir_mfma_f16x2_kernel (fir_f16.hip)
+    std::vector<unsigned short> hfrag_host;
     int                hfKS = 0;      // < 0: taps that form cannot carry
-    DeviceBuffer       d_dhtab;       // float, decimate by 8, 169 .. 1025 taps: the table of fir_decim8_f16x2_kernel (fir_decim_f16.hip; built on first use)
+    DeviceBuffer       d_dhtab;       // decimate by 4 / 8 / 16 / 32, <= 1025 taps: the table of the f16 band-form decimators (fir_decim_f16.hip)
+    std::vector<unsigned short> dhtab_host;
     int                dhKQ = 0;      // < 0: a shape that kernel does not carry
     std::vector<size_t> hf_off;       // per slice: offset into d_hfrag (in 16-bit units) ...
     std::vector<int>    hf_ks;        // ... and window size
-    DeviceBuffer       d_bdfrag;      // float, decim 2 .. 9, short branches: band-form bf16 fragments (fir_decim_bf16x3_kernel)
+    DeviceBuffer       d_bdfrag;      // float, decim 2 .. 12, complex, decim 3 .. 16, short branches: band-form bf16 fragments (fir_decim_bf16x3_kernel)
+    std::vector<unsigned short> bdfrag_host;
     int                bdKS = 0, bdHb = 0; // bdKS < 0: the window does not fit that kernel
     std::vector<size_t> bf_off;       // per slice: offset into d_bfrag (in bf16 elements) ...
     std::vector<int>    bf_ks;        // ... and window size
     DeviceBuffer       d_hist256, d_histc;
-    DeviceBuffer       d_afrag;       // real, decim 1, 32 < ntaps <= 256: MFMA A fragments (built on first use)
+    DeviceBuffer       d_afrag;       // 33 .. 256 taps without decimation, 16 .. 256 taps per phase with it: f32 MFMA A fragments
+    std::vector<float> afrag_host;
     int                mKp = 0, mKS = 0;
     // per-sample neighbours executed in this filter's launch (gr4hip_fir_set_prologue / _epilogue): private copies of the programs
     gr4hip_ewise*      pre = nullptr, *post = nullptr;
@@ -456,6 +464,14 @@ static int fir_state_on(gr4hip_fir* f, hipStream_t st) {
         GR4_LAUNCH_CHECK();
         f->hist_rescale = 1.0;
     }
+    return GR4HIP_OK;
+}
+// a table built on first use: onto the call's stream, behind the launches that may still read the buffer's earlier contents.  The image is the handle's own.
+template <class T>
+static int fir_upload_table(DeviceBuffer& d, const std::vector<T>& image, hipStream_t st) {
+    if (const int rc = d.ensure(image.size() * sizeof(T))) return rc;
+    const hipError_t e = hipMemcpyAsync(d.ptr, image.data(), image.size() * sizeof(T), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) { set_error("fir: upload failed: %s", hipGetErrorString(e)); return GR4HIP_RUNTIME_ERROR; }
     return GR4HIP_OK;
 }
 
@@ -611,47 +627,525 @@ int gr4hip_fir_set_guard_mode(gr4hip_fir_t* f, int mode) {
     if (f->fd) chain_fused_set_measure(f->fd, mode != GR4HIP_GUARD_OFF && f->ntaps > 1);
     return GR4HIP_OK;
 }
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------ gr4hip_fir_process: which kernel takes a call
+
+// Crossover thresholds of the dispatch: developer knobs read from the environment when the library is loaded (tools/decim_d4_rates.py, tools/cfir_bf16_threshold.py)
+static size_t env_size(const char* name, size_t dflt) {
+    const char* e = std::getenv(name);
+    return e ? (size_t)std::atoi(e) : dflt;
+}
+// taps from which the f16 band-form decimator takes a call.  Measured (G input samples/s, bf16 band kernel / f16 one), float decimate by 8: 64 taps 1037 / 998,
+// 100 taps 984 / 999, 128 taps 963 / 998
+static const size_t kDecimF16MinTaps8  = env_size("GR4HIP_FIR_DECIM_F16_MIN_TAPS", 97);
+static const size_t kDecimF16MinTapsW  = env_size("GR4HIP_FIR_DECIM_F16_MIN_TAPS_WIDE", 33); // (decimate by 16 / 32)
+static const size_t kDecimF16MinTapsC8 = env_size("GR4HIP_FIR_DECIM_F16_MIN_TAPS_C8", 64);   // (complex, decimate by 8)
+static const size_t kDecimF16MinTaps4  = env_size("GR4HIP_FIR_DECIM_F16_MIN_TAPS_D4", 33);   // (decimate by 4, float and complex)
+// complex taps from which the three-term bf16 kernel takes over from the f32 MFMA.  65 puts 33 .. 64 taps back on the f32 MFMA (measured 5-8 % slower: 299-316
+// against 322-333 Gsamples/s); below 33 taps the register-window kernel is ahead up to 27 taps and within 3 % from there (tools/cfir_bf16_threshold.py)
+static const size_t kCBf16MinTaps = env_size("GR4HIP_CFIR_BF16_MIN_TAPS", 33);
+static const size_t kBandMinDecim = env_size("GR4HIP_FIR_BAND_MIN_DECIM", 10); // where the band form takes over from the polyphase form
+
+// the handle moves past a span of n_in input samples: its next history is the span's last hcap samples (unless the launch that took it has written them)
+static int fir_advance(gr4hip_fir* f, const float* x, size_t n_in, hipStream_t st, bool hist_written) {
+    if (!hist_written) {
+        const long tot = (long)f->hcap * f->S;
+        hipLaunchKernelGGL(fir_hist_update_kernel, dim3((unsigned)ceil_div(tot, 256L)), dim3(256), 0, st, x, (const float*)f->d_hist[f->cur].ptr, (float*)f->d_hist[f->cur ^ 1].ptr, (long)n_in,
+                           (int)f->hcap, f->S);
+        GR4_LAUNCH_CHECK();
+    }
+    f->cur ^= 1;
+    f->pos += (long)n_in;
+    return GR4HIP_OK;
+}
+
+// one gr4hip_fir_process call as the paths below see it
+struct FirCall {
+    gr4hip_fir*     f;
+    const float*    x;
+    float*          y;
+    size_t          n_in, n_out;
+    hipStream_t     st;
+    const FirHooks& hk;
+    bool            plain; // no hooks: the matrix-pipe and frequency-domain kernels are for plain filters
+    int             algo;  // f->algo; GR4HIP_FIR_EXACT_F32 (= the register-window kernel only) for a hooked call
+    const float*    hist;  // the hcap samples in front of x + done
+    size_t          done = 0; // input samples already produced (only the fast convolution leaves a remainder)
+    // a kernel that does not judge its own segments (f32 matrix-pipe and three-term bf16 direct forms, band, generic) notes where its part of the span starts and
+    // which samples lie in front of it: the judge and the second evaluation follow it at the end of the call
+    size_t          unj_from = SIZE_MAX;
+    const float*    unj_hist = nullptr;
+    bool            hist_written = false; // the launch that finished the span wrote the next history
+    float* next_hist() const { return (float*)f->d_hist[f->cur ^ 1].ptr; }
+    int    took(bool wrote_hist) { done = n_in; hist_written = wrote_hist; return GR4HIP_OK; }
+    int    took_unjudged(bool wrote_hist) { unj_from = done; unj_hist = hist; return took(wrote_hist); }
+};
+
+static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 // the three-term bf16 kernels are off for this handle (GR4HIP_FIR_EXACT_F32: IEEE float32 multiply-add, the reference's Inf / NaN behaviour) or for the process (developer switch)
 static bool no_bf16x3(const gr4hip_fir_t* f) { return f->algo == GR4HIP_FIR_EXACT_F32 || f->f32_products || dev_switch(kDevFirNoBf16x3); }
+// May the two-term f16 kernels (fir_f16.hip) take the call?  The complex and the float form differ on purpose.
+// complex: not EXACT_F32 (TIME_DOMAIN included) and f32_user, not f32_products: a stream moved by the guard stays on the self-judging f16 kernel
+static bool fir_cf16_ok(const FirCall& c) {
+    const gr4hip_fir* f = c.f;
+    return c.plain && c.algo != GR4HIP_FIR_EXACT_F32 && !f->f32_user && !f->bf16_user && !dev_switch(kDevFirNoBf16x3) && !dev_switch(kDevFirNoF16x2) && f->hfKS >= 0;
+}
+// float: AUTO only (TIME_DOMAIN keeps the f32 matrix pipe); no guard moves a float filter without decimation, so f32_products is the user's choice here
+static bool fir_rf16_ok(const FirCall& c) {
+    const gr4hip_fir* f = c.f;
+    return c.plain && c.algo == GR4HIP_FIR_AUTO && !no_bf16x3(f) && !f->bf16_user && !dev_switch(kDevFirNoF16x2) && f->hfKS >= 0;
+}
 
-// does this call take the band-form bf16 decimators (fir_bf16.hip)?  Builds their fragments on first use.
-// does the f16 band-form decimator (fir_decim_f16.hip: D = 4 / 8 / 16 / 32, two-term f16 products, carries the filter's programs since round 5) take this call?
+// (first use) the two-term f16 tables (fir_f16_make_afrag) in slices of 256 taps, one after the other in d_hfrag.  hfKS < 0: taps that form cannot carry.
+// pad9: a slice of 8 K-steps runs the 9-step kernel on zero-padded taps (the complex sliced kernel at 8 K-steps would keep two registers in scratch).
+// thr_in_header: the last slice's header carries a tighter guard ratio of a library-internal caller -- a second verdict on the segment's WHOLE output power; the
+// quietest-column statistic keeps its 21 dB (at 15 dB it dips below on narrow-band noise alone: 1 % pass band, half of all segments marked).
+static int fir_f16_tables(gr4hip_fir* f, hipStream_t st, bool pad9, bool thr_in_header) {
+    if (f->hfKS != 0) return GR4HIP_OK;
+    const size_t                 nslice = ceil_div(f->ntaps, (size_t)256);
+    std::vector<unsigned short>& all    = f->hfrag_host;
+    all.clear();
+    f->hf_off.assign(nslice, 0);
+    f->hf_ks.assign(nslice, 0);
+    for (size_t p = 0; p < nslice; ++p) {
+        std::vector<unsigned short> af;
+        const size_t                len = std::min<size_t>(256, f->ntaps - 256 * p);
+        const int                   nat = std::max(3, (int)((len - 1 + 16 + 31) / 32));
+        if (!fir_f16_make_afrag(f->taps.data() + 256 * p, len, &f->hf_ks[p], &af, 1, pad9 && nat == 8 ? 9 : 0)) { f->hfKS = -1; return GR4HIP_OK; }
+        if (thr_in_header && p + 1 == nslice && f->guard_ratio != kGuardSegmentRatio) {
+            const float g = (float)(f->tap_power * f->guard_ratio);
+            std::memcpy(af.data() + (size_t)f->hf_ks[p] * 1536 + 6, &g, 4);
+        }
+        f->hf_off[p] = all.size();
+        all.insert(all.end(), af.begin(), af.end());
+    }
+    if (const int rc = fir_upload_table(f->d_hfrag, all, st)) return rc;
+    f->hfKS = f->hf_ks[0];
+    return GR4HIP_OK;
+}
+// (first use) the three-term bf16 fragments (fir_bf16_make_afrag) in slices of 256 taps, one after the other in d_bfrag
+static int fir_bf16_tables(gr4hip_fir* f, hipStream_t st) {
+    if (f->bfKS != 0) return GR4HIP_OK;
+    const size_t                 nslice = ceil_div(f->ntaps, (size_t)256);
+    std::vector<unsigned short>& all    = f->bfrag_host;
+    all.clear();
+    f->bf_off.assign(nslice, 0);
+    f->bf_ks.assign(nslice, 0);
+    for (size_t p = 0; p < nslice; ++p) {
+        std::vector<unsigned short> af;
+        fir_bf16_make_afrag(f->taps.data() + 256 * p, std::min<size_t>(256, f->ntaps - 256 * p), &f->bf_ks[p], &af, 1, 0);
+        f->bf_off[p] = all.size();
+        all.insert(all.end(), af.begin(), af.end());
+    }
+    if (const int rc = fir_upload_table(f->d_bfrag, all, st)) return rc;
+    f->bfKS = f->bf_ks[0];
+    return GR4HIP_OK;
+}
+// (first use) the A fragments of the f32 MFMA kernels (fir_batched.hip): the block-Toeplitz form without decimation, the polyphase form with it
+static int fir_mfma_table(gr4hip_fir* f, hipStream_t st) {
+    if (f->mKS != 0) return GR4HIP_OK;
+    if (f->decim == 1) fir_mfma_make_afrag(f->taps.data(), f->ntaps, 1, &f->mKp, &f->mKS, &f->afrag_host);
+    else fir_mfma_make_afrag_decim(f->taps.data(), f->ntaps, f->decim, &f->mKp, &f->mKS, &f->afrag_host);
+    const int rc = fir_upload_table(f->d_afrag, f->afrag_host, st);
+    if (rc) f->mKS = 0;
+    return rc;
+}
+
+// does the f16 band-form decimator (fir_decim_f16.hip: D = 4 / 8 / 16 / 32, two-term f16 products, carries the filter's programs) take this call?
 static bool fir_decim_f16_shape(const gr4hip_fir_t* f, size_t n_in, const void* d_in, const void* d_out, bool hooked) {
     if (hooked && f->decim == 4 && (f->S == 2 ? 2 * f->ntaps - 1 : f->ntaps) > 577) return false; // (decimate by 4 with more than five K-steps per wave AND programs: 256 registers do not hold it without spills; the bf16 band kernel takes it)
-    // developer knobs.  Measured (G input samples/s, bf16 band kernel / this one), float decimate by 8: 64 taps 1037 / 998, 100 taps 984 / 999, 128 taps 963 / 998
-    static const size_t kMin8   = [] { const char* e = std::getenv("GR4HIP_FIR_DECIM_F16_MIN_TAPS"); return e ? (size_t)std::atoi(e) : (size_t)97; }();
-    static const size_t kMinW   = [] { const char* e = std::getenv("GR4HIP_FIR_DECIM_F16_MIN_TAPS_WIDE"); return e ? (size_t)std::atoi(e) : (size_t)33; }(); // (decimate by 16 / 32)
-    static const size_t kMinC8  = [] { const char* e = std::getenv("GR4HIP_FIR_DECIM_F16_MIN_TAPS_C8"); return e ? (size_t)std::atoi(e) : (size_t)64; }();   // (complex, decimate by 8)
-    static const size_t kMin4   = [] { const char* e = std::getenv("GR4HIP_FIR_DECIM_F16_MIN_TAPS_D4"); return e ? (size_t)std::atoi(e) : (size_t)33; }();   // (decimate by 4, float and complex: round 5)
-    const size_t D = f->decim;
-    const bool   taps_ok = (f->S == 1 && ((D == 8 && f->ntaps >= kMin8) || ((D == 16 || D == 32) && f->ntaps >= kMinW) || (D == 4 && f->ntaps >= kMin4))) ||
-                         (f->S == 2 && (((D == 16 || D == 32) && f->ntaps >= kMinW) || (D == 8 && f->ntaps >= kMinC8) || (D == 4 && f->ntaps >= kMin4)));
-    return taps_ok && f->ntaps <= 1025 && n_in * f->S >= (1u << 17) && ((reinterpret_cast<uintptr_t>(d_out) | reinterpret_cast<uintptr_t>(d_in)) & 15) == 0 && f->algo == GR4HIP_FIR_AUTO && !f->f32_user &&
-           !f->bf16_user && !dev_switch(kDevFirNoBf16x3) && !dev_switch(kDevFirNoF16x2) && !dev_switch(kDevFirNoDecimF16) && f->dhKQ >= 0;
+    const size_t D = f->decim, K = f->ntaps;
+    const bool   taps_ok = (f->S == 1 && ((D == 8 && K >= kDecimF16MinTaps8) || ((D == 16 || D == 32) && K >= kDecimF16MinTapsW) || (D == 4 && K >= kDecimF16MinTaps4))) ||
+                           (f->S == 2 && (((D == 16 || D == 32) && K >= kDecimF16MinTapsW) || (D == 8 && K >= kDecimF16MinTapsC8) || (D == 4 && K >= kDecimF16MinTaps4)));
+    return taps_ok && K <= 1025 && n_in * f->S >= (1u << 17) && al16(d_out) && al16(d_in) && f->algo == GR4HIP_FIR_AUTO && !f->f32_user && !f->bf16_user &&
+           !dev_switch(kDevFirNoBf16x3) && !dev_switch(kDevFirNoF16x2) && !dev_switch(kDevFirNoDecimF16) && f->dhKQ >= 0;
 }
+// does the band-form bf16 decimator (fir_bf16.hip) take this call?  Builds its fragments on first use.
 static bool fir_decim_bf16_ready(gr4hip_fir_t* f, size_t n_in, const void* d_in, const void* d_out, int* rc, hipStream_t st) {
     *rc = GR4HIP_OK;
     if (!(f->decim >= (f->S == 1 ? (size_t)2 : (size_t)3) && f->decim <= (f->S == 1 ? (size_t)12 : (size_t)16) && n_in / f->decim >= (1u << 14) && f->algo == GR4HIP_FIR_AUTO && f->bdKS >= 0 &&
-          ((reinterpret_cast<uintptr_t>(d_out) | reinterpret_cast<uintptr_t>(d_in)) & 15) == 0 && !no_bf16x3(f)))
+          al16(d_out) && al16(d_in) && !no_bf16x3(f)))
         return false;
     if (f->bdKS == 0) {
-        std::vector<unsigned short> af;
-        int                         ks = 0;
-        fir_decim_bf16_make_afrag(f->taps.data(), f->ntaps, f->decim, &ks, &f->bdHb, &af, f->S == 2);
+        int ks = 0;
+        fir_decim_bf16_make_afrag(f->taps.data(), f->ntaps, f->decim, &ks, &f->bdHb, &f->bdfrag_host, f->S == 2);
         if (ks == 0 || (f->S == 1 && f->decim == 8 && ks > 9 && f->ntaps <= 1024)) f->bdKS = -1; // the window does not fit -- or decimate-by-8 with a long window, where the
                                                                                                   // frequency-domain kernel is faster (762 against 305 G input samples/s at 1024 taps)
         else {
-            *rc = f->d_bdfrag.ensure(af.size() * sizeof(unsigned short));
-            if (!*rc) { hipError_t e = hipMemcpyAsync(f->d_bdfrag.ptr, af.data(), af.size() * sizeof(unsigned short), hipMemcpyHostToDevice, st); if (e != hipSuccess) { set_error("fir: upload failed: %s", hipGetErrorString(e)); *rc = GR4HIP_RUNTIME_ERROR; } }
-            if (*rc) return false;
+            if ((*rc = fir_upload_table(f->d_bdfrag, f->bdfrag_host, st))) return false;
             f->bdKS = ks;
         }
     }
     return f->bdKS > 0;
 }
-static int fir_process_core(gr4hip_fir_t* f, const void* d_in, size_t n_in, void* d_out, gr4hip_stream_t stream, const FirHooks& hk);
+// the band form of the decimating contraction (fir_batched.hip: samples in stream order, the decimation in the A operand).  Declines when its tile does not fit the LDS.
+static int fir_band(FirCall& c) {
+    gr4hip_fir* f = c.f;
+    if (f->bandKp == 0) {
+        fir_decim_band_make_row(f->taps.data(), f->ntaps, f->decim, &f->bandKp, &f->band_host);
+        if (const int rc = fir_upload_table(f->d_band, f->band_host, c.st)) { f->bandKp = 0; return rc; }
+    }
+    const int rc = fir_decim_band_launch((int)f->decim, f->bandKp, c.x, c.hist, (int)f->hcap, (const float*)f->d_band.ptr, c.y, (long)c.n_out, (long)c.n_in, c.st);
+    if (rc == GR4HIP_UNSUPPORTED) return GR4HIP_OK;
+    return rc ? rc : c.took_unjudged(false);
+}
 
-int gr4hip_fir_process(gr4hip_fir_t* f, const void* d_in, size_t n_in, void* d_out, size_t* n_out_p, gr4hip_stream_t stream) {
+// ---- the paths, in the order fir_process_core tries them.  Each returns GR4HIP_OK having taken the span (c.done == n_in) or, the fast convolution, its first part --
+// or having declined (c.done as it was); anything else is an error.
+
+// complex, no decimation, 33 .. 256 taps, long 16-byte-aligned span: the f16 direct form (path 2) takes it
+static bool fir_cf16_shape(const FirCall& c) {
+    const gr4hip_fir* f = c.f;
+    return f->S == 2 && f->decim == 1 && f->ntaps > 32 && f->ntaps <= 256 && c.n_in - c.done >= kMfmaMinSamples / 2 && al16(c.x + c.done * 2) && al16(c.y + c.done * 2) && fir_cf16_ok(c);
+}
+
+// 1. complex, no decimation, 97 .. 256 taps, long input path 2 does not take (unaligned, developer switches, TIME_DOMAIN_BF16X3): whole 8192-sample frames through
+// the fused FFT -> xH -> inverse kernel (chain_fused.hip: 2 transforms per frame instead of 1024 flop per sample); the direct form finishes the remainder.  (<= 96 taps
+// the direct form is faster and has no dynamic-range floor: 300 .. 356 Gsamples/s up to 64 taps, 311 .. 275 at 65 .. 96 on the bf16 matrix pipe, against 248 at every
+// tap count here, tools/cfir_taps_sweep.py.  Path 2 is as fast at 256 taps and faster below -- 129 / 192 / 256 taps 288 / 255 / 237 against 241 / 242 / 240 --, its
+// error is relative to the output and the call stays asynchronous.)  Guard (the chain's policy, include/gr4hip.h): the error floor is ~2e-6 of the INPUT rms, so it
+// shows below an output / input power ratio of 0.04.  Strict: every frame judged behind the launch, the marked ones evaluated again in float64 (fir_judge_kernel +
+// fir_exact_kernel).  Deferred: a stream's first call probes eight frames synchronously.  An earlier launch's measurement, once it has arrived, moves a stream that
+// rejects most of its input to the direct form for good.
+static int fir_path_cfast(FirCall& c) {
+    gr4hip_fir* f = c.f;
+    if (!(f->S == 2 && f->decim == 1 && f->ntaps > 96 && f->ntaps <= 256 && c.n_in >= kFdMinFrames * kFdFrame && c.algo == GR4HIP_FIR_AUTO && !f->fd_blocked &&
+          !fir_cf16_shape(c)))
+        return GR4HIP_OK;
+    int rc = GR4HIP_OK;
+    if (!f->fd) {
+        rc = chain_fused_create(&f->fd, f->taps.data(), f->ntaps, kFdFrame, GR4HIP_WIN_NONE, GR4HIP_CHAIN_FUSED_FD);
+        if (!rc && f->ntaps > 1 && f->guard_mode != GR4HIP_GUARD_OFF) chain_fused_set_measure(f->fd, true);
+    }
+    if (!rc) rc = f->d_hist256.ensure(256 * sizeof(float2));
+    if (rc) return rc;
+    const float* h256 = (const float*)f->d_hist256.ptr;
+    hipLaunchKernelGGL(fir_hist_widen_kernel<float2>, dim3(1), dim3(256), 0, c.st, (const float2*)c.hist, (int)f->hcap, (float2*)f->d_hist256.ptr, 256);
+    GR4_LAUNCH_CHECK();
+    const size_t frames  = c.n_in / kFdFrame; // >= kFdMinFrames: more than a probe
+    const bool   guarded = f->ntaps > 1 && f->guard_mode != GR4HIP_GUARD_OFF;
+    const bool   strict  = guarded && f->guard_mode == GR4HIP_GUARD_STRICT;
+    float        ratio;
+    if (chain_fused_power_ratio(f->fd, false, true, &ratio)) f->fd_ratio = ratio; // a finished earlier launch: no waiting
+    size_t probe = 0;
+    if (guarded && !strict && !f->fd_probed) {
+        probe = std::min<size_t>(frames, 8);
+        if ((rc = chain_fused_fir(f->fd, c.x, h256, probe, c.y, c.st))) return rc;
+        if (chain_fused_power_ratio(f->fd, true, true, &ratio)) f->fd_ratio = ratio;
+    }
+    if (guarded) f->fd_probed = true;
+    if (guarded && f->fd_ratio >= 0.f && f->fd_ratio < 0.04f) {
+        f->fd_blocked = f->f32_products = true; // the direct form takes the span, the probed frames too (float32 products from here on)
+        return GR4HIP_OK;
+    }
+    const long nfd = (long)(frames * kFdFrame);
+    rc = chain_fused_fir(f->fd, c.x + probe * kFdFrame * 2, probe ? c.x + (probe * kFdFrame - 256) * 2 : h256, frames - probe, c.y + probe * kFdFrame * 2, c.st);
+    if (!rc && strict) {
+        rc = f->d_flags_fd.ensure(frames);
+        if (!rc) rc = fir_judge_launch(c.x, nfd, c.y, nfd, 1, 1, 13, 0.04f, (unsigned char*)f->d_flags_fd.ptr, c.st);
+        if (!rc) rc = fir_exact_launch(c.x, nfd, c.hist, (int)f->hcap, (const float*)f->d_tapsf.ptr, (int)f->ntaps, 1, 1, c.y, nfd, (const unsigned char*)f->d_flags_fd.ptr, 13, nullptr, c.st);
+    }
+    if (rc) return rc;
+    c.done = (size_t)nfd;
+    c.hist = c.x + (c.done - f->hcap) * 2; // the hcap samples in front of the remainder are part of the input itself
+    return GR4HIP_OK;
+}
+
+// 2. complex, no decimation, 33 .. 256 taps, what the fast convolution did not take: the block-Toeplitz product on the f16 matrix pipe, two-term splits under a
+// per-segment block exponent (fir_f16.hip).  Every segment judges itself; the marked ones get float64 products behind the launch (FP64 matrix pipe, fir_exact.hip).
+static int fir_path_cf16(FirCall& c) {
+    gr4hip_fir* f = c.f;
+    if (!fir_cf16_shape(c)) return GR4HIP_OK;
+    if (const int rc = fir_f16_tables(f, c.st, false, true)) return rc;
+    if (f->hfKS <= 0) return GR4HIP_OK;
+    float*       nh   = c.done == 0 ? c.next_hist() : nullptr;
+    const long   nrem = (long)(c.n_in - c.done);
+    const float* xr   = c.x + c.done * 2;
+    float*       yr   = c.y + c.done * 2;
+    int          rc   = f->d_flags.ensure((size_t)ceil_div(nrem, 2048L));
+    if (!rc) rc = fir_f16_c32_launch(f->hfKS, xr, nrem, c.hist, (int)f->hcap, f->d_hfrag.ptr, yr, c.st, nh, f->guard_mode != GR4HIP_GUARD_OFF, (unsigned char*)f->d_flags.ptr);
+    if (!rc) rc = fir_exact_launch(xr, nrem, c.hist, (int)f->hcap, (const float*)f->d_tapsf.ptr, (int)f->ntaps, 1, 1, yr, nrem, (const unsigned char*)f->d_flags.ptr, 11, nullptr, c.st);
+    return rc ? rc : c.took(nh != nullptr);
+}
+
+// 3. complex, no decimation, 257 .. 1792 taps (seven slices: a slice's window and its delay must fit the kernel's 2048-sample segment): slices of 256 taps on the
+// same kernel, each a pass over the input delayed by 256 p samples that adds to y (the f32 matrix pipe at its peak managed 512 taps 36 Gsamples/s, 1024 taps 17).
+// The last slice judges the sums against the whole filter's threshold; marked segments again with all the taps on the FP64 matrix pipe.
+static int fir_path_cf16_slices(FirCall& c) {
+    gr4hip_fir* f = c.f;
+    if (!(f->S == 2 && f->decim == 1 && f->ntaps > 256 && f->ntaps <= 1792 && c.done == 0 && c.n_in >= kMfmaMinSamples / 2 && al16(c.x) && al16(c.y) && fir_cf16_ok(c)))
+        return GR4HIP_OK;
+    if (const int rc = fir_f16_tables(f, c.st, true, true)) return rc;
+    if (f->hfKS <= 0) return GR4HIP_OK;
+    const size_t nslice = ceil_div(f->ntaps, (size_t)256);
+    const bool   judged = f->guard_mode != GR4HIP_GUARD_OFF;
+    int          rc     = f->d_flags.ensure((size_t)ceil_div((long)c.n_in, 2048L));
+    for (size_t p = 0; p < nslice && !rc; ++p)
+        rc = fir_f16_c32_launch(f->hf_ks[p], c.x, (long)c.n_in, c.hist, (int)f->hcap, (const unsigned short*)f->d_hfrag.ptr + f->hf_off[p], c.y, c.st, p == 0 ? c.next_hist() : nullptr,
+                                p + 1 == nslice && judged, (unsigned char*)f->d_flags.ptr, (int)(256 * p), p > 0, (float)(f->tap_power * kGuardSegmentRatio));
+    if (!rc) rc = fir_exact_launch(c.x, (long)c.n_in, c.hist, (int)f->hcap, (const float*)f->d_tapsf.ptr, (int)f->ntaps, 1, 1, c.y, (long)c.n_in, (const unsigned char*)f->d_flags.ptr, 11, nullptr, c.st);
+    return rc ? rc : c.took(true);
+}
+
+// 4. complex, no decimation, kCBf16MinTaps .. 256 taps, long 16-byte-aligned span the f16 kernels do not take: the three-term bf16 form of the same product (fir_bf16.hip)
+static int fir_path_cbf16(FirCall& c) {
+    gr4hip_fir* f = c.f;
+    if (!(f->S == 2 && f->decim == 1 && f->ntaps >= kCBf16MinTaps && f->ntaps <= 256 && c.n_in - c.done >= kMfmaMinSamples / 2 && al16(c.x + c.done * 2) &&
+          al16(c.y + c.done * 2) && !no_bf16x3(f) && c.plain))
+        return GR4HIP_OK;
+    if (const int rc = fir_bf16_tables(f, c.st)) return rc;
+    float* nh = c.done == 0 ? c.next_hist() : nullptr;
+    if (const int rc = fir_bf16_c32_launch(f->bfKS, c.x + c.done * 2, (long)(c.n_in - c.done), c.hist, (int)f->hcap, f->d_bfrag.ptr, c.y + c.done * 2, c.st, nh)) return rc;
+    return c.took_unjudged(nh != nullptr);
+}
+
+// 5. complex, no decimation, 33 .. 256 taps, long span with a 16-byte-aligned output: the same product on the f32 MFMA units (fir_mfma_c32_kernel)
+static int fir_path_cmfma(FirCall& c) {
+    gr4hip_fir* f = c.f;
+    if (!(c.algo != GR4HIP_FIR_EXACT_F32 && f->S == 2 && f->decim == 1 && f->ntaps > 32 && f->ntaps <= 256 && c.n_in - c.done >= kMfmaMinSamples / 2 && al16(c.y + c.done * 2)))
+        return GR4HIP_OK;
+    if (const int rc = fir_mfma_table(f, c.st)) return rc;
+    const float* hw = c.hist; // (hcap = bit_ceil(ntaps) is Kp for 33 .. 256 taps: read in place; a span served by this launch alone also gets its next history from it)
+    if ((int)f->hcap != f->mKp) {
+        if (const int rc = f->d_histc.ensure(256 * sizeof(float2))) return rc;
+        hipLaunchKernelGGL(fir_hist_widen_kernel<float2>, dim3(1), dim3(256), 0, c.st, (const float2*)c.hist, (int)f->hcap, (float2*)f->d_histc.ptr, f->mKp);
+        GR4_LAUNCH_CHECK();
+        hw = (const float*)f->d_histc.ptr;
+    }
+    float* nh = (c.done == 0 && (int)f->hcap == f->mKp) ? c.next_hist() : nullptr;
+    if (const int rc = fir_mfma_c32_launch(f->mKS, c.x + c.done * 2, (long)(c.n_in - c.done), hw, (const float*)f->d_afrag.ptr, c.y + c.done * 2, c.st, nh)) return rc;
+    return c.took_unjudged(nh != nullptr);
+}
+
+// 6. float, no decimation, 33 .. 3840 taps, long 16-byte-aligned span: the block-Toeplitz product on the f16 matrix pipe, two-term splits under a per-segment block
+// exponent (fir_f16.hip: three products per tap instead of the bf16 form's six); beyond 256 taps slices of 256, each a pass over the input delayed by 256 p samples
+// that adds to y (fifteen slices: a slice's window and delay must fit the kernel's 4096-sample segment; 257 / 300 / 383 taps 167 / 148 / 119 Gsamples/s on the other
+// kernels, 1100 taps 44).  The last slice judges the sums it leaves in y against the whole filter's threshold; marked segments -- rejected, or with samples the
+// block exponent cannot carry in ANY slice -- are evaluated again with all the taps on the FP64 matrix pipe.
+static int fir_path_rf16(FirCall& c) {
+    gr4hip_fir* f = c.f;
+    if (!(f->S == 1 && f->decim == 1 && f->ntaps > 32 && f->ntaps <= 3840 && c.n_in >= kMfmaMinSamples && al16(c.x) && al16(c.y) && fir_rf16_ok(c))) return GR4HIP_OK;
+    if (const int rc = fir_f16_tables(f, c.st, false, false)) return rc;
+    if (f->hfKS <= 0) return GR4HIP_OK;
+    const size_t nslice = ceil_div(f->ntaps, (size_t)256);
+    const float  gthr   = (nslice > 1 || f->guard_ratio != kGuardSegmentRatio) ? (float)(f->tap_power * f->guard_ratio) : 0.f;
+    int          rc     = f->d_flags.ensure(ceil_div(c.n_in, (size_t)4096));
+    for (size_t p = 0; p < nslice && !rc; ++p)
+        rc = fir_f16_launch(f->hf_ks[p], c.x, (long)c.n_in, c.hist, (int)f->hcap, (const unsigned short*)f->d_hfrag.ptr + f->hf_off[p], c.y, c.st, p == 0 ? c.next_hist() : nullptr, 0, 0, 1,
+                            (int)(256 * p), p > 0, p + 1 == nslice && f->guard_mode != GR4HIP_GUARD_OFF, (unsigned char*)f->d_flags.ptr, 0, gthr);
+    if (!rc) rc = fir_exact_launch(c.x, (long)c.n_in, c.hist, (int)f->hcap, (const float*)f->d_tapsf.ptr, (int)f->ntaps, 1, 0, c.y, (long)c.n_in, (const unsigned char*)f->d_flags.ptr, 12, nullptr, c.st);
+    return rc ? rc : c.took(true);
+}
+
+// 7. float, no decimation, 33 .. 256 or 384 .. 1024 taps, long 16-byte-aligned span the f16 kernel does not take: the product on the bf16 matrix pipe with three-term
+// splits of samples and taps (fir_bf16.hip: float32 accuracy, 2.4 times less matrix-pipe time than the f32 MFMA), slices of 256 taps beyond 256 (512 taps 115 instead
+// of 90 Gsamples/s on the register-window kernel, 1024 taps 50.5 instead of 47; below 384 and above 1024 taps the extra passes cost more than they save)
+static int fir_path_rbf16(FirCall& c) {
+    gr4hip_fir* f = c.f;
+    if (!(c.done == 0 && f->S == 1 && f->decim == 1 && f->ntaps > 32 && (f->ntaps <= 256 || (f->ntaps >= 384 && f->ntaps <= 1024)) && c.n_in >= kMfmaMinSamples && al16(c.x) &&
+          al16(c.y) && c.algo == GR4HIP_FIR_AUTO && !no_bf16x3(f) && c.plain))
+        return GR4HIP_OK;
+    if (const int rc = fir_bf16_tables(f, c.st)) return rc;
+    const size_t nslice = ceil_div(f->ntaps, (size_t)256);
+    int          rc     = GR4HIP_OK;
+    for (size_t p = 0; p < nslice && !rc; ++p)
+        rc = fir_bf16_launch(f->bf_ks[p], c.x, (long)c.n_in, c.hist, (int)f->hcap, (const unsigned short*)f->d_bfrag.ptr + f->bf_off[p], c.y, c.st, p == 0 ? c.next_hist() : nullptr, 0, 0,
+                             1, (int)(256 * p), p > 0);
+    return rc ? rc : c.took_unjudged(true);
+}
+
+// 8. float, no decimation, 33 .. 256 taps, long span with a 16-byte-aligned output: block-Toeplitz product on the f32 MFMA units (about twice the rate of the
+// register-window VALU kernel, which is FP32-issue bound from ~48 taps on)
+static int fir_path_rmfma(FirCall& c) {
+    gr4hip_fir* f = c.f;
+    if (!(c.algo != GR4HIP_FIR_EXACT_F32 && c.done == 0 && f->S == 1 && f->decim == 1 && f->ntaps > 32 && f->ntaps <= 256 && c.n_in >= kMfmaMinSamples && al16(c.y)))
+        return GR4HIP_OK;
+    if (const int rc = fir_mfma_table(f, c.st)) return rc;
+    // hcap = bit_ceil(ntaps) IS Kp for 33 .. 256 taps: the block's history is read as it lies, and the launch writes the next one (one launch per call instead of
+    // three: what a scheduler's 64 Ki-sample chunks cost is launches)
+    const float* hw = c.hist;
+    if ((int)f->hcap != f->mKp) {
+        if (const int rc = f->d_hist256.ensure(256 * sizeof(float2))) return rc;
+        hipLaunchKernelGGL(fir_hist_widen_kernel<float>, dim3(1), dim3(256), 0, c.st, c.hist, (int)f->hcap, (float*)f->d_hist256.ptr, f->mKp);
+        GR4_LAUNCH_CHECK();
+        hw = (const float*)f->d_hist256.ptr;
+    }
+    float* nh = (int)f->hcap == f->mKp ? c.next_hist() : nullptr;
+    if (const int rc = fir_mfma_launch(f->mKS, c.x, (long)c.n_in, hw, (const float*)f->d_afrag.ptr, c.y, (long)((c.n_in + 3) & ~(size_t)3), (long)c.n_in, 1, c.st, nh)) return rc;
+    return c.took_unjudged(nh != nullptr);
+}
+
+// 9. float or complex, decimate by 4 / 8 / 16 / 32 (BASELINE configs[2]: float, by 8, 1024 taps), long 16-byte-aligned span: the band form on the f16 matrix pipe,
+// two-term splits under a per-segment block exponent, the K-steps split over the four waves (fir_decim_f16.hip).  Every segment is judged in the launch; the marked
+// ones are evaluated again on the FP64 matrix pipe behind it (in samples: a complex segment is half as many outputs).  Its error is relative to the output, so it
+// needs no host-side guard and the call stays asynchronous.  Hooked calls too: the kernel carries the programs, fir_exact_kernel<true> runs them again.
+static int fir_path_decim_f16(FirCall& c) {
+    gr4hip_fir* f = c.f;
+    if (!(c.done == 0 && fir_decim_f16_shape(f, c.n_in, c.x, c.y, c.hk.any))) return GR4HIP_OK;
+    if (f->dhKQ == 0) {
+        if (!fir_decim_f16_make_table(f->taps.data(), f->ntaps, f->decim, &f->dhKQ, &f->dhtab_host, f->S == 2)) f->dhKQ = -1;
+        else if (const int rc = fir_upload_table(f->d_dhtab, f->dhtab_host, c.st)) { f->dhKQ = 0; return rc; }
+    }
+    if (f->dhKQ <= 0) return GR4HIP_OK;
+    const long segf = 8192 / (long)f->decim; // the kernel's segment: 8192 input floats = this many output floats
+    int        rc   = f->d_flags.ensure((size_t)ceil_div((long)(c.n_out * f->S), segf));
+    if (!rc)
+        rc = fir_decim_f16_launch((int)f->decim, f->dhKQ, c.x, (long)(c.n_in * f->S), c.hist, (int)(f->hcap * f->S), f->d_dhtab.ptr, c.y, (long)(c.n_out * f->S), c.st, c.next_hist(),
+                                  f->guard_mode != GR4HIP_GUARD_OFF, (unsigned char*)f->d_flags.ptr, f->S == 2, &c.hk.pre, &c.hk.post);
+    if (!rc)
+        rc = fir_exact_launch(c.x, (long)c.n_in, c.hist, (int)f->hcap, (const float*)f->d_tapsf.ptr, (int)f->ntaps, (int)f->decim, f->S == 2, c.y, (long)c.n_out, (const unsigned char*)f->d_flags.ptr,
+                              ilog2((size_t)(segf / f->S)), nullptr, c.st, 1, 0, 0, 0, 0, &c.hk.pre, &c.hk.post);
+    return rc ? rc : c.took(true);
+}
+
+// 10. float, decimate by 2 .. 12, or complex, by 3 .. 16, window <= 1152 samples, long 16-byte-aligned span: the band form with three-term bf16 products
+// (fir_bf16.hip; complex: the rows of a tile alternate between the re and im phases of the window).  The register-window kernel stages a decimator's samples one by
+// one (decimate by 8, 64 taps: 171 G input samples/s against 483 here; by 16: 97 against 445; by 2 it is ahead: 389 / 307 against 348 / 252 at 16 / 64 taps).  The
+// kernels carry the neighbours' programs and judge every segment; the marked ones are evaluated again on the FP64 matrix pipe, programs included.
+static int fir_path_decim_bf16(FirCall& c) {
+    gr4hip_fir* f  = c.f;
+    int         rc = GR4HIP_OK;
+    if (c.done != 0 || !fir_decim_bf16_ready(f, c.n_in, c.x, c.y, &rc, c.st)) return rc;
+    const bool judged  = f->guard_mode != GR4HIP_GUARD_OFF && f->ntaps > 1;
+    int        seg_out = 0;
+    if (judged) { if ((rc = f->d_flags.ensure((size_t)ceil_div((long)(c.n_out * f->S), 512L)))) return rc; }
+    rc = fir_decim_bf16_launch(f->bdKS, (int)f->decim, f->bdHb, c.x, (long)(c.n_in * f->S), c.hist, (int)(f->hcap * f->S), f->d_bdfrag.ptr, c.y, (long)(c.n_out * f->S), c.st, c.next_hist(),
+                               c.hk.pre.n_ops > 0 ? &c.hk.pre : nullptr, c.hk.post.n_ops > 0 ? &c.hk.post : nullptr, f->S == 2, judged ? (unsigned char*)f->d_flags.ptr : nullptr,
+                               (float)(f->tap_power * f->guard_ratio), &seg_out);
+    if (rc == GR4HIP_OK && judged)
+        rc = fir_exact_launch(c.x, (long)c.n_in, c.hist, (int)f->hcap, (const float*)f->d_tapsf.ptr, (int)f->ntaps, (int)f->decim, f->S == 2, c.y, (long)c.n_out, (const unsigned char*)f->d_flags.ptr,
+                              ilog2((size_t)(seg_out / f->S)), nullptr, c.st, 1, 0, 0, 0, 0, &c.hk.pre, &c.hk.post);
+    if (rc == GR4HIP_OK) return c.took(true);
+    if (rc != GR4HIP_UNSUPPORTED) return rc;
+    f->bdKS = -1; // (the staged segment does not fit: do not ask again)
+    return GR4HIP_OK;
+}
+
+// 11. float, decimate by 8, <= 1024 taps, long span with a 16-byte-aligned input: overlap-save blocks of 8192 samples in the frequency domain (fir_decim_fd.hip: ~35
+// lane-operations per input sample instead of 2 K / 8 flop), the partial last block in the same launch (through the polyphase kernel it cost a 44 us launch behind
+// a 164 us transform kernel).  The guard of path 1 at kDecimFdMinPowerRatio (an anti-alias filter is where strong out-of-band power is removed): strict, segments
+// of 2048 outputs judged behind the launch and the marked ones evaluated again in float64; an earlier launch's measurement moves the stream off for good.
+static int fir_path_decim_fd(FirCall& c) {
+    gr4hip_fir* f = c.f;
+    if (!(c.done == 0 && f->S == 1 && c.algo == GR4HIP_FIR_AUTO && !f->fd_blocked && fir_decim_fd_supported(f->ntaps, f->decim) && f->ntaps <= 1024 && c.n_in >= kDfMinBlocks * kDfHopS &&
+          al16(c.x) && !dev_switch(kDevFirNoDecimFd)))
+        return GR4HIP_OK;
+    int rc = GR4HIP_OK;
+    if (!f->dfd && (rc = fir_decim_fd_create(&f->dfd, f->taps.data(), f->ntaps))) return rc;
+    const bool guarded = f->guard_mode != GR4HIP_GUARD_OFF && f->ntaps > 1;
+    float      ratio;
+    if (guarded && fir_decim_fd_power_ratio(f->dfd, false, &ratio)) f->fd_ratio = ratio;
+    if (guarded && f->fd_ratio >= 0.f && f->fd_ratio < kDecimFdMinPowerRatio) f->fd_blocked = f->f32_products = true;
+    if (f->fd_blocked) return GR4HIP_OK;
+    if ((rc = fir_decim_fd_run(f->dfd, c.x, c.n_in, c.hist, (int)f->hcap, c.y, c.st, guarded))) return rc;
+    c.took(false);
+    if (guarded && f->guard_mode == GR4HIP_GUARD_STRICT) {
+        rc = f->d_flags_fd.ensure((size_t)ceil_div((long)c.n_out, 2048L));
+        if (!rc) rc = fir_judge_launch(c.x, (long)c.n_in, c.y, (long)c.n_out, (int)f->decim, 0, 11, kDecimFdMinPowerRatio, (unsigned char*)f->d_flags_fd.ptr, c.st);
+        if (!rc)
+            rc = fir_exact_launch(c.x, (long)c.n_in, c.hist, (int)f->hcap, (const float*)f->d_tapsf.ptr, (int)f->ntaps, (int)f->decim, 0, c.y, (long)c.n_out, (const unsigned char*)f->d_flags_fd.ptr,
+                                  11, nullptr, c.st);
+        if (rc && rc != GR4HIP_UNSUPPORTED) return rc;
+    }
+    return GR4HIP_OK;
+}
+
+// 12. float, decimate by kBandMinDecim .. 128, long span: the band form
+static int fir_path_band(FirCall& c) {
+    const gr4hip_fir* f = c.f;
+    if (!(c.done == 0 && f->S == 1 && f->decim >= kBandMinDecim && f->decim <= 128 && c.n_out >= (1u << 14) && c.algo == GR4HIP_FIR_AUTO)) return GR4HIP_OK;
+    return fir_band(c);
+}
+
+// 13. float polyphase decimator with 16 .. 256 taps per phase and a long span with a 16-byte-aligned output: the f32 MFMA contraction with the D phase products summed
+// in one accumulator tile.  Declines when the de-interleaved segment does not fit the LDS.
+static int fir_path_decim_mfma(FirCall& c) {
+    gr4hip_fir* f = c.f;
+    if (!(c.algo != GR4HIP_FIR_EXACT_F32 && c.done == 0 && f->S == 1 && f->decim >= 2 && ceil_div(f->ntaps, f->decim) >= 16 && ceil_div(f->ntaps, f->decim) <= 256 &&
+          c.n_out >= (1u << 14) && al16(c.y)))
+        return GR4HIP_OK;
+    if (const int rc = fir_mfma_table(f, c.st)) return rc;
+    const int hl = f->mKp * (int)f->decim; // history the kernel wants: Kp D samples
+    if (const int rc = f->d_hist256.ensure((size_t)hl * sizeof(float))) return rc;
+    const int hu = (int)std::min<size_t>(f->hcap, (size_t)hl); // newest hu samples of the block's history are what the kernel can see
+    hipLaunchKernelGGL(fir_hist_widen_kernel<float>, dim3((unsigned)ceil_div(hl, 256)), dim3(256), 0, c.st, c.hist + (f->hcap - hu), hu, (float*)f->d_hist256.ptr, hl);
+    GR4_LAUNCH_CHECK();
+    const int rc = fir_mfma_decim_launch(f->mKS, (int)f->decim, c.x, (const float*)f->d_hist256.ptr, (const float*)f->d_afrag.ptr, c.y, (long)c.n_out, c.st);
+    if (rc == GR4HIP_UNSUPPORTED) return GR4HIP_OK;
+    return rc ? rc : c.took_unjudged(false);
+}
+
+// 14. the register-window kernel of this file at the largest workgroup size whose D phase rows fit the LDS; the only kernel that takes the rest of a span, and
+// hooked calls of every shape the band-form decimators do not take.  It judges itself.
+static int fir_path_window(FirCall& c) {
+    const gr4hip_fir* f = c.f;
+    const int         E = 4 / f->S;
+    for (int bs : {256, 128, 64}) {
+        const size_t Lf  = (size_t)bs * kFirR + 4 * (size_t)f->G;
+        const size_t lds = f->decim * (Lf + (size_t)f->G * E) * sizeof(float);
+        if (lds > 150 * 1024) continue;
+        const float* xr = c.x + c.done * f->S;
+        float*       yr = c.y + (c.done / f->decim) * f->S;
+        const long   ni = (long)(c.n_in - c.done), no = (long)((c.n_in - c.done) / f->decim);
+        float*       nh = c.done == 0 ? c.next_hist() : nullptr; // the whole span in this launch: it writes the next history itself
+        int          rc;
+        if (f->S == 1) rc = bs == 256 ? fir_launch<1, 256>(f, xr, c.hist, yr, ni, no, lds, c.st, nh, c.hk) : bs == 128 ? fir_launch<1, 128>(f, xr, c.hist, yr, ni, no, lds, c.st, nh, c.hk) : fir_launch<1, 64>(f, xr, c.hist, yr, ni, no, lds, c.st, nh, c.hk);
+        else rc = bs == 256 ? fir_launch<2, 256>(f, xr, c.hist, yr, ni, no, lds, c.st, nh, c.hk) : bs == 128 ? fir_launch<2, 128>(f, xr, c.hist, yr, ni, no, lds, c.st, nh, c.hk) : fir_launch<2, 64>(f, xr, c.hist, yr, ni, no, lds, c.st, nh, c.hk);
+        return rc ? rc : c.took(nh != nullptr);
+    }
+    return GR4HIP_OK;
+}
+
+// 15. float decimator whose D phase rows do not fit the LDS at any workgroup size: the band form at any span length
+static int fir_path_band_fallback(FirCall& c) {
+    if (!(c.done == 0 && c.f->S == 1 && c.f->decim >= 2 && c.plain)) return GR4HIP_OK;
+    return fir_band(c);
+}
+
+// 16. no tiling fits (decimation x taps beyond every LDS tiling, e.g. complex data decimated by 100): the one-output-per-lane kernel
+static int fir_path_generic(FirCall& c) {
+    const gr4hip_fir* f = c.f;
+    if (!(c.done == 0 && c.plain)) return GR4HIP_OK;
+    const unsigned g = (unsigned)ceil_div((long)c.n_out, 256L);
+    if (f->S == 1) hipLaunchKernelGGL(fir_generic_kernel<1>, dim3(g), dim3(256), 0, c.st, c.x, c.hist, (int)f->hcap, (const float*)f->d_tapsf.ptr, (int)f->ntaps, (long)f->decim, c.y, (long)c.n_out, (long)c.n_in);
+    else hipLaunchKernelGGL(fir_generic_kernel<2>, dim3(g), dim3(256), 0, c.st, c.x, c.hist, (int)f->hcap, (const float*)f->d_tapsf.ptr, (int)f->ntaps, (long)f->decim, c.y, (long)c.n_out, (long)c.n_in);
+    GR4_LAUNCH_CHECK();
+    return c.took_unjudged(false);
+}
+
+static int fir_process_core(gr4hip_fir_t* f, const void* d_in, size_t n_in, void* d_out, gr4hip_stream_t stream, const FirHooks& hk) {
+    static int (*const kPaths[])(FirCall&) = {fir_path_cfast, fir_path_cf16, fir_path_cf16_slices, fir_path_cbf16, fir_path_cmfma, fir_path_rf16, fir_path_rbf16, fir_path_rmfma,
+                                              fir_path_decim_f16, fir_path_decim_bf16, fir_path_decim_fd, fir_path_band, fir_path_decim_mfma, fir_path_window, fir_path_band_fallback,
+                                              fir_path_generic};
+    // hooks run in the register-window kernel and the band-form decimators only: the matrix-pipe and frequency-domain kernels are for plain filters
+    FirCall c{f, static_cast<const float*>(d_in), static_cast<float*>(d_out), n_in, n_in / f->decim, as_stream(stream), hk, !hk.any, hk.any ? (int)GR4HIP_FIR_EXACT_F32 : f->algo,
+              (const float*)f->d_hist[f->cur].ptr};
+    for (auto path : kPaths) {
+        if (c.done == n_in) break;
+        if (const int rc = path(c)) return rc;
+    }
+    if (c.done != n_in) { set_error("fir_process: ntaps=%zu decim=%zu does not fit the LDS tiling", f->ntaps, f->decim); return GR4HIP_UNSUPPORTED; }
+    // the guard's verdict and second evaluation behind a kernel that does not judge itself
+    if (c.unj_from != SIZE_MAX && f->guard_mode != GR4HIP_GUARD_OFF && f->ntaps > 1) {
+        const long   ni = (long)(n_in - c.unj_from), no = ni / (long)f->decim;
+        const int    shift = f->S == 2 ? 10 : 11;
+        const float* xr = c.x + c.unj_from * f->S;
+        float*       yr = c.y + (c.unj_from / f->decim) * f->S;
+        if (no > 0) {
+            if (const int rc = f->d_flags.ensure((size_t)ceil_div(no, 1L << shift))) return rc;
+            if (const int rc = fir_judge_launch(xr, ni, yr, no, (int)f->decim, f->S == 2, shift, (float)(f->tap_power * kGuardSegmentRatio), (unsigned char*)f->d_flags.ptr, c.st,
+                                                f->guard_ratio != kGuardSegmentRatio ? (float)(f->tap_power * f->guard_ratio) : 0.f)) // (a tighter ratio: on the segment's whole output power -- the quietest quarter dips on narrow-band noise)
+                return rc;
+            const int rc = fir_exact_launch(xr, ni, c.unj_hist, (int)f->hcap, (const float*)f->d_tapsf.ptr, (int)f->ntaps, (int)f->decim, f->S == 2, yr, no, (const unsigned char*)f->d_flags.ptr, shift, nullptr, c.st);
+            if (rc && rc != GR4HIP_UNSUPPORTED) return rc; // (UNSUPPORTED: decimation x taps beyond what the second evaluation stages -- the float32 sums stand)
+        }
+    }
+    return fir_advance(f, c.x, n_in, c.st, c.hist_written);
+}
+
+extern "C" int gr4hip_fir_process(gr4hip_fir_t* f, const void* d_in, size_t n_in, void* d_out, size_t* n_out_p, gr4hip_stream_t stream) {
     GR4_REQUIRE(f, "fir_process: null handle");
     GR4_REQUIRE(n_in % f->decim == 0, "fir_process: n_in=%zu is not a multiple of decim=%zu", n_in, f->decim);
     const size_t n_out = n_in / f->decim;
@@ -694,496 +1188,6 @@ int gr4hip_fir_process(gr4hip_fir_t* f, const void* d_in, size_t n_in, void* d_o
     return rc;
 }
 
-} // extern "C"
-
-static int fir_process_core(gr4hip_fir_t* f, const void* d_in, size_t n_in, void* d_out, gr4hip_stream_t stream, const FirHooks& hk) {
-    const size_t n_out = n_in / f->decim;
-    hipStream_t  st   = as_stream(stream);
-    const float* x    = static_cast<const float*>(d_in);
-    float*       y    = static_cast<float*>(d_out);
-    const bool   plain = !hk.any;
-    const int    algo  = plain ? f->algo : (int)GR4HIP_FIR_EXACT_F32; // (EXACT_F32 == "the register-window kernel only") // hooks run in the register-window kernel only: the matrix-pipe and frequency-domain kernels below are for plain filters
-    const float* hist = (const float*)f->d_hist[f->cur].ptr;
-    size_t       done = 0; // samples already produced by the frequency-domain path
-    bool         mfma_wrote_hist = false;
-    // a kernel that does not judge its own segments (the float32 matrix-pipe forms, the three-term bf16 direct forms) notes here where its part of the span starts and which
-    // samples lie in front of it: fir_judge_kernel + fir_exact_kernel follow it at the end of the call (every kernel of this file answers to the same guard)
-    size_t       unj_from = SIZE_MAX;
-    const float* unj_hist = nullptr;
-    // complex<float>, no decimation, <= 256 taps, long input: whole 8192-sample frames go through the fused FFT -> xH -> inverse
-    // kernel (2 transforms per frame instead of 1024 flop per sample); the direct-form kernel finishes the remainder
-    // (<= 96 taps: the direct form is faster -- write-bound 300 .. 356 Gsamples/s up to 64 taps, 311 .. 275 at 65 .. 96 taps on the bf16 matrix pipe, against
-    // the fast convolution's 248 at every tap count, tools/cfir_taps_sweep.py -- and has no dynamic-range floor; 128 taps: 220, 256 taps: 151)
-    // (round 4: the direct form on the f16 matrix pipe -- further down -- is as fast at 256 taps and faster below (129 taps 288 against 241, 192 taps 255 against 242,
-    // 256 taps 237 against 240 Gsamples/s, tools/cfir_taps_sweep.py), its error is relative to the output, a non-finite sample reaches ntaps outputs instead of an
-    // 8192-sample block and the call stays asynchronous: the fast convolution is left with the spans that kernel does not take -- unaligned ones)
-    const bool f16c = f->S == 2 && f->decim == 1 && f->ntaps > 32 && f->ntaps <= 256 && n_in >= kMfmaMinSamples / 2 && ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(x)) & 15) == 0 &&
-                      algo != GR4HIP_FIR_EXACT_F32 && !f->f32_user && !f->bf16_user && !dev_switch(kDevFirNoBf16x3) && !dev_switch(kDevFirNoF16x2) && f->hfKS >= 0 && plain;
-    if (f->S == 2 && f->decim == 1 && f->ntaps > 96 && f->ntaps <= 256 && n_in >= kFdMinFrames * kFdFrame && algo == GR4HIP_FIR_AUTO && !f->fd_blocked && !f16c) {
-        int rc = GR4HIP_OK;
-        if (!f->fd) {
-            rc = chain_fused_create(&f->fd, f->taps.data(), f->ntaps, kFdFrame, GR4HIP_WIN_NONE, GR4HIP_CHAIN_FUSED_FD);
-            if (!rc && f->ntaps > 1 && f->guard_mode != GR4HIP_GUARD_OFF) chain_fused_set_measure(f->fd, true);
-        }
-        if (!rc) rc = f->d_hist256.ensure(256 * sizeof(float2));
-        if (rc) return rc;
-        hipLaunchKernelGGL(fir_hist_widen_kernel<float2>, dim3(1), dim3(256), 0, st, (const float2*)hist, (int)f->hcap, (float2*)f->d_hist256.ptr, 256);
-        GR4_LAUNCH_CHECK();
-        const size_t frames = n_in / kFdFrame;
-        float        ratio;
-        const bool   guarded = f->ntaps > 1 && f->guard_mode != GR4HIP_GUARD_OFF;
-        if (guarded && f->guard_mode == GR4HIP_GUARD_STRICT) {
-            // (round 5: nobody waits) the whole span on the fast convolution; every 8192-sample frame is judged behind it at the fast convolution's own threshold -- output power
-            // below 0.04 x input power: its error floor, ~2e-6 of the INPUT rms, would show against such an output -- and the marked frames are evaluated again with float64
-            // products (fir_judge_kernel + fir_exact_kernel on the same stream).  The measurement of an EARLIER launch, when it has arrived, moves a stream that rejects most of
-            // its input to the direct form for good.
-            if (chain_fused_power_ratio(f->fd, false, true, &ratio)) f->fd_ratio = ratio;
-            f->fd_probed = true;
-            if (f->fd_ratio >= 0.f && f->fd_ratio < 0.04f) f->fd_blocked = f->f32_products = true;
-            else {
-                const long nfd = (long)(frames * kFdFrame);
-                rc = chain_fused_fir(f->fd, x, (const float*)f->d_hist256.ptr, frames, y, st);
-                if (!rc) rc = f->d_flags_fd.ensure(frames);
-                if (!rc) rc = fir_judge_launch(x, nfd, y, nfd, 1, 1, 13, 0.04f, (unsigned char*)f->d_flags_fd.ptr, st);
-                if (!rc) rc = fir_exact_launch(x, nfd, hist, (int)f->hcap, (const float*)f->d_tapsf.ptr, (int)f->ntaps, 1, 1, y, nfd, (const unsigned char*)f->d_flags_fd.ptr, 13, nullptr, st);
-                if (rc) return rc;
-                done = (size_t)nfd;
-                hist = x + (done - f->hcap) * 2;
-            }
-        } else {
-        if (chain_fused_power_ratio(f->fd, false, true, &ratio)) f->fd_ratio = ratio; // a finished earlier launch: no waiting
-        size_t probe = 0;
-        if (!f->fd_probed && guarded) { // first fast convolution of this stream: eight frames, synchronously, before the span is committed to it
-            probe = std::min<size_t>(frames, 8);
-            rc    = chain_fused_fir(f->fd, x, (const float*)f->d_hist256.ptr, probe, y, st);
-            if (rc) return rc;
-            if (chain_fused_power_ratio(f->fd, true, true, &ratio)) f->fd_ratio = ratio;
-            f->fd_probed = true;
-        }
-        if (guarded && f->fd_ratio >= 0.f && f->fd_ratio < 0.04f) {
-            f->fd_blocked = f->f32_products = true; // the direct form below redoes the probed frames too (float32 products from here on)
-        } else {
-            if (probe < frames) {
-                rc = chain_fused_fir(f->fd, x + probe * kFdFrame * 2, probe ? x + (probe * kFdFrame - 256) * 2 : (const float*)f->d_hist256.ptr, frames - probe, y + probe * kFdFrame * 2, st);
-                if (rc) return rc;
-            }
-            done = frames * kFdFrame;
-            hist = x + (done - f->hcap) * 2; // the hcap samples in front of the remainder are part of the input itself
-        }
-        }
-    }
-    // complex<float>, no decimation, 33..256 taps, whatever the fast convolution did not take (GR4HIP_FIR_TIME_DOMAIN, a stream the dynamic-range guard has
-    // moved to the direct form, or both): the same block-Toeplitz product on the re and im planes of the interleaved samples (fir_mfma_c32_kernel)
-    // (16-byte-aligned input too: the three-term bf16 form of the same product, fir_bf16.hip)
-    // ... since round 4 on the f16 matrix pipe with two-term splits under a per-segment block exponent (fir_f16.hip): half the products, and every segment judges its
-    // own output / input power -- so a stream the fast convolution's guard has handed over stays here (the segments that need float32 products get them inside the launch)
-    if (f->S == 2 && f->decim == 1 && f->ntaps > 32 && f->ntaps <= 256 && n_in - done >= kMfmaMinSamples / 2 && ((reinterpret_cast<uintptr_t>(y + done * 2) | reinterpret_cast<uintptr_t>(x + done * 2)) & 15) == 0 &&
-        algo != GR4HIP_FIR_EXACT_F32 && !f->f32_user && !f->bf16_user && !dev_switch(kDevFirNoBf16x3) && !dev_switch(kDevFirNoF16x2) && f->hfKS >= 0 && plain) {
-        int rc = GR4HIP_OK;
-        if (f->hfKS == 0) {
-            std::vector<unsigned short> af;
-            if (!fir_f16_make_afrag(f->taps.data(), f->ntaps, &f->hfKS, &af, 1, 0)) f->hfKS = -1;
-            else {
-                if (f->guard_ratio != kGuardSegmentRatio) { const float g = (float)(f->tap_power * f->guard_ratio); std::memcpy(af.data() + (size_t)f->hfKS * 1536 + 6, &g, 4); } // (the table's header, fir_f16_make_afrag: the tighter
-                // threshold goes on the segment's WHOLE output power; the quietest-column statistic keeps its 21 dB -- at 15 dB it dips below on narrow-band noise alone: 1 % pass band, half of all segments marked)
-                rc = f->d_hfrag.ensure(af.size() * sizeof(unsigned short));
-                if (!rc) { hipError_t e = hipMemcpyAsync(f->d_hfrag.ptr, af.data(), af.size() * sizeof(unsigned short), hipMemcpyHostToDevice, st); if (e != hipSuccess) { set_error("fir: upload failed: %s", hipGetErrorString(e)); rc = GR4HIP_RUNTIME_ERROR; } }
-                if (rc) { f->hfKS = 0; return rc; }
-            }
-        }
-        if (f->hfKS > 0) {
-            float* nh = done == 0 ? (float*)f->d_hist[f->cur ^ 1].ptr : nullptr;
-            const long nrem = (long)(n_in - done);
-            rc = f->d_flags.ensure((size_t)ceil_div(nrem, 2048L));
-            if (rc) return rc;
-            rc = fir_f16_c32_launch(f->hfKS, x + done * 2, nrem, hist, (int)f->hcap, f->d_hfrag.ptr, y + done * 2, st, nh, f->guard_mode != GR4HIP_GUARD_OFF, (unsigned char*)f->d_flags.ptr);
-            if (rc) return rc;
-            rc = fir_exact_launch(x + done * 2, nrem, hist, (int)f->hcap, (const float*)f->d_tapsf.ptr, (int)f->ntaps, 1, 1, y + done * 2, nrem, (const unsigned char*)f->d_flags.ptr, 11, nullptr, st); // the marked segments again, on the FP64 matrix pipe
-            if (rc) return rc;
-            done = n_in;
-            mfma_wrote_hist = nh != nullptr;
-        }
-    }
-    // (round 5) complex, 257 .. 1792 taps: slices of 256 taps on the same kernel, each a pass over the input delayed by 256 p samples that adds to y (the float path's scheme below;
-    // until then these filters took the f32 matrix pipe at its peak: 512 taps 36 Gsamples/s, 1024 taps 17).  The last slice judges the sums against the whole filter's threshold;
-    // marked segments again with all the taps on the FP64 matrix pipe.
-    if (f->S == 2 && f->decim == 1 && f->ntaps > 256 && f->ntaps <= 1792 /* (seven slices: a slice's window and its delay must fit the kernel's 2048-sample segment) */ && done == 0 && n_in >= kMfmaMinSamples / 2 && ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(x)) & 15) == 0 &&
-        algo != GR4HIP_FIR_EXACT_F32 && !f->f32_user && !f->bf16_user && !dev_switch(kDevFirNoBf16x3) && !dev_switch(kDevFirNoF16x2) && f->hfKS >= 0 && plain) {
-        int          rc = GR4HIP_OK;
-        const size_t nslice = ceil_div(f->ntaps, (size_t)256);
-        if (f->hfKS == 0) {
-            std::vector<unsigned short> all;
-            bool                        ok = true;
-            f->hf_off.assign(nslice, 0);
-            f->hf_ks.assign(nslice, 0);
-            for (size_t p = 0; p < nslice && ok; ++p) {
-                std::vector<unsigned short> af;
-                const size_t                len = std::min<size_t>(256, f->ntaps - 256 * p);
-                const int                   nat = std::max(3, (int)((len - 1 + 16 + 31) / 32));
-                ok = fir_f16_make_afrag(f->taps.data() + 256 * p, len, &f->hf_ks[p], &af, 1, nat == 8 ? 9 : 0); // (the sliced kernel at 8 K-steps would keep two registers in scratch: such a slice runs the 9-step kernel on zero-padded taps)
-                if (ok && p + 1 == nslice && f->guard_ratio != kGuardSegmentRatio) { const float g = (float)(f->tap_power * f->guard_ratio); std::memcpy(af.data() + (size_t)f->hf_ks[p] * 1536 + 6, &g, 4); } // (the judging slice carries the
-                // library-internal caller's second verdict on the whole output power, like the one-pass table above)
-                f->hf_off[p] = all.size();
-                all.insert(all.end(), af.begin(), af.end());
-            }
-            if (!ok) f->hfKS = -1;
-            else {
-                rc = f->d_hfrag.ensure(all.size() * sizeof(unsigned short));
-                if (!rc) { hipError_t e = hipMemcpyAsync(f->d_hfrag.ptr, all.data(), all.size() * sizeof(unsigned short), hipMemcpyHostToDevice, st); if (e != hipSuccess) { set_error("fir: upload failed: %s", hipGetErrorString(e)); rc = GR4HIP_RUNTIME_ERROR; } }
-                if (rc) return rc;
-                f->hfKS = f->hf_ks[0];
-            }
-        }
-        if (f->hfKS > 0) {
-            float* nh = (float*)f->d_hist[f->cur ^ 1].ptr;
-            rc = f->d_flags.ensure((size_t)ceil_div((long)n_in, 2048L));
-            if (rc) return rc;
-            const bool judged = f->guard_mode != GR4HIP_GUARD_OFF;
-            for (size_t p = 0; p < nslice && !rc; ++p)
-                rc = fir_f16_c32_launch(f->hf_ks[p], x, (long)n_in, hist, (int)f->hcap, (const unsigned short*)f->d_hfrag.ptr + f->hf_off[p], y, st, p == 0 ? nh : nullptr, p + 1 == nslice && judged,
-                                        (unsigned char*)f->d_flags.ptr, (int)(256 * p), p > 0, (float)(f->tap_power * kGuardSegmentRatio));
-            if (rc) return rc;
-            rc = fir_exact_launch(x, (long)n_in, hist, (int)f->hcap, (const float*)f->d_tapsf.ptr, (int)f->ntaps, 1, 1, y, (long)n_in, (const unsigned char*)f->d_flags.ptr, 11, nullptr, st);
-            if (rc) return rc;
-            done = n_in;
-            mfma_wrote_hist = true;
-        }
-    }
-    static const size_t kCBfMinTaps = [] { const char* e = std::getenv("GR4HIP_CFIR_BF16_MIN_TAPS"); return e ? (size_t)std::atoi(e) : (size_t)33; }(); // developer knob: 65 puts 33..64 taps back on the f32 MFMA (measured 5-8 % slower: 299-316 against 322-333 Gsamples/s); below 33 taps the register-window kernel is ahead up to 27 taps and within 3 % from there (tools/cfir_bf16_threshold.py)
-    if (done < n_in && f->S == 2 && f->decim == 1 && f->ntaps >= kCBfMinTaps && f->ntaps <= 256 && n_in - done >= kMfmaMinSamples / 2 && ((reinterpret_cast<uintptr_t>(y + done * 2) | reinterpret_cast<uintptr_t>(x + done * 2)) & 15) == 0 &&
-        !no_bf16x3(f) && plain) {
-        int rc = GR4HIP_OK;
-        if (f->bfKS == 0) {
-            std::vector<unsigned short> af;
-            fir_bf16_make_afrag(f->taps.data(), f->ntaps, &f->bfKS, &af, 1, 0);
-            rc = f->d_bfrag.ensure(af.size() * sizeof(unsigned short));
-            if (!rc) { hipError_t e = hipMemcpyAsync(f->d_bfrag.ptr, af.data(), af.size() * sizeof(unsigned short), hipMemcpyHostToDevice, st); if (e != hipSuccess) { set_error("fir: upload failed: %s", hipGetErrorString(e)); rc = GR4HIP_RUNTIME_ERROR; } }
-            if (rc) { f->bfKS = 0; return rc; }
-        }
-        float* nh = done == 0 ? (float*)f->d_hist[f->cur ^ 1].ptr : nullptr;
-        rc = fir_bf16_c32_launch(f->bfKS, x + done * 2, (long)(n_in - done), hist, (int)f->hcap, f->d_bfrag.ptr, y + done * 2, st, nh);
-        if (rc) return rc;
-        unj_from = done; unj_hist = hist;
-        done = n_in;
-        mfma_wrote_hist = nh != nullptr;
-    }
-    const bool exact = algo == GR4HIP_FIR_EXACT_F32; // only the register-window kernel: its products are the taps' (padded to a multiple of 4 per phase), nothing wider
-    if (!exact && done < n_in && f->S == 2 && f->decim == 1 && f->ntaps > 32 && f->ntaps <= 256 && n_in - done >= kMfmaMinSamples / 2 && (reinterpret_cast<uintptr_t>(y + done * 2) & 15) == 0) {
-        int rc = GR4HIP_OK;
-        if (f->mKS == 0) {
-            std::vector<float> af;
-            fir_mfma_make_afrag(f->taps.data(), f->ntaps, 1, &f->mKp, &f->mKS, &af);
-            rc = f->d_afrag.ensure(af.size() * sizeof(float));
-            if (!rc) { hipError_t e = hipMemcpyAsync(f->d_afrag.ptr, af.data(), af.size() * sizeof(float), hipMemcpyHostToDevice, st); if (e != hipSuccess) { set_error("fir: upload failed: %s", hipGetErrorString(e)); rc = GR4HIP_RUNTIME_ERROR; } }
-            if (rc) { f->mKS = 0; return rc; }
-        }
-        const float* hk = hist; // (hcap = bit_ceil(ntaps) is Kp for 33 .. 256 taps: read in place; a span served by this launch alone also gets its next history from it)
-        if ((int)f->hcap != f->mKp) {
-            rc = f->d_histc.ensure(256 * sizeof(float2));
-            if (rc) return rc;
-            hipLaunchKernelGGL(fir_hist_widen_kernel<float2>, dim3(1), dim3(256), 0, st, (const float2*)hist, (int)f->hcap, (float2*)f->d_histc.ptr, f->mKp);
-            GR4_LAUNCH_CHECK();
-            hk = (const float*)f->d_histc.ptr;
-        }
-        float* nh = (done == 0 && (int)f->hcap == f->mKp) ? (float*)f->d_hist[f->cur ^ 1].ptr : nullptr;
-        rc = fir_mfma_c32_launch(f->mKS, x + done * 2, (long)(n_in - done), hk, (const float*)f->d_afrag.ptr, y + done * 2, st, nh);
-        if (rc) return rc;
-        unj_from = done; unj_hist = hist;
-        done = n_in;
-        mfma_wrote_hist = nh != nullptr;
-    }
-    // float, no decimation, 33 .. 256 taps, long 16-byte-aligned span: the same product on the bf16 matrix pipe with three-term splits of samples and taps
-    // (fir_bf16.hip: float32 accuracy, 2.4 times less matrix-pipe time than the f32 MFMA -- HBM-bound instead of MFMA-bound)
-    // (384 .. 1024 taps: slices of 256 taps, each a pass over the input delayed by 256 p samples that adds to y: 512 taps 115 instead of 90 Gsamples/s on the
-    // register-window kernel, 1024 taps 50.5 instead of 47; below 384 and above 1024 taps the extra passes cost more than they save -- measured)
-    if (f->S == 1 && f->decim == 1 && f->ntaps > 32 && f->ntaps <= 3840 /* (fifteen slices: a slice's window and its delay must fit the kernel's 4096-sample segment; round 5's last day: 257 .. 383 and 1025 .. 3840 taps as slices too -- the three-term bf16 slices they were measured against in round 3 are not what they compete with any more: 257 / 300 / 383 taps 167 / 148 / 119 Gsamples/s on the other kernels, 1100 taps 44) */ && n_in >= kMfmaMinSamples && ((reinterpret_cast<uintptr_t>(d_out) | reinterpret_cast<uintptr_t>(d_in)) & 15) == 0 &&
-        algo == GR4HIP_FIR_AUTO && !no_bf16x3(f) && !f->bf16_user && !dev_switch(kDevFirNoF16x2) && f->hfKS >= 0 && plain) {
-        // ... on the f16 matrix pipe with two-term splits under a per-segment block exponent (fir_f16.hip): three products per tap instead of six
-        int          rc = GR4HIP_OK;
-        const size_t nslice = ceil_div(f->ntaps, (size_t)256);
-        if (f->hfKS == 0) {
-            std::vector<unsigned short> all;
-            bool                        ok = true;
-            f->hf_off.assign(nslice, 0);
-            f->hf_ks.assign(nslice, 0);
-            for (size_t p = 0; p < nslice && ok; ++p) {
-                std::vector<unsigned short> af;
-                const size_t                len = std::min<size_t>(256, f->ntaps - 256 * p);
-                ok = fir_f16_make_afrag(f->taps.data() + 256 * p, len, &f->hf_ks[p], &af, 1, 0);
-                f->hf_off[p] = all.size();
-                all.insert(all.end(), af.begin(), af.end());
-            }
-            if (!ok) f->hfKS = -1;
-            else {
-                rc = f->d_hfrag.ensure(all.size() * sizeof(unsigned short));
-                if (!rc) { hipError_t e = hipMemcpyAsync(f->d_hfrag.ptr, all.data(), all.size() * sizeof(unsigned short), hipMemcpyHostToDevice, st); if (e != hipSuccess) { set_error("fir: upload failed: %s", hipGetErrorString(e)); rc = GR4HIP_RUNTIME_ERROR; } }
-                if (rc) return rc;
-                f->hfKS = f->hf_ks[0];
-            }
-        }
-        if (f->hfKS > 0) {
-            float* nh = (float*)f->d_hist[f->cur ^ 1].ptr;
-            rc = f->d_flags.ensure(ceil_div(n_in, (size_t)4096));
-            if (rc) return rc;
-            // every segment judges its own output / input power (fir_f16.hip); of a long filter's slices the LAST one does, on the sums it leaves in y (the whole filter's
-            // outputs) against the whole filter's threshold.  Marked segments -- rejected, or with samples the block exponent cannot carry in ANY slice -- are evaluated
-            // again with all the taps on the FP64 matrix pipe (fir_exact.hip)
-            const double h2 = f->tap_power;
-            for (size_t p = 0; p < nslice && !rc; ++p)
-                rc = fir_f16_launch(f->hf_ks[p], x, (long)n_in, hist, (int)f->hcap, (const unsigned short*)f->d_hfrag.ptr + f->hf_off[p], y, st, p == 0 ? nh : nullptr, 0, 0, 1, (int)(256 * p), p > 0,
-                                    p + 1 == nslice && f->guard_mode != GR4HIP_GUARD_OFF, (unsigned char*)f->d_flags.ptr, 0, (nslice > 1 || f->guard_ratio != kGuardSegmentRatio) ? (float)(h2 * f->guard_ratio) : 0.f);
-            if (rc) return rc;
-            rc = fir_exact_launch(x, (long)n_in, hist, (int)f->hcap, (const float*)f->d_tapsf.ptr, (int)f->ntaps, 1, 0, y, (long)n_in, (const unsigned char*)f->d_flags.ptr, 12, nullptr, st);
-            if (rc) return rc;
-            done = n_in;
-            mfma_wrote_hist = true;
-        }
-    }
-    if (done == 0 && f->S == 1 && f->decim == 1 && f->ntaps > 32 && (f->ntaps <= 256 || (f->ntaps >= 384 && f->ntaps <= 1024)) && n_in >= kMfmaMinSamples && ((reinterpret_cast<uintptr_t>(d_out) | reinterpret_cast<uintptr_t>(d_in)) & 15) == 0 &&
-        algo == GR4HIP_FIR_AUTO && !no_bf16x3(f) && plain) {
-        int          rc = GR4HIP_OK;
-        const size_t nslice = ceil_div(f->ntaps, (size_t)256);
-        if (f->bfKS == 0) {
-            std::vector<unsigned short> all;
-            f->bf_off.assign(nslice, 0);
-            f->bf_ks.assign(nslice, 0);
-            for (size_t p = 0; p < nslice; ++p) {
-                std::vector<unsigned short> af;
-                const size_t                len = std::min<size_t>(256, f->ntaps - 256 * p);
-                fir_bf16_make_afrag(f->taps.data() + 256 * p, len, &f->bf_ks[p], &af, 1, 0);
-                f->bf_off[p] = all.size();
-                all.insert(all.end(), af.begin(), af.end());
-            }
-            rc = f->d_bfrag.ensure(all.size() * sizeof(unsigned short));
-            if (!rc) { hipError_t e = hipMemcpyAsync(f->d_bfrag.ptr, all.data(), all.size() * sizeof(unsigned short), hipMemcpyHostToDevice, st); if (e != hipSuccess) { set_error("fir: upload failed: %s", hipGetErrorString(e)); rc = GR4HIP_RUNTIME_ERROR; } }
-            if (rc) return rc;
-            f->bfKS = f->bf_ks[0];
-        }
-        float* nh = (float*)f->d_hist[f->cur ^ 1].ptr;
-        for (size_t p = 0; p < nslice && !rc; ++p)
-            rc = fir_bf16_launch(f->bf_ks[p], x, (long)n_in, hist, (int)f->hcap, (const unsigned short*)f->d_bfrag.ptr + f->bf_off[p], y, st, p == 0 ? nh : nullptr, 0, 0, 1, (int)(256 * p), p > 0);
-        if (rc) return rc;
-        unj_from = 0; unj_hist = hist;
-        done = n_in;
-        mfma_wrote_hist = true;
-    }
-    // float, no decimation, 33..256 taps, long 16-byte-aligned output: block-Toeplitz product on the f32 MFMA units (about twice the
-    // rate of the register-window VALU kernel, which is FP32-issue bound from ~48 taps on)
-    if (!exact && done == 0 && f->S == 1 && f->decim == 1 && f->ntaps > 32 && f->ntaps <= 256 && n_in >= kMfmaMinSamples && (reinterpret_cast<uintptr_t>(d_out) & 15) == 0) {
-        int rc = GR4HIP_OK;
-        if (f->mKS == 0) {
-            std::vector<float> af;
-            fir_mfma_make_afrag(f->taps.data(), f->ntaps, 1, &f->mKp, &f->mKS, &af);
-            rc = f->d_afrag.ensure(af.size() * sizeof(float));
-            if (!rc) { hipError_t e = hipMemcpyAsync(f->d_afrag.ptr, af.data(), af.size() * sizeof(float), hipMemcpyHostToDevice, st); if (e != hipSuccess) { set_error("fir: upload failed: %s", hipGetErrorString(e)); rc = GR4HIP_RUNTIME_ERROR; } }
-            if (rc) { f->mKS = 0; return rc; }
-        }
-        // hcap = bit_ceil(ntaps) IS Kp for 33 .. 256 taps: the block's history is read as it lies, and the launch writes the next one (one launch per call
-        // instead of three: what a scheduler's 64 Ki-sample chunks cost is launches)
-        const float* hk = hist;
-        if ((int)f->hcap != f->mKp) {
-            rc = f->d_hist256.ensure(256 * sizeof(float2));
-            if (rc) return rc;
-            hipLaunchKernelGGL(fir_hist_widen_kernel<float>, dim3(1), dim3(256), 0, st, hist, (int)f->hcap, (float*)f->d_hist256.ptr, f->mKp);
-            GR4_LAUNCH_CHECK();
-            hk = (const float*)f->d_hist256.ptr;
-        }
-        float* nh = (int)f->hcap == f->mKp ? (float*)f->d_hist[f->cur ^ 1].ptr : nullptr;
-        rc = fir_mfma_launch(f->mKS, x, (long)n_in, hk, (const float*)f->d_afrag.ptr, y, (long)((n_in + 3) & ~(size_t)3), (long)n_in, 1, st, nh);
-        if (rc) return rc;
-        unj_from = 0; unj_hist = hist;
-        done = n_in;
-        mfma_wrote_hist = nh != nullptr;
-    }
-    // float, decimate by 8, 97 .. 1025 taps (BASELINE configs[2]), long 16-byte-aligned span: the band form on the f16 matrix pipe, two-term splits under a per-segment block
-    // exponent, the K-steps split over the four waves, every segment judged and the rejected ones evaluated again with float32 products inside the launch (fir_decim_f16.hip)
-    // -- its error is relative to the output, so it needs no host-side guard and the call stays asynchronous
-    if (done == 0 && fir_decim_f16_shape(f, n_in, d_in, d_out, hk.any)) { // (hooked calls too: the kernel carries the programs, fir_exact_kernel<true> runs them again on marked segments)
-        int rc = GR4HIP_OK;
-        if (f->dhKQ == 0) {
-            std::vector<unsigned short> tab;
-            if (!fir_decim_f16_make_table(f->taps.data(), f->ntaps, f->decim, &f->dhKQ, &tab, f->S == 2)) f->dhKQ = -1;
-            else {
-                rc = f->d_dhtab.ensure(tab.size() * sizeof(unsigned short));
-                if (!rc) { hipError_t e = hipMemcpyAsync(f->d_dhtab.ptr, tab.data(), tab.size() * sizeof(unsigned short), hipMemcpyHostToDevice, st); if (e != hipSuccess) { set_error("fir: upload failed: %s", hipGetErrorString(e)); rc = GR4HIP_RUNTIME_ERROR; } }
-                if (rc) { f->dhKQ = 0; return rc; }
-            }
-        }
-        if (f->dhKQ > 0) {
-            const long segf = 8192 / (long)f->decim; // the kernel's segment: 8192 input floats = this many output floats
-            rc = f->d_flags.ensure((size_t)ceil_div((long)(n_out * f->S), segf));
-            if (rc) return rc;
-            rc = fir_decim_f16_launch((int)f->decim, f->dhKQ, x, (long)(n_in * f->S), hist, (int)(f->hcap * f->S), f->d_dhtab.ptr, y, (long)(n_out * f->S), st, (float*)f->d_hist[f->cur ^ 1].ptr,
-                                      f->guard_mode != GR4HIP_GUARD_OFF, (unsigned char*)f->d_flags.ptr, f->S == 2, &hk.pre, &hk.post);
-            if (rc) return rc;
-            // the marked segments again on the FP64 matrix pipe (fir_exact.hip; in samples: a complex segment is half as many outputs)
-            rc = fir_exact_launch(x, (long)n_in, hist, (int)f->hcap, (const float*)f->d_tapsf.ptr, (int)f->ntaps, (int)f->decim, f->S == 2, y, (long)n_out, (const unsigned char*)f->d_flags.ptr,
-                                  ilog2((size_t)(segf / f->S)), nullptr, st, 1, 0, 0, 0, 0, &hk.pre, &hk.post);
-            if (rc) return rc;
-            done = n_in;
-            mfma_wrote_hist = true;
-        }
-    }
-    // float, decimate by 2 .. 12 with a window of <= 1152 samples (taps - 1 + 15 D), long 16-byte-aligned span: the band form with three-term bf16 products
-    // (fir_bf16.hip; windows beyond 288 samples with the K-steps split over the four waves)
-    // complex<float> (real taps), decimate by 3 .. 16: the same kernels on the interleaved stream read as floats (fir_decim_bf16_make_afrag: the rows of a tile
-    // alternate between the re and im phases of the window) -- the register-window kernel below stages a decimator's samples one by one (decimate by 8, 64 taps:
-    // 171 G input samples/s against 483 here; by 16: 97 against 445; by 2 it is ahead: 389 / 307 against 348 / 252 at 16 / 64 taps)
-    // These kernels take the neighbours' programs themselves (load hook where the samples are split into bf16 planes, store hook on the output tile).
-    if (done == 0) {
-        int rc = GR4HIP_OK;
-        if (fir_decim_bf16_ready(f, n_in, d_in, d_out, &rc, st)) {
-            float* nh = (float*)f->d_hist[f->cur ^ 1].ptr;
-            // every segment judges its own output / input power (the three-term products' error is relative to the products); the marked ones are evaluated again on the
-            // FP64 matrix pipe behind the launch (fir_exact.hip), which runs the launch's load / store programs too
-            const bool judged = f->guard_mode != GR4HIP_GUARD_OFF && f->ntaps > 1;
-            int        seg_out = 0;
-            if (judged) { rc = f->d_flags.ensure((size_t)ceil_div((long)(n_out * f->S), 512L)); if (rc) return rc; }
-            const double h2 = f->tap_power;
-            rc = fir_decim_bf16_launch(f->bdKS, (int)f->decim, f->bdHb, x, (long)(n_in * f->S), hist, (int)(f->hcap * f->S), f->d_bdfrag.ptr, y, (long)(n_out * f->S), st, nh,
-                                       hk.pre.n_ops > 0 ? &hk.pre : nullptr, hk.post.n_ops > 0 ? &hk.post : nullptr, f->S == 2, judged ? (unsigned char*)f->d_flags.ptr : nullptr,
-                                       (float)(h2 * f->guard_ratio), &seg_out);
-            if (rc == GR4HIP_OK && judged)
-                rc = fir_exact_launch(x, (long)n_in, hist, (int)f->hcap, (const float*)f->d_tapsf.ptr, (int)f->ntaps, (int)f->decim, f->S == 2, y, (long)n_out, (const unsigned char*)f->d_flags.ptr,
-                                      ilog2((size_t)(seg_out / f->S)), nullptr, st, 1, 0, 0, 0, 0, &hk.pre, &hk.post);
-            if (rc == GR4HIP_OK) { done = n_in; mfma_wrote_hist = true; }
-            else if (rc == GR4HIP_UNSUPPORTED) f->bdKS = -1; // (the staged segment does not fit: do not ask again)
-            else return rc;
-        } else if (rc) return rc;
-    }
-    // float, decimate by 8, <= 1024 taps, long 16-byte-aligned span: overlap-save blocks of 8192 samples in the frequency domain (~35 lane-operations per
-    // input sample instead of 2 K / 8 flop: HBM / power-bound instead of FP32-bound); a partial last block rides in the same launch
-    constexpr size_t kDfHopS = 7168, kDfMinBlocks = 64;
-    if (done == 0 && f->S == 1 && algo == GR4HIP_FIR_AUTO && !f->fd_blocked && fir_decim_fd_supported(f->ntaps, f->decim) && f->ntaps <= 1024 && n_in >= kDfMinBlocks * kDfHopS &&
-        (reinterpret_cast<uintptr_t>(d_in) & 15) == 0 && !dev_switch(kDevFirNoDecimFd)) {
-        int rc = GR4HIP_OK;
-        if (!f->dfd) rc = fir_decim_fd_create(&f->dfd, f->taps.data(), f->ntaps);
-        if (rc) return rc;
-        // whole blocks and the span's partial last block in ONE launch (+ one small launch in front that widens the history and stages the partial block):
-        // sending the < 7168 leftover samples through the polyphase kernel cost a 44 us single-workgroup launch behind a 164 us transform kernel
-        // the same dynamic-range guard as the complex fast convolution above: the error floor of the transforms is ~2e-6 of the INPUT rms, and an anti-alias
-        // filter is exactly where strong out-of-band power is removed.  Strict: this launch's own measurement decides before the call returns (the polyphase
-        // kernels below redo the span); deferred: a finished earlier launch decides; from the first rejection on the stream stays on the polyphase kernels
-        const bool guarded = f->guard_mode != GR4HIP_GUARD_OFF && f->ntaps > 1;
-        float      ratio;
-        if (guarded && fir_decim_fd_power_ratio(f->dfd, false, &ratio)) f->fd_ratio = ratio;
-        // threshold: this kernel's floor is one forward 4096-point and one inverse 1024-point transform -- measured (tools/decim_fd_floor.py) max 2.5e-7 .. 3.7e-7, rms 7e-8 of
-        // the INPUT rms per output sample, six times below the fused chain's -- so 1e-5 of the OUTPUT rms holds down to a power ratio of (4e-7 / 1e-5)^2 = 1.6e-3; 2.5e-3
-        // (-26 dB) with margin.  White noise through a DC-gain-1 low-pass of cut-off fc passes 2 fc of its power: every anti-alias filter down to fc = 0.00125 stays here.
-        constexpr float kDecimFdMinPowerRatio = 2.5e-3f;
-        if (guarded && f->fd_ratio >= 0.f && f->fd_ratio < kDecimFdMinPowerRatio) f->fd_blocked = f->f32_products = true; // (an earlier launch's measurement, read without waiting)
-        if (!f->fd_blocked) {
-            rc = fir_decim_fd_run(f->dfd, x, n_in, hist, (int)f->hcap, y, st, guarded);
-            if (rc) return rc;
-            done = n_in;
-            if (guarded && f->guard_mode == GR4HIP_GUARD_STRICT) { // (round 5: nobody waits) segments of 2048 outputs judged behind the launch at this kernel's threshold, the marked ones again in float64
-                rc = f->d_flags_fd.ensure((size_t)ceil_div((long)n_out, 2048L));
-                if (!rc) rc = fir_judge_launch(x, (long)n_in, y, (long)n_out, (int)f->decim, 0, 11, kDecimFdMinPowerRatio, (unsigned char*)f->d_flags_fd.ptr, st);
-                if (!rc) rc = fir_exact_launch(x, (long)n_in, hist, (int)f->hcap, (const float*)f->d_tapsf.ptr, (int)f->ntaps, (int)f->decim, 0, y, (long)n_out, (const unsigned char*)f->d_flags_fd.ptr, 11, nullptr, st);
-                if (rc && rc != GR4HIP_UNSUPPORTED) return rc;
-            }
-        }
-    }
-    // float, decimate by kBandMinDecim .. 128, long span: the band form of the contraction (samples in stream order, the decimation in the A operand)
-    static const size_t kBandMinDecim = [] { const char* e = std::getenv("GR4HIP_FIR_BAND_MIN_DECIM"); return e ? (size_t)std::atoi(e) : (size_t)10; }(); // (developer switch: where the band form takes over from the polyphase form)
-    if (done == 0 && f->S == 1 && f->decim >= kBandMinDecim && f->decim <= 128 && n_out >= (1u << 14) && algo == GR4HIP_FIR_AUTO) {
-        int rc = GR4HIP_OK;
-        if (f->bandKp == 0) {
-            std::vector<float> row;
-            fir_decim_band_make_row(f->taps.data(), f->ntaps, f->decim, &f->bandKp, &row);
-            rc = f->d_band.ensure(row.size() * sizeof(float));
-            if (!rc) { hipError_t e = hipMemcpyAsync(f->d_band.ptr, row.data(), row.size() * sizeof(float), hipMemcpyHostToDevice, st); if (e != hipSuccess) { set_error("fir: upload failed: %s", hipGetErrorString(e)); rc = GR4HIP_RUNTIME_ERROR; } }
-            if (rc) { f->bandKp = 0; return rc; }
-        }
-        rc = fir_decim_band_launch((int)f->decim, f->bandKp, x, hist, (int)f->hcap, (const float*)f->d_band.ptr, y, (long)n_out, (long)n_in, st);
-        if (rc == GR4HIP_OK) { done = n_in; unj_from = 0; unj_hist = hist; }
-        else if (rc != GR4HIP_UNSUPPORTED) return rc; // UNSUPPORTED: the tile does not fit the LDS, keep the kernels below
-    }
-    // float polyphase decimator with >= 16 taps per phase and a long span: the same contraction with the D phase products summed in
-    // one accumulator tile (BASELINE configs[2]: decim 8, 1024 taps)
-    if (!exact && done == 0 && f->S == 1 && f->decim >= 2 && ceil_div(f->ntaps, f->decim) >= 16 && ceil_div(f->ntaps, f->decim) <= 256 && n_out >= (1u << 14) &&
-        (reinterpret_cast<uintptr_t>(d_out) & 15) == 0) {
-        int rc = GR4HIP_OK;
-        if (f->mKS == 0) {
-            std::vector<float> af;
-            fir_mfma_make_afrag_decim(f->taps.data(), f->ntaps, f->decim, &f->mKp, &f->mKS, &af);
-            rc = f->d_afrag.ensure(af.size() * sizeof(float));
-            if (!rc) { hipError_t e = hipMemcpyAsync(f->d_afrag.ptr, af.data(), af.size() * sizeof(float), hipMemcpyHostToDevice, st); if (e != hipSuccess) { set_error("fir: upload failed: %s", hipGetErrorString(e)); rc = GR4HIP_RUNTIME_ERROR; } }
-            if (rc) { f->mKS = 0; return rc; }
-        }
-        const int hl = f->mKp * (int)f->decim; // history the kernel wants: Kp D samples
-        rc = f->d_hist256.ensure((size_t)hl * sizeof(float));
-        if (rc) return rc;
-        const int hu = (int)std::min<size_t>(f->hcap, (size_t)hl); // newest hu samples of the block's history are what the kernel can see
-        hipLaunchKernelGGL(fir_hist_widen_kernel<float>, dim3((unsigned)ceil_div(hl, 256)), dim3(256), 0, st, hist + (f->hcap - hu), hu, (float*)f->d_hist256.ptr, hl);
-        GR4_LAUNCH_CHECK();
-        rc = fir_mfma_decim_launch(f->mKS, (int)f->decim, x, (const float*)f->d_hist256.ptr, (const float*)f->d_afrag.ptr, y, (long)n_out, st);
-        if (rc == GR4HIP_OK) { done = n_in; unj_from = 0; unj_hist = hist; }
-        else if (rc != GR4HIP_UNSUPPORTED) return rc; // UNSUPPORTED: the de-interleaved segment does not fit the LDS, keep the VALU kernel
-    }
-    const int E  = 4 / f->S;
-    int       rc = done == n_in ? GR4HIP_OK : GR4HIP_UNSUPPORTED;
-    bool      hist_written = mfma_wrote_hist;
-    for (int bs : {256, 128, 64}) {
-        if (done == n_in) break;
-        const size_t Lf  = (size_t)bs * kFirR + 4 * (size_t)f->G;
-        const size_t lds = f->decim * (Lf + (size_t)f->G * E) * sizeof(float);
-        if (lds > 150 * 1024) continue;
-        const float* xr = x + done * f->S;
-        float*       yr = y + (done / f->decim) * f->S;
-        const long   ni = (long)(n_in - done), no = (long)((n_in - done) / f->decim);
-        float*       nh = done == 0 ? (float*)f->d_hist[f->cur ^ 1].ptr : nullptr; // the whole span in this launch: it writes the next history itself
-        if (f->S == 1) rc = bs == 256 ? fir_launch<1, 256>(f, xr, hist, yr, ni, no, lds, st, nh, hk) : bs == 128 ? fir_launch<1, 128>(f, xr, hist, yr, ni, no, lds, st, nh, hk) : fir_launch<1, 64>(f, xr, hist, yr, ni, no, lds, st, nh, hk);
-        else rc = bs == 256 ? fir_launch<2, 256>(f, xr, hist, yr, ni, no, lds, st, nh, hk) : bs == 128 ? fir_launch<2, 128>(f, xr, hist, yr, ni, no, lds, st, nh, hk) : fir_launch<2, 64>(f, xr, hist, yr, ni, no, lds, st, nh, hk);
-        hist_written = nh != nullptr && rc == GR4HIP_OK;
-        break;
-    }
-    if (rc == GR4HIP_UNSUPPORTED && done == 0 && f->S == 1 && f->decim >= 2 && plain) { // D phase rows do not fit the LDS at any workgroup size: the band form at any span length
-        if (f->bandKp == 0) {
-            std::vector<float> row;
-            fir_decim_band_make_row(f->taps.data(), f->ntaps, f->decim, &f->bandKp, &row);
-            int rb = f->d_band.ensure(row.size() * sizeof(float));
-            if (!rb) { hipError_t e = hipMemcpyAsync(f->d_band.ptr, row.data(), row.size() * sizeof(float), hipMemcpyHostToDevice, st); if (e != hipSuccess) { set_error("fir: upload failed: %s", hipGetErrorString(e)); rb = GR4HIP_RUNTIME_ERROR; } }
-            if (rb) { f->bandKp = 0; return rb; }
-        }
-        rc = fir_decim_band_launch((int)f->decim, f->bandKp, x, hist, (int)f->hcap, (const float*)f->d_band.ptr, y, (long)n_out, (long)n_in, st);
-        if (rc == GR4HIP_OK) { unj_from = 0; unj_hist = hist; }
-    }
-    if (rc == GR4HIP_UNSUPPORTED && done == 0 && plain) { // no tiling fits: the one-output-per-lane kernel (the guard's second evaluation follows it where that one fits)
-        const unsigned g = (unsigned)ceil_div((long)n_out, 256L);
-        if (f->S == 1) hipLaunchKernelGGL(fir_generic_kernel<1>, dim3(g), dim3(256), 0, st, x, hist, (int)f->hcap, (const float*)f->d_tapsf.ptr, (int)f->ntaps, (long)f->decim, y, (long)n_out, (long)n_in);
-        else hipLaunchKernelGGL(fir_generic_kernel<2>, dim3(g), dim3(256), 0, st, x, hist, (int)f->hcap, (const float*)f->d_tapsf.ptr, (int)f->ntaps, (long)f->decim, y, (long)n_out, (long)n_in);
-        GR4_LAUNCH_CHECK();
-        rc = GR4HIP_OK; unj_from = 0; unj_hist = hist;
-    }
-    if (rc == GR4HIP_UNSUPPORTED) { set_error("fir_process: ntaps=%zu decim=%zu does not fit the LDS tiling", f->ntaps, f->decim); return rc; }
-    if (rc) return rc;
-    if (unj_from != SIZE_MAX && f->guard_mode != GR4HIP_GUARD_OFF && f->ntaps > 1) {
-        const long ni = (long)(n_in - unj_from), no = ni / (long)f->decim;
-        const int  shift = f->S == 2 ? 10 : 11;
-        const float* xr = x + unj_from * f->S;
-        float*       yr = y + (unj_from / f->decim) * f->S;
-        if (no > 0) {
-            rc = f->d_flags.ensure((size_t)ceil_div(no, 1L << shift));
-            if (rc) return rc;
-            rc = fir_judge_launch(xr, ni, yr, no, (int)f->decim, f->S == 2, shift, (float)(f->tap_power * kGuardSegmentRatio), (unsigned char*)f->d_flags.ptr, st,
-                                  f->guard_ratio != kGuardSegmentRatio ? (float)(f->tap_power * f->guard_ratio) : 0.f); // (a tighter ratio: on the segment's whole output power -- the quietest quarter dips on narrow-band noise)
-            if (rc) return rc;
-            rc = fir_exact_launch(xr, ni, unj_hist, (int)f->hcap, (const float*)f->d_tapsf.ptr, (int)f->ntaps, (int)f->decim, f->S == 2, yr, no, (const unsigned char*)f->d_flags.ptr, shift, nullptr, st);
-            if (rc && rc != GR4HIP_UNSUPPORTED) return rc; // (UNSUPPORTED: decimation x taps beyond what the second evaluation stages -- the float32 sums stand)
-        }
-    }
-    if (!hist_written) {
-        const long tot = (long)f->hcap * f->S;
-        hipLaunchKernelGGL(fir_hist_update_kernel, dim3((unsigned)ceil_div(tot, 256L)), dim3(256), 0, st, static_cast<const float*>(d_in),
-                           (const float*)f->d_hist[f->cur].ptr, (float*)f->d_hist[f->cur ^ 1].ptr, (long)n_in, (int)f->hcap, f->S);
-        GR4_LAUNCH_CHECK();
-    }
-    f->cur ^= 1;
-    f->pos += (long)n_in;
-    return GR4HIP_OK;
-}
-
 // ------------------------------------------------------------------------------------------------ decimating FIR -> IIR cascade (BASELINE configs[2])
 int  gr4hip_internal_iir_fusable(gr4hip_iir_t* f, const float** d_tab, int* nsec, const float** d_state_in, float** d_state_out, int* warm_blocks, hipStream_t st); // iir.hip
 void gr4hip_internal_iir_commit(gr4hip_iir_t* f);
@@ -1204,12 +1208,11 @@ extern "C" int gr4hip_fir_iir_process(gr4hip_fir_t* f, gr4hip_iir_t* iir, const 
         if (const int rc = gr4hip_fir_process(f, x, n, mid, nullptr, stream)) return rc;
         return gr4hip_iir_process(iir, mid, n / f->decim, y, stream);
     };
-    constexpr size_t kHop = 7168, kMinBlocks = 64;
     const float*     tab = nullptr;
     const float*     st_in = nullptr;
     float*           st_out = nullptr;
     int              nsec = 0, warm = 0;
-    const size_t     whole = n_in / kHop * kHop;
+    const size_t     whole = n_in / kDfHopS * kDfHopS;
     if (f->folded != 1.0 && !f->pre && !f->post) { // (a gain prologue / epilogue that was taken off again left its factor in the taps on this path: gr4hip_fir_process undoes it
                                                    // through fir_prepare_hooks, the fused launch below never came by there)
         FirHooks hk0;
@@ -1217,7 +1220,7 @@ extern "C" int gr4hip_fir_iir_process(gr4hip_fir_t* f, gr4hip_iir_t* iir, const 
     }
     if (const int rc = fir_state_on(f, st)) return rc;
     const bool       fusable = mode == GR4HIP_FIR_IIR_ONE_LAUNCH && f->S == 1 && f->decim == 8 && f->algo == GR4HIP_FIR_AUTO && !f->fd_blocked && !f->pre && !f->post && fir_decim_fd_supported(f->ntaps, f->decim) && f->ntaps <= 1024 &&
-                         whole >= kMinBlocks * kHop && (reinterpret_cast<uintptr_t>(d_in) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_out) & 7) == 0 && !dev_switch(kDevFirNoDecimFd) &&
+                         whole >= kDfMinBlocks * kDfHopS && (reinterpret_cast<uintptr_t>(d_in) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_out) & 7) == 0 && !dev_switch(kDevFirNoDecimFd) &&
                          gr4hip_internal_iir_fusable(iir, &tab, &nsec, &st_in, &st_out, &warm, st);
     if (!fusable) return two_launches(d_in, n_in, d_out);
     int rc = GR4HIP_OK;
@@ -1225,7 +1228,6 @@ extern "C" int gr4hip_fir_iir_process(gr4hip_fir_t* f, gr4hip_iir_t* iir, const 
     if (rc) return rc;
     // the decimator's dynamic-range guard as in gr4hip_fir_process: its own measurement decides (strict: before this call returns -- nothing of the launch is kept, the
     // cascade's state included), a finished earlier launch decides (deferred)
-    constexpr float kDecimFdMinPowerRatio = 2.5e-3f;
     const bool      guarded = f->guard_mode != GR4HIP_GUARD_OFF && f->ntaps > 1;
     float           ratio;
     if (guarded && fir_decim_fd_power_ratio(f->dfd, false, &ratio)) f->fd_ratio = ratio;
@@ -1239,13 +1241,7 @@ extern "C" int gr4hip_fir_iir_process(gr4hip_fir_t* f, gr4hip_iir_t* iir, const 
         if (f->fd_ratio >= 0.f && f->fd_ratio < kDecimFdMinPowerRatio) { f->fd_blocked = f->f32_products = true; return two_launches(d_in, n_in, d_out); } // (neither handle has moved)
     }
     gr4hip_internal_iir_commit(iir);
-    {   // the filter's history moves behind the whole blocks
-        const long tot = (long)f->hcap;
-        hipLaunchKernelGGL(fir_hist_update_kernel, dim3((unsigned)ceil_div(tot, 256L)), dim3(256), 0, st, d_in, hist, (float*)f->d_hist[f->cur ^ 1].ptr, (long)whole, (int)f->hcap, 1);
-        GR4_LAUNCH_CHECK();
-        f->cur ^= 1;
-        f->pos += (long)whole;
-    }
+    if (const int rc = fir_advance(f, d_in, whole, st, false)) return rc; // the filter's history moves behind the whole blocks
     if (whole < n_in) return two_launches(d_in + whole, n_in - whole, d_out + whole / 8); // what is left of the span (< one block): the polyphase kernel and the cascade's own
     return GR4HIP_OK;
 }

@@ -40,7 +40,6 @@ constexpr int kDfOffF = kDfOffW + 8 * kDfRS; // F_q[i''] of the inverse transfor
 constexpr int kDfLds  = kDfOffF + 8 * 129 * 8;
 constexpr int kDfLdsAll = kDfLds + 64; // + the 16 verdict words of the dynamic-range guard (two slots x 8 waves)
 static_assert(2 * kDfLdsAll <= 160 * 1024, "two workgroups per CU");
-constexpr float kDecimFdBlockThreshold = 2.5e-3f; // = kDecimFdMinPowerRatio of fir.hip: the guard's output / input power threshold, applied to every block by itself
 
 struct DecimFdArgs {
     const float*  x;       // input samples (the span); block j covers positions j * 7168 - 1024 .. + 8191
@@ -588,7 +587,7 @@ int fir_decim_fd_run(FirDecimFd* c, const float* d_in, size_t n_in, const float*
         a.pw        = static_cast<float*>(c->d_pw.ptr);
         a.pw_host   = c->d_hpw;
         a.pw_seq    = ++c->pw_seq;
-        a.pw_thr    = kDecimFdBlockThreshold * (float)(kDfHop / 8) / (float)kDfN; // (the scale fir_decim_fd_power_ratio takes out)
+        a.pw_thr    = kDecimFdMinPowerRatio * (float)(kDfHop / 8) / (float)kDfN; // (the guard threshold, applied to every block by itself; the scale fir_decim_fd_power_ratio takes out)
         c->pw_stream = st;
     }
     static PerDevice per_device;
@@ -638,7 +637,7 @@ int fir_decim_fd_power_ratio(FirDecimFd* c, bool wait, float* ratio) {
     const double in = pair[0], out = pair[1];
     // per sampled block: 8192 input samples (the overlap counted twice: statistics only), 896 outputs
     *ratio = in > 0 ? (float)((out / (kDfHop / 8)) / (in / kDfN)) : 1.f;
-    if (reinterpret_cast<volatile unsigned*>(c->h_pw)[3] != 0u && *ratio >= kDecimFdBlockThreshold) *ratio = 0.5f * kDecimFdBlockThreshold; // one block below the threshold is enough
+    if (reinterpret_cast<volatile unsigned*>(c->h_pw)[3] != 0u && *ratio >= kDecimFdMinPowerRatio) *ratio = 0.5f * kDecimFdMinPowerRatio; // one block below the threshold is enough
     return 1;
 }
 
