@@ -410,6 +410,7 @@ struct gr4hip_fir {
     bool               taps_dirty = false; // d_taps / d_tapsf do not hold tp_host / taps yet
     bool               zero_hist  = true;  // d_hist[cur] is to be zeroed (create, reset, a history that had to grow)
     double             hist_rescale = 1.0; // d_hist[cur] is to be multiplied by this (a prologue gain that moved into or out of the taps)
+    unsigned           last_paths = 0;     // which paths served the last gr4hip_fir_process call (gr4hip_internal_fir_last_paths)
     ~gr4hip_fir() { delete pre; delete post; }
 };
 
@@ -1122,9 +1123,11 @@ static int fir_process_core(gr4hip_fir_t* f, const void* d_in, size_t n_in, void
     // hooks run in the register-window kernel and the band-form decimators only: the matrix-pipe and frequency-domain kernels are for plain filters
     FirCall c{f, static_cast<const float*>(d_in), static_cast<float*>(d_out), n_in, n_in / f->decim, as_stream(stream), hk, !hk.any, hk.any ? (int)GR4HIP_FIR_EXACT_F32 : f->algo,
               (const float*)f->d_hist[f->cur].ptr};
-    for (auto path : kPaths) {
+    for (size_t p = 0; p < sizeof(kPaths) / sizeof(kPaths[0]); ++p) {
         if (c.done == n_in) break;
-        if (const int rc = path(c)) return rc;
+        const size_t before = c.done;
+        if (const int rc = kPaths[p](c)) return rc;
+        if (c.done != before) f->last_paths |= 1u << (p + 1);
     }
     if (c.done != n_in) { set_error("fir_process: ntaps=%zu decim=%zu does not fit the LDS tiling", f->ntaps, f->decim); return GR4HIP_UNSUPPORTED; }
     // the guard's verdict and second evaluation behind a kernel that does not judge itself
@@ -1139,6 +1142,7 @@ static int fir_process_core(gr4hip_fir_t* f, const void* d_in, size_t n_in, void
                                                 f->guard_ratio != kGuardSegmentRatio ? (float)(f->tap_power * f->guard_ratio) : 0.f)) // (a tighter ratio: on the segment's whole output power -- the quietest quarter dips on narrow-band noise)
                 return rc;
             const int rc = fir_exact_launch(xr, ni, c.unj_hist, (int)f->hcap, (const float*)f->d_tapsf.ptr, (int)f->ntaps, (int)f->decim, f->S == 2, yr, no, (const unsigned char*)f->d_flags.ptr, shift, nullptr, c.st);
+            f->last_paths |= 1u;
             if (rc && rc != GR4HIP_UNSUPPORTED) return rc; // (UNSUPPORTED: decimation x taps beyond what the second evaluation stages -- the float32 sums stand)
         }
     }
@@ -1150,6 +1154,7 @@ extern "C" int gr4hip_fir_process(gr4hip_fir_t* f, const void* d_in, size_t n_in
     GR4_REQUIRE(n_in % f->decim == 0, "fir_process: n_in=%zu is not a multiple of decim=%zu", n_in, f->decim);
     const size_t n_out = n_in / f->decim;
     if (n_out_p) *n_out_p = n_out;
+    f->last_paths = 0;
     if (n_in == 0) return GR4HIP_OK;
     GR4_REQUIRE(d_in && d_out, "fir_process: null device pointer");
     FirHooks hk;
@@ -1180,12 +1185,21 @@ extern "C" int gr4hip_fir_process(gr4hip_fir_t* f, const void* d_in, size_t n_in
         if (hk.post.n_ops > 0) return ewise_run(hk.post, f->dtype, d_out, d_out, (long)n_out, st);
         return GR4HIP_OK;
     };
-    if (hk.any && fast_shape && !band) return around();
+    if (hk.any && fast_shape && !band) { f->last_paths |= 1u << 17; return around(); }
     const int rc = fir_process_core(f, d_in, n_in, d_out, stream, hk);
     //  a hooked decimator whose phase rows do not fit the register-window kernel's LDS at any workgroup size (decimation ~100 with few taps) -- the one kernel
     // that carries hooks there -- is served like the fast shapes: nothing has been launched or moved when the core says UNSUPPORTED
-    if (rc == GR4HIP_UNSUPPORTED && hk.any) return around();
+    if (rc == GR4HIP_UNSUPPORTED && hk.any) { f->last_paths |= 1u << 17; return around(); }
     return rc;
+}
+
+// Test hook, not ABI (declared in no header): the paths that served the last gr4hip_fir_process call -- bit p (1 .. 16) for each path of fir_process_core's
+// kPaths that advanced the span, bit 0 when the common tail judged an unjudged part and evaluated its marked segments again, bit 17 when the call ran as
+// element-wise launches around the plain filter
+extern "C" int gr4hip_internal_fir_last_paths(const gr4hip_fir_t* f, unsigned* mask) {
+    GR4_REQUIRE(f && mask, "fir_last_paths: null argument");
+    *mask = f->last_paths;
+    return GR4HIP_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ decimating FIR -> IIR cascade (BASELINE configs[2])

@@ -1,0 +1,392 @@
+"""gr4hip_fir_process's dispatch (csrc/fir.hip, fir_process_core): which of its 16 kernel paths serves a call, and whether the carried history survives the
+hand-offs between them.  Every call asserts the exact set of paths that served it, read from the library's test hook gr4hip_internal_fir_last_paths (bit p
+for path p of kPaths, 1 .. 16; bit 0: the common tail judged an unjudged part and evaluated its marked segments again; bit 17: the call ran as element-wise
+launches around the plain filter) -- a routing table here cannot go stale when a threshold moves.  Every result is compared with the float64 oracle under the
+parity contract's bar (include/gr4hip.h); under a rejected tone, with the error of the reference's own float32 sum where that is larger, factor one."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import oracle_lib as O
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+TOL = 1e-5
+J, AROUND = 0, 17  # mask bits beside the 16 paths: the common tail's judge, the element-wise route of gr4hip_fir_process
+FRAMES64 = 64 * 8192  # the fast convolution's (path 1) smallest span: 64 frames of 8192 complex samples
+FD8 = 64 * 7168  # the decimate-by-8 frequency-domain kernel's (path 11) smallest span
+
+
+def _rel(got, truth):
+    """THE parity metric (include/gr4hip.h, "PARITY CONTRACT"): max_k |got_k - truth_k| / max(|truth_k|, rms(truth))"""
+    got = np.asarray(got).astype(np.complex128 if np.iscomplexobj(got) else np.float64).ravel()
+    truth = np.asarray(truth).ravel()
+    rms = np.sqrt(np.mean(np.abs(truth) ** 2))
+    return float(np.max(np.abs(got - truth) / np.maximum(np.abs(truth), rms if rms > 0 else 1.0)))
+
+
+@pytest.fixture(scope="module")
+def G():
+    assert torch.cuda.is_available(), "gpu tests need a GPU"
+    import gnuradio4_amd as G
+    G.capi.lib()
+    return G
+
+
+def _ref32_err(b, x, truth, sl, decim=1):
+    """the error of the REFERENCE's own float32 sum, in the reference's order (oracle gr4o_fir_f32 / _c32), against the float64 evaluation"""
+    r32 = O.fir(b, x, acc64=False)[0][::decim]
+    return _rel(r32[sl], truth[sl])
+
+
+@pytest.fixture
+def devsw(G):
+    """developer switches of the library, restored when the test ends"""
+    used = set()
+
+    def set_(name, value=1):
+        used.add(name)
+        G.capi.developer_switch(name, value)
+    yield set_
+    for name in used:
+        G.capi.developer_switch(name, 0)
+
+
+def _paths(G, f):
+    """the bits of the last call's path record, as a sorted tuple"""
+    fn = G.capi.lib().gr4hip_internal_fir_last_paths  # (test hook, not in include/gr4hip.h)
+    fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_uint)]
+    m = C.c_uint(0xFFFFFFFF)
+    assert fn(f._h, C.byref(m)) == 0
+    return tuple(k for k in range(32) if m.value >> k & 1)
+
+
+def _taps(ntaps, D):
+    return O.design_taps_hamming_lowpass(ntaps, 0.2 if D == 1 else 0.4 / D)
+
+
+def _signal(cplx, n, seed):
+    return (O.signal_c32 if cplx else O.signal_f32)(seed, n, tone_frel=0.03)
+
+
+def _tone(cplx, n, seed, amp):
+    """weak noise under a strong tone at 0.31 cycles / sample, which every low-pass here rejects"""
+    rng = np.random.default_rng(seed)
+    ph = 2 * np.pi * 0.31 * np.arange(n)
+    x = 0.05 * (rng.standard_normal(n) + (1j * rng.standard_normal(n) if cplx else 0)) + amp * (np.exp(1j * ph) if cplx else np.cos(ph))
+    return x.astype(np.complex64 if cplx else np.float32)
+
+
+def _oracle(b, x, D):
+    if D == 1:
+        return O.fir(b, x)[0]
+    return O.fir(b, x)[0][::D] if np.iscomplexobj(x) else O.fir_decim(b, x, D)[0]
+
+
+class _Stream:
+    """one handle fed the consecutive spans of `x`: each call places its input `xoff` and its output `yoff` elements past a 16-byte boundary of a fresh
+    allocation, and records the paths that served it next to the ones it expects"""
+
+    def __init__(self, G, f, x, D):
+        self.G, self.f, self.x, self.D = G, f, x, D
+        self.pos, self.ys, self.seen = 0, [], []
+
+    def __call__(self, n, want, xoff=0, yoff=0):
+        dt, no = self.f.dtype, n // self.D
+        xin = torch.empty(n + 4, dtype=dt, device="cuda")[xoff:xoff + n]
+        xin.copy_(torch.from_numpy(np.ascontiguousarray(self.x[self.pos:self.pos + n])))
+        out = torch.empty(no + 4, dtype=dt, device="cuda")[yoff:yoff + no]
+        assert (xin.data_ptr() % 16 == 0) == (xoff == 0) and (out.data_ptr() % 16 == 0) == (yoff == 0)
+        self.f.process_bulk(xin, out)
+        self.ys.append(out.cpu().numpy())
+        self.seen.append((self.pos, n, xoff, yoff, _paths(self.G, self.f), tuple(sorted(want))))
+        self.pos += n
+
+    def y(self):
+        return np.concatenate(self.ys)
+
+    def wrong_paths(self):
+        return [s for s in self.seen if s[4] != s[5]]
+
+
+# ------------------------------------------------------------------ a. routing table: one case per path
+# (id, cplx, D, ntaps, algo, guard, switch, hooked, calls): calls are (n, xoff, yoff, paths expected); at least two per case, the second from a carried history
+# (path 1 takes every whole frame of a span: its remainder is shorter than one frame, below what paths 2, 4 and 5 take, so it always ends on path 14)
+_ROUTES = [
+    ("p01_cplx200_input_off_by_one", True, 1, 200, None, None, None, False, [(FRAMES64 + 40_000, 1, 0, (1, 14)), (FRAMES64 + 1_000, 1, 0, (1, 14))]),
+    ("p01_cplx200_deferred_probe", True, 1, 200, None, "GUARD_DEFERRED", None, False, [(FRAMES64 + 40_000, 1, 0, (1, 14)), (FRAMES64 + 1_000, 1, 0, (1, 14))]),
+    ("p02_cplx200", True, 1, 200, None, None, None, False, [(40_000, 0, 0, (2,)), (70_000, 0, 0, (2,))]),
+    ("p03_cplx1000", True, 1, 1000, None, None, None, False, [(40_000, 0, 0, (3,)), (50_000, 0, 0, (3,))]),
+    ("p04_cplx128_bf16x3", True, 1, 128, "FIR_TIME_DOMAIN_BF16X3", None, None, False, [(40_000, 0, 0, (4, J)), (50_000, 0, 0, (4, J))]),
+    ("p05_cplx128_f32", True, 1, 128, "FIR_TIME_DOMAIN_F32", None, None, False, [(40_000, 0, 0, (5, J)), (50_000, 0, 0, (5, J))]),
+    ("p06_float200", False, 1, 200, None, None, None, False, [(70_000, 0, 0, (6,)), (100_000, 0, 0, (6,))]),
+    ("p06_float3000", False, 1, 3000, None, None, None, False, [(70_000, 0, 0, (6,)), (80_000, 0, 0, (6,))]),
+    ("p07_float200_bf16x3", False, 1, 200, "FIR_TIME_DOMAIN_BF16X3", None, None, False, [(70_000, 0, 0, (7, J)), (80_000, 0, 0, (7, J))]),
+    ("p07_float700_bf16x3", False, 1, 700, "FIR_TIME_DOMAIN_BF16X3", None, None, False, [(70_000, 0, 0, (7, J)), (80_000, 0, 0, (7, J))]),
+    ("p08_float200_time_domain", False, 1, 200, "FIR_TIME_DOMAIN", None, None, False, [(70_000, 0, 0, (8, J)), (80_000, 0, 0, (8, J))]),
+    ("p09_float_d8_1024", False, 8, 1024, None, None, None, False, [(1 << 17, 0, 0, (9,)), ((1 << 17) + 800, 0, 0, (9,))]),
+    ("p09_cplx_d16_128", True, 16, 128, None, None, None, False, [(1 << 16, 0, 0, (9,)), ((1 << 16) + 1600, 0, 0, (9,))]),
+    ("p10_float_d5_300", False, 5, 300, None, None, None, False, [(81_920, 0, 0, (10,)), (100_000, 0, 0, (10,))]),
+    ("p11_float_d8_1024_output_off_by_one", False, 8, 1024, None, None, None, False, [(FD8, 0, 1, (11,)), (FD8 + 800, 0, 1, (11,))]),
+    ("p11_float_d8_1024_no_decim_f16", False, 8, 1024, None, None, "GR4HIP_FIR_NO_DECIM_F16", False, [(FD8, 0, 0, (11,)), (FD8 + 800, 0, 0, (11,))]),
+    ("p12_float_d20_400", False, 20, 400, None, None, None, False, [(327_680, 0, 0, (12, J)), (340_000, 0, 0, (12, J))]),
+    ("p13_float_d5_300_time_domain", False, 5, 300, "FIR_TIME_DOMAIN", None, None, False, [(81_920, 0, 0, (13, J)), (90_000, 0, 0, (13, J))]),
+    ("p14_float200_short", False, 1, 200, None, None, None, False, [(1_000, 0, 0, (14,)), (3_000, 0, 0, (14,))]),
+    ("p14_cplx128_exact_f32", True, 1, 128, "FIR_EXACT_F32", None, None, False, [(40_000, 0, 0, (14,)), (50_000, 0, 0, (14,))]),
+    ("p14_float64_hooked", False, 1, 64, None, None, None, True, [(5_000, 0, 0, (14,)), (7_000, 0, 0, (14,))]),
+    ("p17_float200_hooked_long", False, 1, 200, None, None, None, True, [(70_000, 0, 0, (AROUND, 6)), (80_000, 0, 0, (AROUND, 6))]),
+    ("p15_float_d100_400", False, 100, 400, None, None, None, False, [(100_000, 0, 0, (15, J)), (150_000, 0, 0, (15, J))]),
+    ("p16_cplx_d100_40", True, 100, 40, None, None, None, False, [(50_000, 0, 0, (16, J)), (70_000, 0, 0, (16, J))]),
+]
+
+
+def test_routing_table_reaches_every_path():
+    seen = set()
+    for case in _ROUTES:
+        for call in case[-1]:
+            seen.update(call[3])
+    assert set(range(1, 17)) | {J, AROUND} <= seen
+
+
+@pytest.mark.parametrize("cid,cplx,D,ntaps,algo,guard,switch,hooked,calls", _ROUTES, ids=[r[0] for r in _ROUTES])
+def test_fir_routing_table(G, devsw, cid, cplx, D, ntaps, algo, guard, switch, hooked, calls):
+    b = _taps(ntaps, D)
+    n = sum(c[0] for c in calls)
+    x = _signal(cplx, n, seed=ntaps + D)
+    if hooked:  # a prologue that is no gain rides as a load hook; samples on a 2^-10 grid keep `+ 0.75` exact in float32
+        x = np.round(x * 1024) / 1024
+        truth = _oracle(b, x + np.float32(0.75), D)
+    else:
+        truth = _oracle(b, x, D)
+    dt = torch.complex64 if cplx else torch.float32
+    f = G.fir_filter(b, dt, decimate=D)
+    if algo:
+        f.set_algo(getattr(G.capi, algo))
+    if guard:
+        f.set_guard_mode(getattr(G.capi, guard))
+    if switch:
+        devsw(switch)
+    if hooked:
+        f.set_prologue(G.Merged(dt, [("Add", 0.75)]))
+    s = _Stream(G, f, x, D)
+    for c in calls:
+        s(c[0], c[3], xoff=c[1], yoff=c[2])
+    y = s.y()
+    e = _rel(y, truth)
+    assert y.shape == truth.shape and e <= TOL and not s.wrong_paths(), (cid, e, s.seen)
+
+
+# ------------------------------------------------------------------ b. hand-off streams: each call changes one thing
+def _check_stream(s, b, x, D, tone=False):
+    truth = _oracle(b, x[:s.pos], D)
+    y = s.y()
+    sl = slice(len(b) // D + 1, None) if tone else slice(None)
+    e = _rel(y[sl], truth[sl])
+    bar = max(TOL, _ref32_err(b, x[:s.pos], truth, sl, D)) if tone else TOL
+    assert y.shape == truth.shape and e <= bar and not s.wrong_paths(), (e, bar, s.seen)
+
+
+def test_handoff_complex200_rejected_tone_through_the_fast_convolution_remainder(G):
+    """a tone 50 dB above the pass band across the fast convolution's hand-off: whole frames on path 1, the remainder (less than one frame: too short for
+    paths 2, 4 and 5, so the tail judge never sees a history inside the input) on the register-window kernel, which judges itself on a history that is the input
+    itself.  The strict guard's measurement of that first call then moves the stream to the direct forms for good."""
+    b = O.design_taps_hamming_lowpass(200, 0.05)
+    x = _tone(True, 2 * FRAMES64 + 300_000, 31, 7.0)
+    f = G.fir_filter(b, torch.complex64)
+    s = _Stream(G, f, x, 1)
+    s(FRAMES64 + 40_000, (1, 14), xoff=1)         # 68 frames, then 7 232 samples from c.hist = c.x + (done - hcap)
+    s(40_000, (2,))                               # aligned: the f16 direct form, history from fir_advance
+    s(FRAMES64 + 3_000, (5, J), xoff=1)           # the strict guard's measurement of the first call moved the stream: no fast convolution
+    f.set_algo(G.capi.FIR_TIME_DOMAIN_BF16X3)
+    s(40_000, (4, J))
+    f.set_algo(G.capi.FIR_AUTO)
+    s(40_000, (14,), yoff=1)
+    f.set_guard_mode(G.capi.GUARD_DEFERRED)
+    s(50_000, (5, J), xoff=1)
+    s(3_001, (14,))
+    s(40_000, (2,))
+    _check_stream(s, b, x, 1, tone=True)
+
+
+def test_handoff_complex200_guard_modes_and_alignment(G):
+    b = _taps(200, 1)
+    x = _signal(True, 3 * FRAMES64 + 300_000, 32)
+    f = G.fir_filter(b, torch.complex64)
+    s = _Stream(G, f, x, 1)
+    f.set_guard_mode(G.capi.GUARD_DEFERRED)
+    s(FRAMES64 + 40_000, (1, 14), xoff=1)         # the deferred guard's synchronous probe, then the rest of the frames
+    f.set_guard_mode(G.capi.GUARD_OFF)
+    s(FRAMES64 + 2_000, (1, 14), xoff=1)          # no judge anywhere; the remainder on the register-window kernel
+    f.set_guard_mode(G.capi.GUARD_STRICT)
+    s(33_000, (2,))
+    s(FRAMES64 + 35_000, (1, 14), xoff=1)
+    s(100, (14,))
+    s(40_000, (5, J), xoff=1)                     # path 5 alone: it writes the next history itself
+    s(40_000, (14,), xoff=1, yoff=1)
+    f.set_algo(G.capi.FIR_TIME_DOMAIN_F32)
+    s(40_000, (5, J))
+    f.set_algo(G.capi.FIR_EXACT_F32)
+    s(40_000, (14,))
+    _check_stream(s, b, x, 1)
+
+
+def test_handoff_float200(G):
+    b = _taps(200, 1)
+    x = _signal(False, 800_000, 33)
+    f = G.fir_filter(b, torch.float32)
+    s = _Stream(G, f, x, 1)
+    s(70_000, (6,))
+    s(70_000, (8, J), xoff=1)
+    s(70_000, (14,), yoff=1)
+    f.set_algo(G.capi.FIR_TIME_DOMAIN_BF16X3)
+    s(70_000, (7, J))
+    f.set_algo(G.capi.FIR_TIME_DOMAIN)
+    s(70_000, (8, J))
+    f.set_algo(G.capi.FIR_AUTO)
+    f.set_guard_mode(G.capi.GUARD_OFF)
+    s(70_000, (6,))
+    s(70_000, (8,), xoff=1)
+    f.set_guard_mode(G.capi.GUARD_STRICT)
+    f.set_algo(G.capi.FIR_EXACT_F32)
+    s(70_000, (14,))
+    f.set_algo(G.capi.FIR_AUTO)
+    s(999, (14,))
+    s(70_001, (8, J), xoff=1)
+    s(70_000, (6,))
+    _check_stream(s, b, x, 1)
+
+
+def test_handoff_float200_rejected_tone(G):
+    b = O.design_taps_hamming_lowpass(200, 0.05)
+    x = _tone(False, 600_000, 34, 7.0)
+    f = G.fir_filter(b, torch.float32)
+    s = _Stream(G, f, x, 1)
+    s(70_000, (6,))
+    s(70_000, (8, J), xoff=1)
+    s(3_000, (14,))
+    f.set_algo(G.capi.FIR_TIME_DOMAIN_BF16X3)
+    s(70_000, (7, J))
+    s(70_000, (14,), yoff=1)
+    f.set_algo(G.capi.FIR_AUTO)
+    s(70_000, (6,))
+    _check_stream(s, b, x, 1, tone=True)
+
+
+def test_handoff_float_decimate_by_8_1024_taps(G, devsw):
+    b = _taps(1024, 8)
+    x = _signal(False, 4 * FD8 + 4 * (1 << 17), 35)
+    f = G.fir_filter(b, torch.float32, decimate=8)
+    s = _Stream(G, f, x, 8)
+    s(1 << 17, (9,))
+    s(FD8, (11,), yoff=1)
+    s(1 << 17, (13, J), xoff=1)
+    s(800, (14,))
+    f.set_algo(G.capi.FIR_TIME_DOMAIN)
+    s(1 << 17, (13, J))
+    f.set_algo(G.capi.FIR_AUTO)
+    s(FD8 + 8, (9,))
+    devsw("GR4HIP_FIR_NO_DECIM_F16")
+    s(FD8, (11,))
+    devsw("GR4HIP_FIR_NO_DECIM_F16", 0)
+    s(8_000, (14,), yoff=1)
+    s(1 << 17, (9,))
+    _check_stream(s, b, x, 8)
+
+
+# ------------------------------------------------------------------ c. settingsChanged in mid stream
+def _settings_stream(G, cplx, D, steps, seed):
+    """steps: (ntaps, "new" | "keep" | "zero", [(n, xoff, yoff, paths, algo)]).  The reference keeps the history unless the taps outgrow its capacity
+    (time_domain_filter.hpp:38-42); then the filter starts again from zeros.  Each segment is compared with the oracle of its own taps."""
+    n = sum(c[0] for st in steps for c in st[2])
+    x = _signal(cplx, n, seed)
+    dt = torch.complex64 if cplx else torch.float32
+    f, s, origin, errs, cap = None, None, 0, [], 0
+    for ntaps, hist, calls in steps:
+        b = _taps(ntaps, D)
+        if f is None:
+            f = G.fir_filter(b, dt, decimate=D)
+            s = _Stream(G, f, x, D)
+        else:
+            f.settings_changed(b)
+        assert hist == ("new" if cap == 0 else "zero" if ntaps > cap else "keep"), (ntaps, cap, hist)  # (the table says what the reference does)
+        cap = max(cap, 32, 1 << (ntaps - 1).bit_length())
+        if hist == "zero":
+            origin = s.pos
+        start, k0 = s.pos, len(s.ys)
+        for n_, xoff, yoff, want, algo in calls:
+            f.set_algo(getattr(G.capi, algo or "FIR_AUTO"))
+            s(n_, want, xoff=xoff, yoff=yoff)
+        # the oracle from the stream's origin, or from far enough back for these taps (in steps of D: the decimation phase stays)
+        lo = max(origin, start - -(-(ntaps - 1) // D) * D)
+        truth = _oracle(b, x[lo:s.pos], D)[(start - lo) // D:]
+        y = np.concatenate(s.ys[k0:])
+        errs.append((ntaps, hist, y.shape == truth.shape and _rel(y, truth)))
+    bad = [e for e in errs if e[2] is False or e[2] > TOL]
+    assert not bad and not s.wrong_paths(), (errs, s.seen)
+
+
+def test_settings_changed_float_64_300_40_500_20(G):
+    _settings_stream(G, False, 1, [
+        (64, "new", [(70_000, 0, 0, (6,), None), (70_000, 1, 0, (8, J), None)]),
+        (300, "zero", [(70_000, 0, 0, (6,), None), (3_000, 0, 1, (14,), None)]),                 # 300 > 64: capacity 512, history lost
+        (40, "keep", [(70_000, 0, 0, (6,), None), (70_000, 1, 0, (8, J), None),                  # shrink: 512 samples of history, path 8 narrows it to 64
+                      (70_000, 0, 0, (8, J), "FIR_TIME_DOMAIN"), (2_000, 0, 0, (14,), None), (70_000, 0, 0, (7, J), "FIR_TIME_DOMAIN_BF16X3")]),
+        (500, "keep", [(70_000, 0, 0, (6,), None), (70_000, 0, 0, (7, J), "FIR_TIME_DOMAIN_BF16X3"), (5_000, 1, 0, (14,), None)]),  # grow back within 512
+        (20, "keep", [(70_000, 0, 0, (14,), None), (3_000, 1, 1, (14,), None)]),
+    ], 41)
+
+
+def test_settings_changed_complex_200_1000_100_2000(G):
+    _settings_stream(G, True, 1, [
+        (200, "new", [(FRAMES64 + 40_000, 1, 0, (1, 14), None), (40_000, 0, 0, (2,), None)]),
+        (1000, "zero", [(40_000, 0, 0, (3,), None), (3_000, 0, 0, (14,), None)]),                # 1000 > 256: capacity 1024, history lost
+        (100, "keep", [(FRAMES64 + 40_000, 1, 0, (1, 14), None),                                # path 1 narrows 1024 -> 256; its remainder's history is 1024 input samples
+                       (40_000, 0, 0, (2,), None), (40_000, 0, 0, (5, J), "FIR_TIME_DOMAIN_F32"), (40_000, 0, 0, (4, J), "FIR_TIME_DOMAIN_BF16X3"),
+                       (40_000, 1, 0, (5, J), None), (2_000, 0, 0, (14,), None)]),
+        (2000, "zero", [(20_000, 0, 0, (14,), None), (5_000, 1, 0, (14,), None)]),              # 2000 > 1024: capacity 2048, history lost
+    ], 42)
+
+
+def test_settings_changed_complex_1000_100_700(G):
+    _settings_stream(G, True, 1, [
+        (1000, "new", [(40_000, 0, 0, (3,), None), (2_000, 1, 1, (14,), None)]),
+        (100, "keep", [(40_000, 0, 0, (5, J), "FIR_TIME_DOMAIN_F32"), (40_000, 0, 0, (2,), None), (40_000, 1, 0, (5, J), None)]),
+        (700, "keep", [(40_000, 0, 0, (3,), None), (3_000, 0, 0, (14,), None), (40_000, 0, 0, (3,), None)]),  # back within 1024: the long history was kept
+    ], 43)
+
+
+def test_settings_changed_float_decimate_by_8_1024_64_1000_2000(G):
+    _settings_stream(G, False, 8, [
+        (1024, "new", [(1 << 17, 0, 0, (9,), None), (FD8, 0, 1, (11,), None)]),
+        (64, "keep", [(1 << 17, 0, 0, (10,), None), (1 << 17, 1, 0, (14,), None), (FD8, 0, 1, (11,), None)]),
+        (1000, "keep", [(1 << 17, 0, 0, (9,), None), (1 << 17, 1, 0, (13, J), None), (8_000, 0, 0, (14,), None)]),
+        (2000, "zero", [(1 << 17, 0, 0, (13, J), None), (8_000, 0, 0, (14,), None)]),
+    ], 44)
+
+
+# ------------------------------------------------------------------ d. input and output alignment chosen separately
+_LONG = (1 << 17) + 3
+# (cplx, D, ntaps): {(xoff, yoff): paths of each span}
+_ALIGN = {
+    (False, 1, 200): ([1_000, _LONG], {(0, 0): [(14,), (6,)], (1, 0): [(14,), (8, J)], (0, 1): [(14,), (14,)], (1, 1): [(14,), (14,)]}),
+    (True, 1, 200): ([1_000, _LONG, FRAMES64 + 3], {(0, 0): [(14,), (2,), (2,)], (1, 0): [(14,), (5, J), (1, 14)],
+                                                     (0, 1): [(14,), (14,), (1, 14)], (1, 1): [(14,), (14,), (1, 14)]}),
+    (False, 8, 1024): ([1_000, (1 << 17) + 24, FD8 + 24], {(0, 0): [(14,), (9,), (9,)], (1, 0): [(14,), (13, J), (13, J)],
+                                                          (0, 1): [(14,), (14,), (11,)], (1, 1): [(14,), (14,), (14,)]}),
+    (True, 8, 128): ([1_000, (1 << 17) + 24], {(0, 0): [(14,), (9,)], (1, 0): [(14,), (14,)], (0, 1): [(14,), (14,)], (1, 1): [(14,), (14,)]}),
+}
+
+
+@pytest.mark.parametrize("xoff,yoff", [(0, 0), (1, 0), (0, 1), (1, 1)])
+@pytest.mark.parametrize("cplx,D,ntaps", list(_ALIGN), ids=["float", "complex", "float_d8", "complex_d8"])
+def test_alignment_matrix(G, cplx, D, ntaps, xoff, yoff):
+    spans, want = _ALIGN[(cplx, D, ntaps)]
+    b = _taps(ntaps, D)
+    x = _signal(cplx, sum(spans), 50 + D + cplx)
+    f = G.fir_filter(b, torch.complex64 if cplx else torch.float32, decimate=D)
+    s = _Stream(G, f, x, D)
+    for n, w in zip(spans, want[(xoff, yoff)]):
+        s(n, w, xoff=xoff, yoff=yoff)
+    _check_stream(s, b, x, D)
