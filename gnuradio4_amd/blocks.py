@@ -5,6 +5,7 @@ Names, settings and error behaviour follow the reference blocks (citations relat
   FFT                                                                         blocks/fourier/.../fft.hpp
   math_const / math_nary (AddConst..Divide)                                   blocks/math/.../Math.hpp
   Rotator                                                                     blocks/math/.../Rotator.hpp
+  FrequencyEstimatorTimeDomain / FrequencyEstimatorFrequencyDomain            blocks/filter/.../FrequencyEstimator.hpp
   Chain                                                                       the runtime fusion of fir_filter -> FFT -> mag2
                                                                               (Merge<> analogue, core/.../BlockMerging.hpp:136-320)
 Blocks consume and produce torch tensors that live on the GPU (`process_bulk(x) -> y`); torch only provides the
@@ -647,6 +648,92 @@ class Rotator(_Handle):
         v = C.c_float(0)
         check(lib().gr4hip_rotator_phase(self._h, C.byref(v), _stream()), "Rotator.phase")
         return v.value
+
+
+class _FrequencyEstimator(_Handle):
+    """gr::filter::FrequencyEstimator{TimeDomain,FrequencyDomain}<float> (FrequencyEstimator.hpp:30-351) with the reference's setting names plus `chunk`
+    (inputs per output: 1 = processOne; decimating=True gives the decimating form's chunk, 10 / N).  process_bulk takes a multiple of `chunk` samples and returns
+    one estimate per chunk; every fallback of the reference repeats the previous output (include/gr4hip.h "frequency estimators").  A new block starts from
+    f_expected; reset() goes back to it, set_params() keeps the last estimate."""
+    _destroy = "gr4hip_freqest_destroy"
+    _method = None
+    _names = ("sample_rate", "f_min", "f_expected", "f_max", "epsilon")
+
+    def __init__(self, chunk: Optional[int] = None, decimating: bool = False, **settings):
+        super().__init__()
+        self._decimating = bool(decimating) and chunk is None
+        self._p = self._params(capi.FreqEstParams(), settings, chunk, init=True)
+        check(lib().gr4hip_freqest_create(C.byref(self._h), self._method, C.byref(self._p)), type(self).__name__)
+
+    def _params(self, p, settings, chunk, init=False):
+        if init:
+            check(lib().gr4hip_freqest_params_default(self._method, C.byref(p)), type(self).__name__)
+        for k, v in settings.items():
+            if k not in self._names + (self._extra,):
+                raise TypeError(f"{type(self).__name__}: unknown setting '{k}'")
+            setattr(p, k, v)
+        if chunk is not None:
+            p.chunk = int(chunk)
+        elif self._decimating:
+            p.chunk = self._decimating_chunk(p)
+        return p
+
+    def _decimating_chunk(self, p) -> int:
+        raise NotImplementedError
+
+    def geometry(self):
+        """(W, i_min, i_max): the samples each estimate is taken over and, for the frequency domain, the clamped search range [i_min, i_max)"""
+        w, a, b = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        check(lib().gr4hip_freqest_geometry(self._method, C.byref(self._p), C.byref(w), C.byref(a), C.byref(b)), type(self).__name__)
+        return w.value, a.value, b.value
+
+    @property
+    def chunk(self) -> int:
+        return int(self._p.chunk)
+
+    def __getattr__(self, name):
+        if name in type(self)._names + (type(self)._extra,):
+            return getattr(self.__dict__["_p"], name)
+        raise AttributeError(name)
+
+    def set_params(self, chunk: Optional[int] = None, **settings):
+        """settingsChanged: the histories are emptied, the last estimate is kept"""
+        p = self._params(capi.FreqEstParams.from_buffer_copy(self._p), settings, chunk)
+        check(lib().gr4hip_freqest_set_params(self._h, C.byref(p)), f"{type(self).__name__}.set_params")
+        self._p = p
+
+    def reset(self):
+        """reset(): the histories are emptied, the last estimate becomes f_expected"""
+        check(lib().gr4hip_freqest_reset(self._h), f"{type(self).__name__}.reset")
+
+    def process_bulk(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        x = _dev(x, type(self).__name__)
+        if x.dtype != torch.float32:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, type(self).__name__, f"expected torch.float32, got {x.dtype}")
+        n_out = x.numel() // self.chunk
+        out = _out(out, n_out, torch.float32, x, f"{type(self).__name__}.process")
+        check(lib().gr4hip_freqest_process(self._h, x.data_ptr(), x.numel(), out.data_ptr(), None, _stream()), f"{type(self).__name__}.process")
+        return out[:n_out]
+
+
+class FrequencyEstimatorTimeDomain(_FrequencyEstimator):
+    """FrequencyEstimatorTimeDomain<float> (FrequencyEstimator.hpp:30-176); decimating=True: FrequencyEstimatorTimeDomainDecimating (Resampling<10U>, :179)"""
+    _method = capi.FREQEST_TIME_DOMAIN
+    _extra = "n_periods"
+
+    def _decimating_chunk(self, p) -> int:
+        return 10
+
+
+class FrequencyEstimatorFrequencyDomain(_FrequencyEstimator):
+    """FrequencyEstimatorFrequencyDomain<float> (FrequencyEstimator.hpp:186-351); decimating=True: the decimating form, chunk = N (initialiseFFT, :231-242)"""
+    _method = capi.FREQEST_FREQUENCY_DOMAIN
+    _extra = "min_fft_size"
+
+    def _decimating_chunk(self, p) -> int:
+        w = C.c_size_t(0)
+        check(lib().gr4hip_freqest_geometry(self._method, C.byref(p), C.byref(w), None, None), type(self).__name__)
+        return int(w.value)
 
 
 def synth_c32(n: int, seed: int = 42, tone_frel: float = 0.1, tone_amp: float = 1.0, noise_amp: float = 1.0, device="cuda") -> torch.Tensor:

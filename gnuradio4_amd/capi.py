@@ -161,11 +161,27 @@ SIGNATURES = {
     "gr4hip_synth_draws": (_i, [_vp, _sz, C.c_uint64, C.c_uint64, _vp]),
     "gr4hip_synth_c32": (_i, [_vp, _sz, C.c_uint64, _d, _f, _f, _vp]),
     "gr4hip_synth_f32": (_i, [_vp, _sz, C.c_uint64, _d, _f, _f, _vp]),
+    "gr4hip_freqest_params_default": (_i, [_i, _vp]),
+    "gr4hip_freqest_geometry": (_i, [_i, _vp, _psz, _psz, _psz]),
+    "gr4hip_freqest_create": (_i, [_pvp, _i, _vp]),
+    "gr4hip_freqest_set_params": (_i, [_vp, _vp]),
+    "gr4hip_freqest_reset": (_i, [_vp]),
+    "gr4hip_freqest_process": (_i, [_vp, _vp, _sz, _vp, _psz, _vp]),
+    "gr4hip_freqest_destroy": (_i, [_vp]),
 }
 
 class FilterParams(C.Structure):
     _fields_ = [("order", C.c_size_t), ("f_low", _d), ("f_high", _d), ("gain", _d), ("ripple_db", _d), ("attenuation_db", _d),
                 ("beta", _d), ("fs", _d)]
+
+
+FREQEST_TIME_DOMAIN, FREQEST_FREQUENCY_DOMAIN = range(2)
+
+
+class FreqEstParams(C.Structure):
+    """gr4hip_freqest_params: the settings of FrequencyEstimatorTimeDomain / ...FrequencyDomain (FrequencyEstimator.hpp:46-51, 202-207) plus the chunk"""
+    _fields_ = [("sample_rate", _f), ("f_min", _f), ("f_expected", _f), ("f_max", _f), ("epsilon", _f),
+                ("n_periods", C.c_size_t), ("min_fft_size", C.c_size_t), ("chunk", C.c_size_t)]
 
 
 LOWPASS, HIGHPASS, BANDPASS, BANDSTOP = range(4)

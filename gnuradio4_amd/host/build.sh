@@ -26,5 +26,6 @@ if stale $OUT/bench_host_feed tests/bench_host_feed.cpp; then $CXX -O2 tests/ben
 if stale $OUT/bench_host_fanin tests/bench_host_fanin.cpp; then $CXX -O2 tests/bench_host_fanin.cpp -o $OUT/bench_host_fanin $LINK & pids+=($!); fi
 if stale $OUT/dump_signal_generator tests/dump_signal_generator.cpp; then $CXX -O2 tests/dump_signal_generator.cpp -o $OUT/dump_signal_generator $LINK & pids+=($!); fi
 if stale $OUT/test_host_plugin tests/test_host_plugin.cpp; then $CXX -O2 tests/test_host_plugin.cpp -o $OUT/test_host_plugin -ldl & pids+=($!); fi
+if stale $OUT/test_host_freq_est tests/test_host_freq_est.cpp; then $CXX -O2 tests/test_host_freq_est.cpp -o $OUT/test_host_freq_est -ldl & pids+=($!); fi
 for p in "${pids[@]}"; do wait $p; done
 echo "built $(realpath $OUT)"

@@ -359,6 +359,64 @@ inline bool gr_enum_parse(Design& d, std::string_view s) { return gr::detail::en
 }
 inline bool gr_enum_parse(FilterType& d, std::string_view s) { return gr::detail::enum_from_names(d, s, std::array<std::string_view, 2>{"FIR", "IIR"}); }
 inline bool gr_enum_parse(Type& d, std::string_view s) { return gr::detail::enum_from_names(d, s, std::array<std::string_view, 4>{"LOWPASS", "HIGHPASS", "BANDPASS", "BANDSTOP"}); }
+
+// FrequencyEstimatorTimeDomain<float, Args...> / FrequencyEstimatorFrequencyDomain<float, Args...> (blocks/filter/.../FrequencyEstimator.hpp:30-351): the settings
+// and their checks (settingsChanged :62-69, :222-229).  Device-only: the estimates are computed behind compute_domain gpu:hip (gr4hip_freqest_*, gr4/hip.hpp); the
+// host processBulk refuses loudly (work::Status::ERROR).  One output per input chunk: 1 without resampling (processOne), 10 for ...Decimating (Resampling<10U>, :179), N for the
+// frequency-domain decimating form (initialiseFFT sets input_chunk_size = N, :231-242).
+inline void frequency_estimator_check(float fs, float fmin, float fexp, float fmax) { // (:63-66)
+    if (fmin < 0.f || fmax >= fs / 2.f || fexp < 0.f || fexp >= fs / 2.f)
+        throw std::invalid_argument("Ill-formed block parameters: f_min < f_expected < f_max < sample_rate/2 (Nyquist limit) violated");
+}
+
+template <typename T, typename... Args>
+    requires std::floating_point<T>
+struct FrequencyEstimatorTimeDomain : Block<FrequencyEstimatorTimeDomain<T, Args...>, Args...> {
+    using TParent = Block<FrequencyEstimatorTimeDomain<T, Args...>, Args...>;
+    PortIn<T>  in;
+    PortOut<T> out;
+    float      sample_rate = 1e3f, f_min = 40.f, f_expected = 50.f, f_max = 60.f; // (:46-51)
+    Size_t     n_periods = 4U;
+    T          epsilon   = T(1e-8);
+    GR_MAKE_REFLECTABLE(FrequencyEstimatorTimeDomain, in, out, sample_rate, f_expected, f_min, f_max, n_periods, epsilon);
+    void settingsChanged(const property_map&, const property_map&) { frequency_estimator_check(sample_rate, f_min, f_expected, f_max); }
+    [[nodiscard]] std::size_t chunk() const { return TParent::ResamplingControl::kEnabled ? std::max<std::size_t>(1, this->input_chunk_size) : 1; }
+    work::Status processBulk(std::span<const T>, std::span<T>) { // (the graph ends with ERROR: no numbers come out of the host path)
+        std::fprintf(stderr, "FrequencyEstimatorTimeDomain: device-only block, needs compute_domain gpu:hip\n");
+        return work::Status::ERROR;
+    }
+};
+template <typename T>
+using FrequencyEstimatorTimeDomainDecimating = FrequencyEstimatorTimeDomain<T, Resampling<10U>>;
+
+template <typename T, typename... Args>
+    requires std::floating_point<T>
+struct FrequencyEstimatorFrequencyDomain : Block<FrequencyEstimatorFrequencyDomain<T, Args...>, Args...> {
+    using TParent = Block<FrequencyEstimatorFrequencyDomain<T, Args...>, Args...>;
+    PortIn<T>  in;
+    PortOut<T> out;
+    float      sample_rate = 1e3f, f_min = 40.f, f_expected = 50.f, f_max = 60.f; // (:202-207)
+    Size_t     min_fft_size = 256U;
+    T          epsilon      = T(1e-8);
+    GR_MAKE_REFLECTABLE(FrequencyEstimatorFrequencyDomain, in, out, sample_rate, f_expected, f_min, f_max, min_fft_size, epsilon);
+    void settingsChanged(const property_map&, const property_map&) {
+        frequency_estimator_check(sample_rate, f_min, f_expected, f_max);
+        if constexpr (TParent::ResamplingControl::kEnabled && !TParent::ResamplingControl::kIsConst) { // initialiseFFT (:231-242): the chunk is N
+            gr4hip_freqest_params p{sample_rate, f_min, f_expected, f_max, static_cast<float>(epsilon), 1, min_fft_size, 1};
+            std::size_t N = 0;
+            if (gr4hip_freqest_geometry(GR4HIP_FREQEST_FREQUENCY_DOMAIN, &p, &N, nullptr, nullptr) != GR4HIP_OK) throw std::invalid_argument(std::string("FrequencyEstimatorFrequencyDomain: ") + gr4hip_last_error());
+            this->input_chunk_size = static_cast<Size_t>(N);
+        }
+    }
+    [[nodiscard]] std::size_t chunk() const { return TParent::ResamplingControl::kEnabled ? std::max<std::size_t>(1, this->input_chunk_size) : 1; }
+    work::Status processBulk(std::span<const T>, std::span<T>) { // (the graph ends with ERROR: no numbers come out of the host path)
+        std::fprintf(stderr, "FrequencyEstimatorFrequencyDomain: device-only block, needs compute_domain gpu:hip\n");
+        return work::Status::ERROR;
+    }
+};
+// the registered decimating form says Resampling<10U>, but initialiseFFT overrides the chunk with N
+template <typename T>
+using FrequencyEstimatorFrequencyDomainDecimating = FrequencyEstimatorFrequencyDomain<T, Resampling<10U>>;
 } // namespace gr::filter
 namespace gr::algorithm::window {
 enum class Type : int { None, Rectangular, Hamming, Hann, HannExp, Blackman, Nuttall, BlackmanHarris, BlackmanNuttall, FlatTop, Exponential, Kaiser }; // window.hpp:35 == GR4HIP_WIN_*

@@ -552,6 +552,25 @@ struct RotatorStage final : Stage {
     }
 };
 
+// FrequencyEstimator{TimeDomain,FrequencyDomain}<float>: one estimate per chunk; a settings change keeps the last estimate (gr4hip_freqest_set_params)
+struct FreqEstStage final : Stage {
+    gr4hip_freqest_t* h = nullptr;
+    FreqEstStage(int method, const gr4hip_freqest_params& p) {
+        in_bytes = out_bytes = 4; in_chunk = p.chunk; out_chunk = 1;
+        check(gr4hip_freqest_create(&h, method, &p), "gr4hip_freqest_create");
+    }
+    ~FreqEstStage() override { gr4hip_freqest_destroy(h); }
+    bool set_params(const gr4hip_freqest_params& p) {
+        if (p.chunk != in_chunk) return false;
+        check(gr4hip_freqest_set_params(h, &p), "gr4hip_freqest_set_params");
+        return true;
+    }
+    std::string_view kind() const override { return "freq_est"; }
+    int enqueue(const void* in, std::size_t n, void* out, std::size_t* n_out, gr4hip_stream_t s) override {
+        return gr4hip_freqest_process(h, static_cast<const float*>(in), n, static_cast<float*>(out), n_out, s);
+    }
+};
+
 // ---- the float64 instantiations the reference registers (time_domain_filter.hpp:20, 57-60; Rotator.hpp:15; fourier/fft.hpp:29): plain FP64 kernels
 struct Fir64Stage final : Stage {
     gr4hip_fir64_t* h = nullptr;
@@ -801,6 +820,25 @@ struct Kernel<gr::blocks::math::Rotator<std::complex<float>>> {
     using B = gr::blocks::math::Rotator<std::complex<float>>;
     static std::unique_ptr<Stage> make_stage(B& b) { return std::make_unique<RotatorStage>(b.phase_increment, b._accumulated_phase); }
     static work::Status           work(B& b, std::size_t nIn, std::size_t nOut) { return offload_work(b, nIn, nOut, make_stage); }
+};
+
+template <typename... Args>
+struct Kernel<gr::filter::FrequencyEstimatorTimeDomain<float, Args...>> {
+    using B = gr::filter::FrequencyEstimatorTimeDomain<float, Args...>;
+    static gr4hip_freqest_params params(B& b) { return {b.sample_rate, b.f_min, b.f_expected, b.f_max, b.epsilon, b.n_periods, 256, b.chunk()}; }
+    static std::unique_ptr<Stage> make_stage(B& b) { return std::make_unique<FreqEstStage>(GR4HIP_FREQEST_TIME_DOMAIN, params(b)); }
+    static work::Status work(B& b, std::size_t nIn, std::size_t nOut) {
+        return offload_work(b, nIn, nOut, make_stage, [](Stage& st, B& blk) { return static_cast<FreqEstStage&>(st).set_params(params(blk)); });
+    }
+};
+template <typename... Args>
+struct Kernel<gr::filter::FrequencyEstimatorFrequencyDomain<float, Args...>> {
+    using B = gr::filter::FrequencyEstimatorFrequencyDomain<float, Args...>;
+    static gr4hip_freqest_params params(B& b) { return {b.sample_rate, b.f_min, b.f_expected, b.f_max, b.epsilon, 4, b.min_fft_size, b.chunk()}; }
+    static std::unique_ptr<Stage> make_stage(B& b) { return std::make_unique<FreqEstStage>(GR4HIP_FREQEST_FREQUENCY_DOMAIN, params(b)); }
+    static work::Status work(B& b, std::size_t nIn, std::size_t nOut) {
+        return offload_work(b, nIn, nOut, make_stage, [](Stage& st, B& blk) { return static_cast<FreqEstStage&>(st).set_params(params(blk)); });
+    }
 };
 
 // ---- merged blocks (gr4/merge.hpp): the parts of a Merge<> become stages of one block; intermediates stay in HBM

@@ -68,6 +68,10 @@ const bool registered = [] {
     r.insert<BasicDecimatingFilter<float>>(named<float>("gr::filter::BasicFilterProto", ", gr::Resampling<1, 1, false>"));
     r.insert<gr::blocks::math::Rotator<std::complex<float>>>(named<std::complex<float>>("gr::blocks::math::Rotator"));
     r.insert<gr::blocks::math::Rotator<std::complex<double>>>(named<std::complex<double>>("gr::blocks::math::Rotator"));
+    r.insert<FrequencyEstimatorTimeDomain<float>>(named<float>("gr::filter::FrequencyEstimatorTimeDomain")); // FrequencyEstimator.hpp:25-26, 181-182 (float only)
+    r.insert<FrequencyEstimatorTimeDomainDecimating<float>>(named<float>("gr::filter::FrequencyEstimatorTimeDomainDecimating"));
+    r.insert<FrequencyEstimatorFrequencyDomain<float>>(named<float>("gr::filter::FrequencyEstimatorFrequencyDomain"));
+    r.insert<FrequencyEstimatorFrequencyDomainDecimating<float>>(named<float>("gr::filter::FrequencyEstimatorFrequencyDomainDecimating"));
     r.insert<gr::blocks::fft::FFT<double, gr::DataSet<double>>>(named<double>("gr::blocks::fft::FFT"));
     r.insert<gr::blocks::fft::FFT<float>>(named<float>("gr::blocks::fft::FFT"));
     r.insert<gr::blocks::fft::FFT<std::complex<float>>>(named<std::complex<float>>("gr::blocks::fft::FFT"));

@@ -540,6 +540,49 @@ int gr4hip_synth_draws(uint64_t* d_out_u64, size_t n_draws, uint64_t seed, uint6
 int gr4hip_synth_c32(void* d_out_c32, size_t n, uint64_t seed, double tone_frel, float tone_amp, float noise_amp, gr4hip_stream_t stream);
 int gr4hip_synth_f32(float* d_out, size_t n, uint64_t seed, double tone_frel, float tone_amp, float noise_amp, gr4hip_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------ frequency estimators (blocks/filter/.../FrequencyEstimator.hpp)
+ * FrequencyEstimatorTimeDomain<float> (:30-176, Krajewski et al. 2022) and FrequencyEstimatorFrequencyDomain<float> (:186-351, Gasior & Gonzalez 2004), float only
+ * (the reference's double registrations have no entry point here).  Design notes: FREQ_EST.md.  One path per method,
+ * parameterised by the chunk C >= 1: output m is the estimate after input sample (m + 1) C - 1 over the last W samples seen.  processOne is C = 1, the
+ * decimating forms are C = 10 (time domain, Resampling<10U>, :179) and C = N (frequency domain, initialiseFFT sets input_chunk_size = N, :231-242).
+ *   W (gr4hip_freqest_geometry): time domain N_est = n_periods * Size_t(fs / min(f_min, f_expected)) (fs / f_expected when f_min == 0), in float, truncated (:72);
+ *   frequency domain N = bit_ceil(max(min_fft_size, size_t(fs / min(f_min, f_expected)))) (:232); search range [i_min, i_max) with i_min = floor(f_min / fs N),
+ *   i_max = ceil(f_max / fs N) in float, both clamped to [1, N/2 - 1] (:300-306); an empty range (i_min >= i_max) gives k = i_max.
+ * Every output is a fresh estimate or, on any fallback of the reference (settling: fewer than W samples since reset; B <= eps, z outside (-1, 1); peak at the edge,
+ * non-positive or non-finite magnitudes, |denominator| < eps, |delta| >= 1), the previous output: a forward fill on the device across the launch and across calls.
+ *   time domain: the one Bessel biquad at f_max (iir::designFilter<T, 0UZ>, :77 == gr4hip_iir_design(GR4HIP_BESSEL, order 2)) on the library's IIR path into a
+ *     scratch buffer of the handle; the window sums B = sum b^2, C = sum 2ab (= (y[i-1] + y[i+1])^2 / 2 where |4 y[i]| >= eps) direct per output or sliding
+ *     from a direct sum at the head of each run of outputs, in float64; z and acos in float64.  A NaN / Inf input poisons the biquad state: every later
+ *     output is NaN until reset / set_params, as in the reference.
+ *   frequency domain: only bins i_min - 1 .. i_max are evaluated.  The symmetric Hann window (window.hpp:92-97) is 1/2 - e^{j a i}/4 - e^{-j a i}/4, a = 2 pi / (N - 1),
+ *     so each bin is three sliding sums S_theta(n) = sum_i x[n - i] e^{-j theta i} (theta = 2 pi k / N and +-a), updated in O(1) in float64 and anchored by a direct sum at
+ *     the head of every tile of outputs (C < N); with C >= N every output is its own direct sum.  Non-finite samples enter the sums as 0 and are counted: a window
+ *     that holds one gives the previous output (the reference's FFT turns it into non-finite magnitudes).  A search range of more than 2046 bins
+ *     (i_max - i_min + 2 > 2048) returns GR4HIP_UNSUPPORTED.
+ *   GR4HIP_UNSUPPORTED also for W > 2^20, N < 4 and f_max <= 0 (the reference's doc calls f_max < 0 "disable" but its code designs the low-pass anyway);
+ *   GR4HIP_INVALID_ARGUMENT for what settingsChanged rejects (f_min < 0, f_max >= fs/2, f_expected < 0, f_expected >= fs/2; :62-69, :222-229), for f_expected == 0
+ *   (the reference divides by it), non-finite settings, fs <= 0, n_periods == 0 (time domain), chunk == 0 and n_in % chunk != 0.  All of it is checked on the
+ *   host before any device work.
+ * The last estimate: create and reset leave f_expected (reset(), :82-85, :244-247: a created handle is a block that has been reset); set_params keeps it
+ * (settingsChanged only re-initialises: histories emptied).  Both are host-side notes applied by the next process call on its stream. */
+typedef struct gr4hip_freqest gr4hip_freqest_t;
+typedef enum { GR4HIP_FREQEST_TIME_DOMAIN = 0, GR4HIP_FREQEST_FREQUENCY_DOMAIN = 1 } gr4hip_freqest_method;
+typedef struct {
+    float  sample_rate, f_min, f_expected, f_max, epsilon;
+    size_t n_periods;    /* time domain */
+    size_t min_fft_size; /* frequency domain */
+    size_t chunk;        /* C: inputs per output */
+} gr4hip_freqest_params;
+int gr4hip_freqest_params_default(int method, gr4hip_freqest_params* p); /* the blocks' defaults (fs 1000, 40 / 50 / 60 Hz, eps 1e-8, n_periods 4, min_fft_size 256); chunk 1 */
+/* host only: W (N_est or N) and, for the frequency domain, the clamped search range (0, 0 for the time domain); same validation as create */
+int gr4hip_freqest_geometry(int method, const gr4hip_freqest_params* p, size_t* window, size_t* i_min, size_t* i_max);
+int gr4hip_freqest_create(gr4hip_freqest_t** fe, int method, const gr4hip_freqest_params* p);
+int gr4hip_freqest_set_params(gr4hip_freqest_t* fe, const gr4hip_freqest_params* p); /* settingsChanged: histories emptied, the last estimate kept */
+int gr4hip_freqest_reset(gr4hip_freqest_t* fe);                                      /* reset(): histories emptied, the last estimate = f_expected */
+/* n_in a multiple of chunk; writes n_in / chunk outputs (*n_out, may be NULL) */
+int gr4hip_freqest_process(gr4hip_freqest_t* fe, const float* d_in, size_t n_in, float* d_out, size_t* n_out, gr4hip_stream_t stream);
+int gr4hip_freqest_destroy(gr4hip_freqest_t* fe);
+
 #ifdef __cplusplus
 }
 #endif
