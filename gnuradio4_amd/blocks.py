@@ -6,6 +6,7 @@ Names, settings and error behaviour follow the reference blocks (citations relat
   math_const / math_nary (AddConst..Divide)                                   blocks/math/.../Math.hpp
   Rotator                                                                     blocks/math/.../Rotator.hpp
   FrequencyEstimatorTimeDomain / FrequencyEstimatorFrequencyDomain            blocks/filter/.../FrequencyEstimator.hpp
+  IQDemodulator                                                               blocks/filter/.../FrequencyEstimator.hpp
   Chain                                                                       the runtime fusion of fir_filter -> FFT -> mag2
                                                                               (Merge<> analogue, core/.../BlockMerging.hpp:136-320)
 Blocks consume and produce torch tensors that live on the GPU (`process_bulk(x) -> y`); torch only provides the
@@ -734,6 +735,69 @@ class FrequencyEstimatorFrequencyDomain(_FrequencyEstimator):
         w = C.c_size_t(0)
         check(lib().gr4hip_freqest_geometry(self._method, C.byref(p), C.byref(w), None, None), type(self).__name__)
         return int(w.value)
+
+
+class IQDemodulator(_Handle):
+    """gr::filter::IQDemodulator<T> (FrequencyEstimator.hpp:356-653), T in {float32, float64}: a lock-in amplifier with the reference's setting names plus
+    `chunk` (input_chunk_size, the registered Resampling<1024U, 1U, false>).  process_bulk(ref, resp) takes a multiple of `chunk` samples of each input and
+    returns (amplitude, phase, frequency), one value per chunk (include/gr4hip.h "IQ demodulator").  set_params re-initialises the filters iff it names
+    sample_rate, f_high_pass, f_low_pass or derivative_method (settingsChanged, :454-466); reset() always does."""
+    _destroy = "gr4hip_iqdemod_destroy"
+    _names = ("sample_rate", "f_high_pass", "f_low_pass", "phase_unit", "invert_phase", "derivative_method", "epsilon")
+    _filter_keys = ("sample_rate", "f_high_pass", "f_low_pass", "derivative_method")
+
+    def __init__(self, dtype=torch.float32, chunk: int = 1024, **settings):
+        super().__init__()
+        if dtype not in (torch.float32, torch.float64):
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "IQDemodulator", f"dtype {dtype}: float32 or float64")
+        self.dtype = dtype
+        p = capi.IQDemodParams()
+        check(lib().gr4hip_iqdemod_params_default(C.byref(p)), "IQDemodulator")
+        self._p = self._params(p, settings, chunk)
+        check(lib().gr4hip_iqdemod_create(C.byref(self._h), _DTYPE_ID[dtype], C.byref(self._p)), "IQDemodulator")
+
+    def _params(self, p, settings, chunk):
+        for k, v in settings.items():
+            if k not in self._names:
+                raise TypeError(f"IQDemodulator: unknown setting '{k}'")
+            if k == "phase_unit" and isinstance(v, str):
+                v = {"radians": 0, "degrees": 1}[v.lower()]
+            setattr(p, k, int(v) if k in ("phase_unit", "invert_phase", "derivative_method") else v)
+        if chunk is not None:
+            p.chunk = int(chunk)
+        return p
+
+    @property
+    def chunk(self) -> int:
+        return int(self._p.chunk)
+
+    def __getattr__(self, name):
+        if name in type(self)._names:
+            return getattr(self.__dict__["_p"], name)
+        raise AttributeError(name)
+
+    def set_params(self, chunk: Optional[int] = None, **settings):
+        """settingsChanged: a filter key in `settings` re-initialises the filters, the other settings (and chunk) keep their state"""
+        p = self._params(capi.IQDemodParams.from_buffer_copy(self._p), settings, chunk)
+        reinit = any(k in self._filter_keys for k in settings)
+        check(lib().gr4hip_iqdemod_set_params(self._h, C.byref(p), int(reinit)), "IQDemodulator.set_params")
+        self._p = p
+
+    def reset(self):
+        """reset(): the filters are re-initialised"""
+        check(lib().gr4hip_iqdemod_reset(self._h), "IQDemodulator.reset")
+
+    def process_bulk(self, ref: torch.Tensor, resp: torch.Tensor, amplitude: Optional[torch.Tensor] = None, phase: Optional[torch.Tensor] = None,
+                     frequency: Optional[torch.Tensor] = None):
+        ref, resp = _dev(ref, "IQDemodulator"), _dev(resp, "IQDemodulator")
+        if ref.dtype != self.dtype or resp.dtype != self.dtype or ref.numel() != resp.numel() or ref.device != resp.device:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "IQDemodulator", f"ref and resp must be {self.dtype} tensors of one length on one device")
+        n = ref.numel()
+        n_out = n // self.chunk
+        outs = [_out(o, n_out, self.dtype, ref, "IQDemodulator.process") for o in (amplitude, phase, frequency)]
+        check(lib().gr4hip_iqdemod_process(self._h, ref.data_ptr(), resp.data_ptr(), n, outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), None,
+                                           _stream()), "IQDemodulator.process")
+        return tuple(o[:n_out] for o in outs)
 
 
 def synth_c32(n: int, seed: int = 42, tone_frel: float = 0.1, tone_amp: float = 1.0, noise_amp: float = 1.0, device="cuda") -> torch.Tensor:

@@ -168,6 +168,13 @@ SIGNATURES = {
     "gr4hip_freqest_reset": (_i, [_vp]),
     "gr4hip_freqest_process": (_i, [_vp, _vp, _sz, _vp, _psz, _vp]),
     "gr4hip_freqest_destroy": (_i, [_vp]),
+    "gr4hip_iqdemod_params_default": (_i, [_vp]),
+    "gr4hip_iqdemod_check": (_i, [_i, _vp]),
+    "gr4hip_iqdemod_create": (_i, [_pvp, _i, _vp]),
+    "gr4hip_iqdemod_set_params": (_i, [_vp, _vp, _i]),
+    "gr4hip_iqdemod_reset": (_i, [_vp]),
+    "gr4hip_iqdemod_process": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _psz, _vp]),
+    "gr4hip_iqdemod_destroy": (_i, [_vp]),
 }
 
 class FilterParams(C.Structure):
@@ -182,6 +189,12 @@ class FreqEstParams(C.Structure):
     """gr4hip_freqest_params: the settings of FrequencyEstimatorTimeDomain / ...FrequencyDomain (FrequencyEstimator.hpp:46-51, 202-207) plus the chunk"""
     _fields_ = [("sample_rate", _f), ("f_min", _f), ("f_expected", _f), ("f_max", _f), ("epsilon", _f),
                 ("n_periods", C.c_size_t), ("min_fft_size", C.c_size_t), ("chunk", C.c_size_t)]
+
+
+class IQDemodParams(C.Structure):
+    """gr4hip_iqdemod_params: the settings of IQDemodulator<T> (FrequencyEstimator.hpp:423-429) plus the chunk"""
+    _fields_ = [("sample_rate", _f), ("f_high_pass", _f), ("f_low_pass", _f), ("phase_unit", _i), ("invert_phase", _i), ("derivative_method", _i),
+                ("epsilon", _d), ("chunk", C.c_size_t)]
 
 
 LOWPASS, HIGHPASS, BANDPASS, BANDSTOP = range(4)

@@ -27,5 +27,6 @@ if stale $OUT/bench_host_fanin tests/bench_host_fanin.cpp; then $CXX -O2 tests/b
 if stale $OUT/dump_signal_generator tests/dump_signal_generator.cpp; then $CXX -O2 tests/dump_signal_generator.cpp -o $OUT/dump_signal_generator $LINK & pids+=($!); fi
 if stale $OUT/test_host_plugin tests/test_host_plugin.cpp; then $CXX -O2 tests/test_host_plugin.cpp -o $OUT/test_host_plugin -ldl & pids+=($!); fi
 if stale $OUT/test_host_freq_est tests/test_host_freq_est.cpp; then $CXX -O2 tests/test_host_freq_est.cpp -o $OUT/test_host_freq_est -ldl & pids+=($!); fi
+if stale $OUT/test_host_iq_demod tests/test_host_iq_demod.cpp; then $CXX -O2 tests/test_host_iq_demod.cpp -o $OUT/test_host_iq_demod -ldl & pids+=($!); fi
 for p in "${pids[@]}"; do wait $p; done
 echo "built $(realpath $OUT)"

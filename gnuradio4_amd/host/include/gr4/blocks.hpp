@@ -417,6 +417,72 @@ struct FrequencyEstimatorFrequencyDomain : Block<FrequencyEstimatorFrequencyDoma
 // the registered decimating form says Resampling<10U>, but initialiseFFT overrides the chunk with N
 template <typename T>
 using FrequencyEstimatorFrequencyDomainDecimating = FrequencyEstimatorFrequencyDomain<T, Resampling<10U>>;
+
+// IQDemodulator<T, Args...> (blocks/filter/.../FrequencyEstimator.hpp:356-653): a lock-in amplifier with two inputs (ref, resp) and three outputs (amplitude,
+// phase, frequency), one output per input chunk.  Device-only: computed behind compute_domain gpu:hip (gr4hip_iqdemod_*, gr4/hip.hpp); off the device the work
+// loop refuses loudly (deviceOnly: work::Status::ERROR).  A settings update that names sample_rate, f_high_pass, f_low_pass or derivative_method re-initialises
+// the filters (settingsChanged, :454-466); with Derivative<M, true> an update that names derivative_method throws (:455-459).
+enum class PhaseUnit : int { Radians = 0, Degrees = 1 };
+enum class DerivativeMethod : int { SymmetricDifference = 0, SavitzkyGolay5 = 1, SavitzkyGolay7 = 2 };
+inline bool gr_enum_parse(PhaseUnit& d, std::string_view s) { return gr::detail::enum_from_names(d, s, std::array<std::string_view, 2>{"Radians", "Degrees"}); }
+inline bool gr_enum_parse(DerivativeMethod& d, std::string_view s) {
+    return gr::detail::enum_from_names(d, s, std::array<std::string_view, 3>{"SymmetricDifference", "SavitzkyGolay5", "SavitzkyGolay7"});
+}
+template <DerivativeMethod method = DerivativeMethod::SymmetricDifference, bool isConst = false>
+struct Derivative {
+    static constexpr DerivativeMethod kMethod  = method;
+    static constexpr bool             kIsConst = isConst;
+};
+namespace detail {
+template <typename T>
+struct is_derivative : std::false_type {};
+template <DerivativeMethod M, bool C>
+struct is_derivative<Derivative<M, C>> : std::true_type {};
+template <typename... Args>
+struct find_derivative {
+    using type = Derivative<>;
+};
+template <typename A, typename... R>
+struct find_derivative<A, R...> {
+    using type = std::conditional_t<is_derivative<A>::value, A, typename find_derivative<R...>::type>;
+};
+} // namespace detail
+
+template <typename T, typename... Args>
+    requires std::floating_point<T>
+struct IQDemodulator : Block<IQDemodulator<T, Args...>, Args...> {
+    using TParent           = Block<IQDemodulator<T, Args...>, Args...>;
+    using DerivativeControl = typename detail::find_derivative<Args...>::type;
+    PortIn<T>        ref, resp;
+    PortOut<T>       amplitude, phase, frequency;
+    float            sample_rate = 62.5e6f, f_high_pass = 100.f, f_low_pass = 10000.f; // (:423-429)
+    PhaseUnit        phase_unit        = PhaseUnit::Radians;
+    bool             invert_phase      = false;
+    DerivativeMethod derivative_method = DerivativeControl::kMethod;
+    T                epsilon           = T(1e-12);
+    bool             _filters_changed  = false; // an update named a filter key since the device handle last took the settings
+    GR_MAKE_REFLECTABLE(IQDemodulator, ref, resp, amplitude, phase, frequency, sample_rate, f_high_pass, f_low_pass, phase_unit, invert_phase, derivative_method, epsilon);
+    void settingsChanged(const property_map&, const property_map& newSettings) {
+        if constexpr (DerivativeControl::kIsConst) {
+            if (newSettings.contains("derivative_method")) throw std::invalid_argument("derivative_method is compile-time fixed and cannot be changed at runtime");
+        }
+        if (newSettings.contains("sample_rate") || newSettings.contains("f_high_pass") || newSettings.contains("f_low_pass") || newSettings.contains("derivative_method")) {
+            if (f_high_pass <= 0.f || f_low_pass <= 0.f || f_high_pass >= f_low_pass || f_low_pass >= sample_rate / 2.f)
+                throw std::invalid_argument("invalid filter frequencies: 0 < f_hp < f_lp < fs/2 violated");
+            _filters_changed = true;
+        }
+    }
+    [[nodiscard]] std::size_t chunk() const { return TParent::ResamplingControl::kEnabled ? std::max<std::size_t>(1, this->input_chunk_size) : 1; }
+    work::Status deviceOnly() { // (the graph ends with ERROR: no numbers come out of the host path)
+        std::fprintf(stderr, "IQDemodulator: device-only block, needs compute_domain gpu:hip\n");
+        this->_log("IQDemodulator: device-only block, needs compute_domain gpu:hip");
+        return work::Status::ERROR;
+    }
+};
+template <typename T>
+using IQDemodulatorDecimating = IQDemodulator<T, Resampling<1024U, 1U, false>>;
+template <typename T, DerivativeMethod M>
+using IQDemodulatorFixed = IQDemodulator<T, Resampling<1024U, 1U, false>, Derivative<M, true>>;
 } // namespace gr::filter
 namespace gr::algorithm::window {
 enum class Type : int { None, Rectangular, Hamming, Hann, HannExp, Blackman, Nuttall, BlackmanHarris, BlackmanNuttall, FlatTop, Exponential, Kaiser }; // window.hpp:35 == GR4HIP_WIN_*

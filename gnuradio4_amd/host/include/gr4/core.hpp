@@ -1002,6 +1002,8 @@ public:
             for (auto& p : d.in) ins.push_back(p.buffer->read_span(nIn));
             std::span<T> os = d.out.buffer->write_span(nOut);
             return d.processBulk(std::span<const std::span<const T>>(ins), os);
+        } else if constexpr (requires { d.deviceOnly(); }) { // a device-only block of another port shape (IQDemodulator: 2 in, 3 out): refuses, no host fallback
+            return d.deviceOnly();
         } else {
             static_assert(sizeof(Derived) == 0, "unsupported port shape for the default work loop");
         }

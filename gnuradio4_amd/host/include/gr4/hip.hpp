@@ -841,6 +841,58 @@ struct Kernel<gr::filter::FrequencyEstimatorFrequencyDomain<float, Args...>> {
     }
 };
 
+// IQDemodulator<T>: two inputs, three outputs at the seam (like the N-input math blocks: no Stage, the planner leaves it to this per-block path).  Both input
+// spans go to HBM, one gr4hip_iqdemod_process, three spans back.  A settings change that named a filter key re-initialises the handle's filters; any other keeps them.
+template <typename T, typename... Args>
+struct Kernel<gr::filter::IQDemodulator<T, Args...>> {
+    using B = gr::filter::IQDemodulator<T, Args...>;
+    struct State final : Offload {
+        gr4hip_iqdemod_t* h = nullptr;
+        ~State() override { if (h) gr4hip_iqdemod_destroy(h); }
+    };
+    static gr4hip_iqdemod_params params(B& b) {
+        return {b.sample_rate, b.f_high_pass, b.f_low_pass, static_cast<int>(b.phase_unit), b.invert_phase ? 1 : 0, static_cast<int>(b.derivative_method),
+                static_cast<double>(b.epsilon), b.chunk()};
+    }
+    static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
+        try {
+            State*     st = offload_state<State>(blk);
+            const auto p  = params(blk);
+            if (!st->h) {
+                check(gr4hip_iqdemod_create(&st->h, dtype_of<T>(), &p), "gr4hip_iqdemod_create");
+                st->settings_generation = blk._settings_generation;
+                blk._filters_changed    = false;
+            } else if (st->settings_generation != blk._settings_generation) {
+                check(gr4hip_iqdemod_set_params(st->h, &p, blk._filters_changed ? 1 : 0), "gr4hip_iqdemod_set_params");
+                st->settings_generation = blk._settings_generation;
+                blk._filters_changed    = false;
+            }
+            const std::size_t bi = nIn * sizeof(T), bo = nOut * sizeof(T);
+            char*             hin = static_cast<char*>(st->h_in.ensure(2 * bi));
+            std::memcpy(hin, blk.ref.buffer->read_span(nIn).data(), bi);
+            std::memcpy(hin + bi, blk.resp.buffer->read_span(nIn).data(), bi);
+            char* din = static_cast<char*>(st->d_in.ensure(2 * bi));
+            check(gr4hip_memcpy_h2d(din, hin, 2 * bi, nullptr), "h2d");
+            char*       dout     = static_cast<char*>(st->d_out.ensure(3 * bo));
+            std::size_t produced = 0;
+            check(gr4hip_iqdemod_process(st->h, din, din + bi, nIn, dout, dout + bo, dout + 2 * bo, &produced, nullptr), "gr4hip_iqdemod_process");
+            if (produced != nOut) throw std::runtime_error("IQDemodulator: the work loop must hand over whole chunks");
+            const char* hout = static_cast<const char*>(st->h_out.ensure(3 * bo));
+            check(gr4hip_memcpy_d2h(const_cast<char*>(hout), dout, 3 * bo, nullptr), "d2h");
+            check(gr4hip_stream_synchronize(nullptr), "sync");
+            std::size_t k = 0;
+            for (auto* port : {&blk.amplitude, &blk.phase, &blk.frequency}) {
+                if (port->connected()) std::memcpy(port->buffer->write_span(nOut).data(), hout + k * bo, bo);
+                ++k;
+            }
+            return work::Status::OK;
+        } catch (const std::exception& e) {
+            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
+            return work::Status::ERROR; // never a silent host fallback
+        }
+    }
+};
+
 // ---- merged blocks (gr4/merge.hpp): the parts of a Merge<> become stages of one block; intermediates stay in HBM
 struct SeqStage final : Stage {
     std::unique_ptr<Stage> a, b;

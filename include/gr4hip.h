@@ -583,6 +583,42 @@ int gr4hip_freqest_reset(gr4hip_freqest_t* fe);                                 
 int gr4hip_freqest_process(gr4hip_freqest_t* fe, const float* d_in, size_t n_in, float* d_out, size_t* n_out, gr4hip_stream_t stream);
 int gr4hip_freqest_destroy(gr4hip_freqest_t* fe);
 
+/* ------------------------------------------------------------------------------------------------ IQ demodulator (FrequencyEstimator.hpp:356-653)
+ * IQDemodulator<T> (T = float: GR4HIP_F32, double: GR4HIP_F64), a lock-in amplifier: inputs ref (the DDS reference) and resp (the response), one output per
+ * chunk of C inputs on each of amplitude (A_resp / A_ref), phase and frequency.  Design notes: IQ_DEMOD.md.  Restates IQDemodulator<T> exactly:
+ *   coefficients in T as initialiseFilters (:468-506) computes them: alpha_hp = exp(T(-2) pi_v<T> T(f_high_pass) / T(sample_rate)), alpha_lp = 1 - exp(...)
+ *   likewise, the derivative taps {1,0,-1}, {0.2,0.1,0,-0.1,-0.2}, {3,2,1,0,-1,-2,-3}/28 in T, delays 1 / 2 / 3; then widened: every state is float64.
+ *   Per sample n since the last re-initialisation:  h[n] = alpha_hp (h[n-1] + v[n] - v[n-1]) per input (v[-1] = h[-1] = 0);  rQ = sum_k tap[k] h_ref[n-k] once
+ *   n + 1 >= K, else 0;  rI = h_ref[n-d], xI = h_resp[n-d] once n >= d, else 0 (the HistoryBuffer size tests of :548-555, across calls);  the products
+ *   xI rI, xI rQ, rI^2, rQ^2, xI^2 into five low-passes s += alpha_lp (p - s).  At the last sample of every chunk, step 5 (:571-640) in float64: amplitude,
+ *   G(omega) per method, three rounds of asin iterations with an Aitken step, atan2(Q, I sqrt(Pd / Pr)), invert_phase, degrees; rounded to T.  Outputs the
+ *   reference gives as 0 (Pr <= eps, Px <= eps, ...) are exactly 0.  A non-finite input poisons the states until re-initialisation, as in the reference:
+ *   from there on every output is 0.  Where the reference's float arithmetic is ill-conditioned (DC-only input, whose high-passed value decays below rounding;
+ *   |ratio / G| near 1 in the asin) the device gives the float64 result, not the float32 noise.
+ * GR4HIP_INVALID_ARGUMENT, checked on the host before any device work: what settingsChanged rejects (!(0 < f_hp < f_lp < fs / 2), in float, :461), non-finite
+ * settings, sample_rate <= 0, an unknown derivative_method or phase_unit, chunk == 0, n_in % chunk != 0, a dtype other than F32 / F64.
+ * reset() and set_params(reinitialise = 1) re-initialise the filters (states and history zeroed); set_params(reinitialise = 0) keeps them and takes phase_unit,
+ * invert_phase, epsilon and chunk -- the filter settings must then be unchanged.  reinitialise mirrors settingsChanged (:454-466): the caller passes whether the
+ * update named sample_rate, f_high_pass, f_low_pass or derivative_method.  Both are host-side notes applied by the next process call on its stream. */
+typedef struct gr4hip_iqdemod gr4hip_iqdemod_t;
+typedef struct {
+    float  sample_rate, f_high_pass, f_low_pass;
+    int    phase_unit;        /* 0 radians, 1 degrees */
+    int    invert_phase;      /* bool */
+    int    derivative_method; /* 0 symmetric difference, 1 Savitzky-Golay 5, 2 Savitzky-Golay 7 */
+    double epsilon;           /* rounded to T */
+    size_t chunk;             /* C: inputs per output (input_chunk_size) */
+} gr4hip_iqdemod_params;
+int gr4hip_iqdemod_params_default(gr4hip_iqdemod_params* p); /* the block's defaults (62.5 MHz, 100 Hz, 10 kHz, radians, eps 1e-12), chunk 1024 */
+int gr4hip_iqdemod_check(int dtype, const gr4hip_iqdemod_params* p); /* host only: the validation of create */
+int gr4hip_iqdemod_create(gr4hip_iqdemod_t** h, int dtype, const gr4hip_iqdemod_params* p);
+int gr4hip_iqdemod_set_params(gr4hip_iqdemod_t* h, const gr4hip_iqdemod_params* p, int reinitialise);
+int gr4hip_iqdemod_reset(gr4hip_iqdemod_t* h);
+/* d_ref / d_resp: n_in samples of T, n_in a multiple of chunk; writes n_in / chunk samples of T to each output (*n_out, may be NULL) */
+int gr4hip_iqdemod_process(gr4hip_iqdemod_t* h, const void* d_ref, const void* d_resp, size_t n_in, void* d_amp, void* d_phase, void* d_freq, size_t* n_out,
+                           gr4hip_stream_t stream);
+int gr4hip_iqdemod_destroy(gr4hip_iqdemod_t* h);
+
 #ifdef __cplusplus
 }
 #endif
