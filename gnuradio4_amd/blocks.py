@@ -468,13 +468,23 @@ class FirBatched(_Handle):
         check(lib().gr4hip_fir_batched_reset(self._h), "FirBatched.reset")
 
     def process_bulk(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        x = _dev(x, "FirBatched")
+        """x: [nchannels][n]; rows may lie apart (a view with unit inner stride is read in place, row stride = x.stride(0)).  out (optional): [nchannels][>= n] on the
+        same terms; the library wants it 16-byte aligned with a row stride that is a multiple of 4."""
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "FirBatched", "input must be a CUDA/HIP torch tensor (device-only path)")
         if x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != self.b.shape[0]:
             raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "FirBatched", "input must be float32 [nchannels][n]")
+        nch, n = x.shape
+        if n > 0 and not (x.stride(1) == 1 and (nch == 1 or x.stride(0) >= n)):  # rows that overlap, run backwards or are not unit-stride: a copy
+            x = x.contiguous()
         if out is None:
-            out = torch.empty((x.shape[0], (x.shape[1] + 3) // 4 * 4), dtype=torch.float32, device=x.device)
-        check(lib().gr4hip_fir_batched_process(self._h, x.data_ptr(), x.stride(0), x.shape[1], out.data_ptr(), out.stride(0), _stream()), "FirBatched.process")
-        return out[:, :x.shape[1]]
+            out = torch.empty((nch, (n + 3) // 4 * 4), dtype=torch.float32, device=x.device)
+        elif (not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != x.device or out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != nch
+              or out.shape[1] < n or (n > 0 and not (out.stride(1) == 1 and (nch == 1 or out.stride(0) >= n)))):
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "FirBatched", f"out must be a float32 tensor on the input's device, [{nch}][>= {n}] with unit inner stride and rows that do not overlap")
+        in_stride, out_stride = (x.stride(0), out.stride(0)) if nch > 1 else ((n + 3) // 4 * 4,) * 2  # (one row: no stride is ever applied, and torch reports any for a dimension of size 1)
+        check(lib().gr4hip_fir_batched_process(self._h, x.data_ptr(), in_stride, n, out.data_ptr(), out_stride, _stream()), "FirBatched.process")
+        return out[:, :n]
 
 
 def _uncertain_id(t: torch.Tensor, who: str) -> int:

@@ -480,6 +480,9 @@ bool fir_f16_make_afrag(const float* taps, size_t ntaps, int* KS_out, std::vecto
 int  fir_f16_launch(int KS, const float* x, long n, const float* hist, int Kh, const void* table, float* y, hipStream_t st, float* new_hist, long in_stride, long out_stride, unsigned nch, int delay, int accum, int guard,
                     unsigned char* flags, long flags_stride, float gthr);
 }
+// The batched handle.  Three kernel paths (gr4hip_fir_batched_process): the two-term f16 kernel (judges itself, marks per channel and segment), the three-term bf16 kernel
+// (judged behind its launch by fir_judge_kernel), both followed by fir_exact_kernel on the marks, and the f32 MFMA kernel above (unjudged: its sums measured half the
+// reference's float32 error under a rejected tone).
 struct gr4hip_fir_batched {
     size_t       nch = 0, ntaps = 0;
     int          KS = 0, Kp = 0;
@@ -489,7 +492,10 @@ struct gr4hip_fir_batched {
     int          bfKS = 0;
     DeviceBuffer d_hfrag; // > 32 taps: per-channel two-term f16 tables (fir_f16.hip) -- the default on long spans
     int          hfKS = 0;
-    DeviceBuffer d_tapsf, d_flags; // the taps as they are and one byte per channel and segment: what fir_exact_kernel evaluates again behind the f16 launch
+    DeviceBuffer d_tapsf, d_flags; // the taps as they are and one byte per channel and segment: what fir_exact_kernel evaluates again behind the main launch
+    DeviceBuffer d_gthr;           // per channel (sum b^2) / 128 (fir.hip, kGuardSegmentRatio): the threshold fir_judge_kernel holds the bf16 path's segments against
+    unsigned     last_paths = 0;   // which kernel served the last call and whether a second evaluation was enqueued (gr4hip_internal_fir_batched_last_paths)
+    size_t       last_nsegs = 0;   // segments per channel the last call left marks for in d_flags (0: none were made)
     bool         zero_hist = true; // the stream rule (common.hpp): create / reset note it, the next call zeroes d_hist[cur] on its own stream
 };
 
@@ -519,10 +525,20 @@ int gr4hip_fir_batched_create(gr4hip_fir_batched_t** out, size_t nchannels, cons
             rc = f->d_hfrag.ensure(hf.size() * sizeof(unsigned short));
             if (!rc) { hipError_t e = upload_fresh(f->d_hfrag.ptr, hf.data(), hf.size() * sizeof(unsigned short)); if (e != hipSuccess) { set_error("fir_batched: upload failed: %s", hipGetErrorString(e)); rc = GR4HIP_RUNTIME_ERROR; } }
         } else f->hfKS = 0;
-        if (!rc && f->hfKS) {
-            rc = f->d_tapsf.ensure(nchannels * ntaps * sizeof(float));
-            if (!rc) { hipError_t e = upload_fresh(f->d_tapsf.ptr, h_taps, nchannels * ntaps * sizeof(float)); if (e != hipSuccess) { set_error("fir_batched: upload failed: %s", hipGetErrorString(e)); rc = GR4HIP_RUNTIME_ERROR; } }
+    }
+    if (!rc && f->bfKS) { // the second evaluation behind the f16 and the bf16 kernel reads the taps as they are
+        rc = f->d_tapsf.ensure(nchannels * ntaps * sizeof(float));
+        if (!rc) { hipError_t e = upload_fresh(f->d_tapsf.ptr, h_taps, nchannels * ntaps * sizeof(float)); if (e != hipSuccess) { set_error("fir_batched: upload failed: %s", hipGetErrorString(e)); rc = GR4HIP_RUNTIME_ERROR; } }
+    }
+    if (!rc && f->bfKS) {
+        std::vector<float> g(nchannels);
+        for (size_t c = 0; c < nchannels; ++c) {
+            double h2 = 0;
+            for (size_t k = 0; k < ntaps; ++k) h2 += (double)h_taps[c * ntaps + k] * h_taps[c * ntaps + k];
+            g[c] = (float)(h2 / 128.0);
         }
+        rc = f->d_gthr.ensure(nchannels * sizeof(float));
+        if (!rc) { hipError_t e = upload_fresh(f->d_gthr.ptr, g.data(), nchannels * sizeof(float)); if (e != hipSuccess) { set_error("fir_batched: upload failed: %s", hipGetErrorString(e)); rc = GR4HIP_RUNTIME_ERROR; } }
     }
     for (int k = 0; k < 2 && !rc; ++k) rc = f->d_hist[k].ensure(nchannels * f->Kp * sizeof(float));
     if (!rc) rc = gr4hip_fir_batched_reset(f);
@@ -539,6 +555,8 @@ int gr4hip_fir_batched_reset(gr4hip_fir_batched_t* f) {
 
 int gr4hip_fir_batched_process(gr4hip_fir_batched_t* f, const float* d_in, size_t in_stride, size_t n, float* d_out, size_t out_stride, gr4hip_stream_t stream) {
     GR4_REQUIRE(f, "fir_batched_process: null handle");
+    f->last_paths = 0;
+    f->last_nsegs = 0;
     if (n == 0) return GR4HIP_OK;
     GR4_REQUIRE(d_in && d_out && in_stride >= n && out_stride >= n, "fir_batched_process: null pointer or stride shorter than n");
     GR4_REQUIRE(((uintptr_t)d_out % 16 == 0) && (out_stride % 4 == 0), "fir_batched_process: output must be 16-byte aligned with a stride multiple of 4");
@@ -548,17 +566,31 @@ int gr4hip_fir_batched_process(gr4hip_fir_batched_t* f, const float* d_in, size_
         f->zero_hist = false;
     }
     const float *hist = (const float*)f->d_hist[f->cur].ptr, *af = (const float*)f->d_afrag.ptr;
-    int rc;
+    const long nsegs = (long)ceil_div(n, (size_t)4096);
+    int        rc;
     if (f->hfKS && n >= 32768 && (uintptr_t)d_in % 16 == 0 && in_stride % 4 == 0 && !dev_switch(kDevFirNoBf16x3) && !dev_switch(kDevFirNoF16x2)) { // two-term f16 form (fir_f16.hip): same history layout
-        const long nsegs = (long)ceil_div(n, (size_t)4096);
         rc = f->d_flags.ensure((size_t)nsegs * f->nch);
         if (!rc) rc = fir_f16_launch(f->hfKS, d_in, (long)n, hist, f->Kp, f->d_hfrag.ptr, d_out, st, nullptr, (long)in_stride, (long)out_stride, (unsigned)f->nch, 0, 0, 1, (unsigned char*)f->d_flags.ptr, nsegs, 0.f);
         if (!rc) rc = fir_exact_launch(d_in, (long)n, hist, f->Kp, (const float*)f->d_tapsf.ptr, (int)f->ntaps, 1, 0, d_out, (long)n, (const unsigned char*)f->d_flags.ptr, 12, nullptr, st, (unsigned)f->nch,
                                        (long)in_stride, (long)out_stride, (long)f->ntaps, nsegs); // the marked segments again on the FP64 matrix pipe
-    } else if (f->bfKS && n >= 32768 && (uintptr_t)d_in % 16 == 0 && in_stride % 4 == 0 && !dev_switch(kDevFirNoBf16x3)) // three-term bf16 form (fir_bf16.hip): same history layout
+        f->last_paths = 1u << 1 | 1u;
+        f->last_nsegs = (size_t)nsegs;
+    } else if (f->bfKS && n >= 32768 && (uintptr_t)d_in % 16 == 0 && in_stride % 4 == 0 && !dev_switch(kDevFirNoBf16x3)) { // three-term bf16 form (fir_bf16.hip): same history layout
         rc = fir_bf16_launch(f->bfKS, d_in, (long)n, hist, f->Kp, f->d_bfrag.ptr, d_out, st, nullptr, (long)in_stride, (long)out_stride, (unsigned)f->nch, 0, 0);
-    else
+        f->last_paths = 1u << 2;
+        // This kernel does not judge itself, and under a rejected tone its sums measured 1.5 x the error of the reference's float32 sum (64 taps): the common tail of
+        // fir_process_core (fir.hip), per channel -- every segment's output power against its input power, the rejected ones again on the FP64 matrix pipe (the parity
+        // contract's second clause, include/gr4hip.h)
+        if (!rc) rc = f->d_flags.ensure((size_t)nsegs * f->nch);
+        if (!rc) rc = fir_judge_launch(d_in, (long)n, d_out, (long)n, 1, 0, 12, 0.f, (unsigned char*)f->d_flags.ptr, st, 0.f, (unsigned)f->nch, (long)in_stride, (long)out_stride, nsegs, (const float*)f->d_gthr.ptr);
+        if (!rc) rc = fir_exact_launch(d_in, (long)n, hist, f->Kp, (const float*)f->d_tapsf.ptr, (int)f->ntaps, 1, 0, d_out, (long)n, (const unsigned char*)f->d_flags.ptr, 12, nullptr, st, (unsigned)f->nch,
+                                       (long)in_stride, (long)out_stride, (long)f->ntaps, nsegs);
+        f->last_paths |= 1u;
+        f->last_nsegs = (size_t)nsegs;
+    } else { // f32 MFMA: float32 products summed four at a time -- measured 0.49 .. 0.53 x the reference's float32 error under a rejected tone (tests/test_gpu_fir_batched.py): no second evaluation
         rc = fir_mfma_launch(f->KS, d_in, (long)in_stride, hist, af, d_out, (long)out_stride, (long)n, (unsigned)f->nch, st, nullptr);
+        f->last_paths = 1u << 3;
+    }
     if (rc) return rc;
     hipLaunchKernelGGL(fir_batched_hist_kernel, dim3((unsigned)ceil_div(f->Kp, 64), (unsigned)f->nch), dim3(64), 0, st, d_in, (long)in_stride, hist,
                        (float*)f->d_hist[f->cur ^ 1].ptr, (long)n, f->Kp);
@@ -568,5 +600,28 @@ int gr4hip_fir_batched_process(gr4hip_fir_batched_t* f, const float* d_in, size_
 }
 
 int gr4hip_fir_batched_destroy(gr4hip_fir_batched_t* f) { delete f; return GR4HIP_OK; }
+
+// Test hooks, not ABI (declared in no header).  The kernel that served the last gr4hip_fir_batched_process call: bit 1 the two-term f16 form, bit 2 the three-term bf16
+// form, bit 3 the f32 MFMA form; bit 0: a second evaluation (fir_exact_kernel on the marked segments) was enqueued behind it.  0 after a call with n = 0.
+int gr4hip_internal_fir_batched_last_paths(const gr4hip_fir_batched_t* f, unsigned* mask) {
+    GR4_REQUIRE(f && mask, "fir_batched_last_paths: null argument");
+    *mask = f->last_paths;
+    return GR4HIP_OK;
+}
+
+// The last call's marks, [nch][nsegs] bytes (a segment = 4096 outputs; 1: sample spread beyond the block exponent, 2: a non-finite sample, 3: rejected by the guard), copied to
+// h_out once `stream` has drained.  nsegs = 0 when the call made none; GR4HIP_INVALID_ARGUMENT when cap < nch * nsegs (the sizes are still reported).
+int gr4hip_internal_fir_batched_last_flags(gr4hip_fir_batched_t* f, unsigned char* h_out, size_t cap, size_t* nch, size_t* nsegs, gr4hip_stream_t stream) {
+    GR4_REQUIRE(f && nch && nsegs, "fir_batched_last_flags: null argument");
+    *nch   = f->nch;
+    *nsegs = f->last_nsegs;
+    const size_t bytes = f->nch * f->last_nsegs;
+    if (bytes == 0) return GR4HIP_OK;
+    GR4_REQUIRE(h_out && cap >= bytes, "fir_batched_last_flags: room for %zu bytes needed", bytes);
+    hipStream_t st = as_stream(stream);
+    GR4_HIP_TRY(hipMemcpyAsync(h_out, f->d_flags.ptr, bytes, hipMemcpyDeviceToHost, st));
+    GR4_HIP_TRY(hipStreamSynchronize(st));
+    return GR4HIP_OK;
+}
 
 } // extern "C"

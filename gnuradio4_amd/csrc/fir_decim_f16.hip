@@ -209,7 +209,7 @@ __global__ __launch_bounds__(256, 2) void fir_decim_f16x2_kernel(const float* __
         const int slow = (e == 255 || px != px) ? 2 : ((mn != 0xffffffffu && e - el > kHfMaxRange) ? 1 : 0);
         if (slow == 0 && mx != 0u && (e < 127 - 60 || e > 127 + 60)) px = -1.f; // the powers are sums of SQUARES: with the largest sample outside [2^-60, 2^60] they leave float32's range (0 or Inf)
                                                                                    // and the guard cannot judge -- judge() hands such a segment to the second evaluation as if it were rejected
-        const int ec = e < 15 ? 15 : (e > 254 ? 254 : e);
+        const int ec = e < 25 ? 25 : (e > 254 ? 254 : e); // (25, not 15: the split multiplies by 2^11 s, which must stay finite -- an all-zero segment gave 0 x Inf)
         s     = __uint_as_float((unsigned)(268 - ec) << 23);
         inv_s = __uint_as_float((unsigned)(ec - 14) << 23);
         return slow;

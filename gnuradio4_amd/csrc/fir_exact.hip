@@ -234,8 +234,14 @@ int fir_exact_launch(const float* x, long n_in, const float* hist, int Kh, const
 // ---- the verdict for kernels that do not judge themselves (the float32 matrix-pipe forms, the three-term bf16 direct forms): one byte per 2^seg_shift outputs, non-zero where the
 // outputs' power (of the segment's quietest quarter) is below gthr x the power of the D x as many samples in front of them.  One pass over x and y; non-finite power either
 // side leaves the segment unmarked (the main kernel's classes stand).
-__global__ __launch_bounds__(256) void fir_judge_kernel(const float* __restrict__ x, long nxf, const float* __restrict__ y, long nyf, int D, int segf, float gthr, float gthr_all, unsigned char* __restrict__ flags, long nseg) {
+// Channel blockIdx.y of a batch: x + c in_stride, y + c out_stride, flags + c flags_stride, threshold gthr_ch[c] (null: gthr for every channel).
+__global__ __launch_bounds__(256) void fir_judge_kernel(const float* __restrict__ x0, long nxf, const float* __restrict__ y0, long nyf, int D, int segf, float gthr, float gthr_all, unsigned char* __restrict__ flags0, long nseg,
+                                                        long in_stride, long out_stride, long flags_stride, const float* __restrict__ gthr_ch) {
     __shared__ float red[8];
+    const float*   x     = x0 + (long)blockIdx.y * in_stride;
+    const float*   y     = y0 + (long)blockIdx.y * out_stride;
+    unsigned char* flags = flags0 + (long)blockIdx.y * flags_stride;
+    if (gthr_ch != nullptr) gthr = gthr_ch[blockIdx.y];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, q = segf / 4; // a wave's quarter: q output floats, q D input floats
     for (long sgi = blockIdx.x; sgi < nseg; sgi += gridDim.x) {
         const long y0 = sgi * segf + (long)wave * q, x0 = y0 * D;
@@ -262,11 +268,13 @@ __global__ __launch_bounds__(256) void fir_judge_kernel(const float* __restrict_
         }
     }
 }
-int fir_judge_launch(const float* x, long n_in, const float* y, long n_out, int D, int cplx, int seg_shift, float gthr, unsigned char* flags, hipStream_t st, float gthr_all) {
+int fir_judge_launch(const float* x, long n_in, const float* y, long n_out, int D, int cplx, int seg_shift, float gthr, unsigned char* flags, hipStream_t st, float gthr_all, unsigned nch, long in_stride,
+                     long out_stride, long flags_stride, const float* gthr_ch) {
     const int  NC = cplx ? 2 : 1, segf = NC << seg_shift;
     const long nseg = ceil_div(n_out, 1L << seg_shift);
     if (nseg <= 0) return GR4HIP_OK;
-    hipLaunchKernelGGL(fir_judge_kernel, dim3((unsigned)std::min<long>(nseg, 256 * 16)), dim3(256), 0, st, x, n_in * NC, y, n_out * NC, D, segf, gthr, gthr_all, flags, nseg);
+    hipLaunchKernelGGL(fir_judge_kernel, dim3((unsigned)std::min<long>(nseg, 256 * 16), nch), dim3(256), 0, st, x, n_in * NC, y, n_out * NC, D, segf, gthr, gthr_all, flags, nseg,
+                       in_stride, out_stride, flags_stride, gthr_ch);
     GR4_LAUNCH_CHECK();
     return GR4HIP_OK;
 }

@@ -14,6 +14,8 @@ int fir_exact_launch(const float* x, long n_in, const float* hist, int Kh, const
                      const EwiseHook* post = nullptr);
 // the verdict for a kernel that does not judge itself: flags[s] != 0 where the 2^seg_shift outputs of segment s carry less than gthr x the power of the samples in front of them
 // gthr_all > 0: a second verdict on the segment's WHOLE output power (the chain's kernel pair: chain.hip kChainPairGuardRatio)
-int fir_judge_launch(const float* x, long n_in, const float* y, long n_out, int D, int cplx, int seg_shift, float gthr, unsigned char* flags, hipStream_t st, float gthr_all = 0.f);
+// nch > 1: a batch -- channel c at x + c in_stride, y + c out_stride (floats), flags + c flags_stride, judged against gthr_ch[c] (device, optional: gthr otherwise)
+int fir_judge_launch(const float* x, long n_in, const float* y, long n_out, int D, int cplx, int seg_shift, float gthr, unsigned char* flags, hipStream_t st, float gthr_all = 0.f, unsigned nch = 1,
+                     long in_stride = 0, long out_stride = 0, long flags_stride = 0, const float* gthr_ch = nullptr);
 
 } // namespace gr4

@@ -521,7 +521,10 @@ int gr4hip_rotator64_destroy(gr4hip_rotator64_t* rot);
  * nchannels independent fir_filter<float> instances, per-channel taps h_taps[c][k], channel-major samples
  * d_in[c * in_stride + n]; evaluated as a block-Toeplitz contraction on the matrix pipe: more than 32 taps on spans of >= 32768 samples per channel with two-term
  * f16 splits under a per-segment block exponent (csrc/fir_f16.hip: three products per tap, every segment judged, see gr4hip_fir_set_algo above), otherwise with
- * float32 products on the f32 MFMA units. */
+ * float32 products on the f32 MFMA units.  d_in: in_stride >= n; d_out: 16-byte aligned, out_stride >= n and a multiple of 4; nothing outside the rows' [0, n) is
+ * read or written.  The guard per path: the f16 kernel judges each channel's segments itself, the three-term bf16 kernel that replaces it under
+ * GR4HIP_FIR_NO_F16X2 (or when a tap is not finite) is judged behind its launch, and the marked segments of either are evaluated again on the FP64 matrix pipe
+ * (csrc/fir_exact.hip); the f32 MFMA kernel's sums stay below the reference's own float32 error (measured 0.5 x under a rejected tone) and are not judged. */
 typedef struct gr4hip_fir_batched gr4hip_fir_batched_t;
 int gr4hip_fir_batched_create(gr4hip_fir_batched_t** fb, size_t nchannels, const float* h_taps, size_t ntaps);
 int gr4hip_fir_batched_reset(gr4hip_fir_batched_t* fb);

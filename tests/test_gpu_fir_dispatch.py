@@ -178,6 +178,23 @@ def test_fir_routing_table(G, devsw, cid, cplx, D, ntaps, algo, guard, switch, h
     assert y.shape == truth.shape and e <= TOL and not s.wrong_paths(), (cid, e, s.seen)
 
 
+@pytest.mark.parametrize("cplx,D,ntaps,n,path", [(False, 1, 200, 70_000, 6), (True, 1, 200, 40_000, 2), (False, 8, 1024, 1 << 17, 9)], ids=["p06_float200", "p02_cplx200", "p09_float_d8_1024"])
+def test_all_zero_segments_on_the_f16_kernels(G, cplx, D, ntaps, n, path):
+    """silence in mid stream: whole segments of zeros (the second half of one call, the first half of the next) on the kernels that scale every segment by a block
+    exponent.  With nothing to take the exponent from, the scale times the split's 2^11 left float32's range and 0 x Inf made every output of such a segment NaN
+    (found by tests/test_gpu_fir_batched.py's all-zero channel).  Zeros in, past the filter's memory, give exact zeros out."""
+    b = _taps(ntaps, D)
+    x = _signal(cplx, 2 * n, 60 + path)
+    x[n // 2:n // 2 + n] = 0
+    f = G.fir_filter(b, torch.complex64 if cplx else torch.float32, decimate=D)
+    s = _Stream(G, f, x, D)
+    s(n, (path,))
+    s(n, (path,))
+    _check_stream(s, b, x, D)
+    y = s.y()
+    assert np.isfinite(y).all() and not y[(n // 2 + ntaps) // D + 1:(n // 2 + n) // D].any()
+
+
 # ------------------------------------------------------------------ b. hand-off streams: each call changes one thing
 def _check_stream(s, b, x, D, tone=False):
     truth = _oracle(b, x[:s.pos], D)

@@ -104,6 +104,16 @@ def test_caller_supplied_output_tensors_are_checked(G):
         G.Merged(torch.float32, [("Add", 1.0)]).process_bulk(x, torch.empty(4095, dtype=torch.float32, device="cuda"))
     with pytest.raises(G.capi.Gr4HipError):
         G.FFT(256, "None").mag2(G.synth_c32(1024), torch.empty(1023, dtype=torch.float32, device="cuda"))
+    fb, xb = G.FirBatched(np.ones((2, 8), np.float32)), torch.zeros((2, 1000), dtype=torch.float32, device="cuda")
+    good = torch.empty((2, 1008), dtype=torch.float32, device="cuda")
+    assert fb.process_bulk(xb, good).data_ptr() == good.data_ptr()
+    assert fb.process_bulk(xb, torch.empty((2, 2016), dtype=torch.float32, device="cuda")[:, :1000]).shape == (2, 1000)  # a row-strided view with unit inner stride is legal
+    for bad in (torch.empty((2, 999), dtype=torch.float32, device="cuda"), torch.empty((3, 1000), dtype=torch.float32, device="cuda"), torch.empty(2000, dtype=torch.float32, device="cuda"),
+                torch.empty((2, 1000), dtype=torch.float32), torch.empty((2, 1000), dtype=torch.float64, device="cuda"), torch.empty((2, 2000), dtype=torch.float32, device="cuda")[:, ::2],
+                torch.empty((1000, 2), dtype=torch.float32, device="cuda").t()):
+        with pytest.raises(G.capi.Gr4HipError) as e:
+            fb.process_bulk(xb, bad)
+        assert e.value.status == G.capi.INVALID_ARGUMENT
 
 
 def test_native_library_is_loaded_and_shares_torch_runtime(G):
@@ -988,17 +998,35 @@ def test_batched_fir_mfma_parity(G, nch, ntaps):
     assert _rel(y0[0], t0) <= TOL
 
 
+def _batched_paths(G, f):
+    """bits of the batched dispatcher's path record (test hook of csrc/fir_batched.hip): 1 the f16 kernel, 2 the bf16 one, 3 the f32 MFMA one; 0: a second evaluation behind it"""
+    fn = G.capi.lib().gr4hip_internal_fir_batched_last_paths
+    fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_uint)]
+    m = C.c_uint(0xFFFFFFFF)
+    assert fn(f._h, C.byref(m)) == 0
+    return tuple(k for k in range(32) if m.value >> k & 1)
+
+
+@pytest.mark.parametrize("switch", [None, "GR4HIP_FIR_NO_F16X2"], ids=["f16", "bf16"])
 @pytest.mark.parametrize("nch,ntaps", [(5, 256), (3, 65), (2, 130), (4, 33), (3, 48), (2, 64)])
-def test_batched_fir_long_spans_take_the_bf16_three_term_kernel(G, nch, ntaps):
-    """configs[3] at spans of >= 32768 samples per channel and more than 32 taps: per-channel taps as three bf16 planes each (fir_bf16.hip), the channels in
-    grid.y; ragged ends, per-channel history handed between the bf16 kernel (long spans) and the f32 kernel (short ones)"""
+def test_batched_fir_long_spans_take_the_f16_or_the_bf16_kernel(G, devsw, nch, ntaps, switch):
+    """configs[3] at spans of >= 32768 samples per channel and more than 32 taps: per-channel taps as two f16 planes each (fir_f16.hip; the default) or, with
+    GR4HIP_FIR_NO_F16X2, as three bf16 planes (fir_bf16.hip), the channels in grid.y; ragged ends, per-channel history handed between that kernel (long spans) and
+    the f32 kernel (short ones).  Each call asserts the kernel that served it."""
     rng = np.random.default_rng(nch * 1000 + ntaps)
     b = (rng.standard_normal((nch, ntaps)) / np.sqrt(ntaps)).astype(np.float32)
     n = 90_000 + 36
     x = np.stack([O.signal_f32(142 + c, n) for c in range(nch)])
     f = G.FirBatched(b)
+    if switch:
+        devsw(switch)
+    long_path = (0, 2) if switch else (0, 1)
     cuts = [0, 40_004, 41_000, n]
-    y = np.concatenate([f.process_bulk(dev(np.ascontiguousarray(x[:, lo:hi]))).cpu().numpy() for lo, hi in zip(cuts[:-1], cuts[1:])], axis=1)
+    ys = []
+    for lo, hi, want in zip(cuts[:-1], cuts[1:], (long_path, (3,), long_path)):
+        ys.append(f.process_bulk(dev(np.ascontiguousarray(x[:, lo:hi]))).cpu().numpy())
+        assert _batched_paths(G, f) == want, (lo, hi)
+    y = np.concatenate(ys, axis=1)
     for c in range(nch):
         truth, _ = O.fir(b[c], x[c])
         assert _rel(y[c], truth) <= TOL, c
