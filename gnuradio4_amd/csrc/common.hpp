@@ -24,6 +24,7 @@ enum DevSwitch {
     kDevIirThreePass,         // GR4HIP_IIR_THREE_PASS
     kDevIirLookback,          // GR4HIP_IIR_LOOKBACK
     kDevIirNoSplit,           // GR4HIP_IIR_NO_SPLIT
+    kDevIirSeqSlots,          // GR4HIP_IIR_SEQ_SLOTS: an integer; non-zero: the segment-sequential kernel cuts a span into runs as if the chip had this many workgroup slots (0: 4 per CU)
     kDevFftBluesteinPipeline, // GR4HIP_FFT_BLUESTEIN_PIPELINE
     kDevFftNoPipeline,        // GR4HIP_FFT_NO_PIPELINE
     kDevRotatorLeap,          // GR4HIP_ROTATOR_LEAP

@@ -723,12 +723,11 @@ int gr4hip_iir64_create(gr4hip_iir64_t** out, int form, size_t nsections, const 
     f->d.nsec = (int)nsections;
     f->d.ord  = (int)ord;
     for (size_t c = 0; c < nsections; ++c) {
-        const double a0 = h_a[c * na];
-        if (a0 == 0.0) { delete f; set_error("iir64: a[0] = 0 in section %zu", c); return GR4HIP_INVALID_ARGUMENT; }
-        for (size_t k = 0; k <= ord; ++k) { // normalised by a[0] (FilterTool.hpp Section)
-            f->d.b[c][k] = k < nb ? h_b[c * nb + k] / a0 : 0.0;
-            f->d.a[c][k] = k < na ? h_a[c * na + k] / a0 : 0.0;
+        for (size_t k = 0; k <= ord; ++k) {
+            f->d.b[c][k] = k < nb ? h_b[c * nb + k] : 0.0;
+            f->d.a[c][k] = k < na ? h_a[c * na + k] : 0.0;
         }
+        f->d.a[c][0] = 1.0; // a[0] is taken as 1 whatever it holds, as detail::computeFilter does (FilterTool.hpp:116-158 never reads it) and as gr4hip_iir_create does
     }
     const int mp = f->mp = (int)(nsections * ord);
     // Phi_L: the zero-input state transition over L samples, column j = the state after L steps from the unit state e_j (host restatement of iir64_step)
@@ -803,6 +802,10 @@ int gr4hip_iir64_process(gr4hip_iir64_t* f, const double* d_in, size_t n, double
     GR4_REQUIRE(f, "iir64_process: null handle");
     if (n == 0) return GR4HIP_OK;
     GR4_REQUIRE(d_in && d_out, "iir64_process: null device pointer");
+    { // (as gr4hip_iir_process: the passes read the input through __restrict__ pointers while other workgroups write the output)
+        const uintptr_t xi = reinterpret_cast<uintptr_t>(d_in), yi = reinterpret_cast<uintptr_t>(d_out), bytes = n * sizeof(double);
+        GR4_REQUIRE(xi + bytes <= yi || yi + bytes <= xi, "iir64_process: the input and output ranges overlap (the cascade does not run in place)");
+    }
     hipStream_t st    = as_stream(stream);
     if (f->zero_state) { // a pending reset: onto this call's stream, in front of its launches
         for (auto& s : f->d_state) GR4_HIP_TRY(hipMemsetAsync(s.ptr, 0, kI64MP * sizeof(double), st));

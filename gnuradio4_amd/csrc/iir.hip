@@ -648,7 +648,7 @@ __global__ __launch_bounds__(kIirBS) void iir_onepass_kernel(IirOnePassArgs a, I
 // unknown; a stable filter forgets: after W samples an error in the start state has shrunk by ||Phi^W||.  The host picks the smallest warm-up of 1, 2 or 4
 // tiles with ||Phi_B^w||_inf <= 1e-8 (below float32 resolution of the state; the parity bar is 1e-5) and every run but the first starts w tiles early from
 // the zero state with stores and the second recurrence pass switched off (a warm-up tile costs the zero-state pass and the scan only).  Filters whose memory
-// does not fade within 4 tiles = 32768 samples (poles within ~6e-4 of the unit circle) keep the look-back kernel, and so do short spans.
+// does not fade within 4 tiles = 32768 samples (poles within ~6e-4 of the unit circle) keep the look-back kernel; every other span, a short one included, runs here.
 struct IirSeqArgs {
     const float* x;
     float*       y;
@@ -943,6 +943,9 @@ struct gr4hip_iir {
     bool                top = true;
     // the stream rule (common.hpp): create / reset / set_algo only note that the state is to be zeroed; iir_state_on() enqueues it on the stream of the next call
     bool                zero_state = true, zero_seq = true;
+    // what the last gr4hip_iir_process call enqueued for this handle (gr4hip_internal_iir_last_path): kernel (1 segment-sequential runs, 2 look-back single pass,
+    // 3 three-pass, 4 sequential float32; 0 nothing yet), ORD, padded NSEC, warm_tiles, warm_chunks, tiles_per_wg, grid, nt -- host-side stores only
+    int                 last_path[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     ~gr4hip_iir() {
         if (h_err) hip_quiet(hipHostFree(h_err));
         delete part[0];
@@ -986,6 +989,11 @@ static std::vector<double> mat_square(const std::vector<double>& A, int M) {
 
 static int iir_take_error(gr4hip_iir* f, const char* where);
 
+static void iir_note(gr4hip_iir* f, int kernel, int ord, int nsec, int warm_tiles, int warm_chunks, long tiles_per_wg, long grid, int nt) {
+    const int rec[8] = {kernel, ord, nsec, warm_tiles, warm_chunks, (int)tiles_per_wg, (int)grid, nt};
+    std::memcpy(f->last_path, rec, sizeof(rec));
+}
+
 template <int ORD, int NSEC>
 static int iir_run(gr4hip_iir* f, const float* x, float* y, long n, hipStream_t st) {
     constexpr int MP      = ORD * NSEC;
@@ -999,7 +1007,8 @@ static int iir_run(gr4hip_iir* f, const float* x, float* y, long n, hipStream_t 
             int              dev = -1, n_cu = per_device.current(&first, &dev);
             GR4_REQUIRE(n_cu != 0, "iir: cannot query the current device");
             if (first) { n_cu = -n_cu; per_device.done(dev, n_cu); }
-            const long slots = 4L * n_cu; // four resident workgroups per CU (LDS 38.7 KB, <= 128 VGPRs)
+            const int  dev_slots = dev_switch(kDevIirSeqSlots); // (developer switch: runs longer than their warm-up at a few dozen tiles, for the tests)
+            const long slots = dev_slots > 0 ? (long)dev_slots : 4L * n_cu; // four resident workgroups per CU (LDS 38.7 KB, <= 128 VGPRs)
             // runs as short as the warm-up itself when the span has fewer tiles than the chip has workgroup slots: half of such a run is warm-up, but every slot
             // works (measured, 4 biquads: 2^22 / 2^23 / 2^24 samples 207 / 278 / 358 Gsamples/s against 67 / 130 / 248 with runs of >= 8 warm-ups)
             long       per   = std::max<long>(f->warm_tiles, ceil_div(nblocks, slots));
@@ -1022,6 +1031,7 @@ static int iir_run(gr4hip_iir* f, const float* x, float* y, long n, hipStream_t 
             a.nt           = (size_t)n * 2 * sizeof(float) > ((size_t)192 << 20); // input + output beyond what the 256 MB memory-side cache would keep
             hipLaunchKernelGGL((iir_seq_kernel<ORD, NSEC>), dim3((unsigned)ceil_div(nblocks, per)), dim3(kIirBS), 0, st, a, cf);
             GR4_LAUNCH_CHECK();
+            iir_note(f, 1, ORD, NSEC, a.warm_tiles, a.warm_chunks, per, ceil_div(nblocks, per), a.nt);
             f->cur ^= 1;
             return GR4HIP_OK;
         }
@@ -1066,6 +1076,7 @@ static int iir_run(gr4hip_iir* f, const float* x, float* y, long n, hipStream_t 
 #endif
             hipLaunchKernelGGL((iir_onepass_kernel<ORD, NSEC>), dim3((unsigned)nblocks), dim3(kIirBS), 0, st, a, cf);
             GR4_LAUNCH_CHECK();
+            iir_note(f, 2, ORD, NSEC, 0, 0, 1, nblocks, 0);
 #ifdef GR4_IIR_TIMING
             {
                 std::vector<unsigned long long> h(16 * nblocks);
@@ -1099,6 +1110,7 @@ static int iir_run(gr4hip_iir* f, const float* x, float* y, long n, hipStream_t 
     hipLaunchKernelGGL((iir_pass_y<ORD, NSEC>), dim3((unsigned)nblocks), dim3(kIirBS), 0, st, x, y, n, coef, phi, (const float*)f->d_zc.ptr, (const float*)f->d_tb.ptr,
                        (float*)f->d_state[f->cur ^ 1].ptr);
     GR4_LAUNCH_CHECK();
+    iir_note(f, 3, ORD, NSEC, 0, 0, 1, nblocks, 0);
     f->cur ^= 1;
     return GR4HIP_OK;
 }
@@ -1290,6 +1302,8 @@ static int iir_selftest(gr4hip_iir* f) {
     if (!rc) rc = iir_process_parallel(f, static_cast<const float*>(dx.ptr), (size_t)n, static_cast<float*>(dy.ptr), nullptr);
     if (rc) return rc;
     GR4_HIP_TRY(hipMemcpy(y.data(), dy.ptr, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    for (gr4hip_iir* h : {f, f->part[0], f->part[1]}) // (the path record speaks of gr4hip_iir_process calls only)
+        if (h) h->last_path[0] = 0;
     f->top = false;
     rc     = gr4hip_iir_reset(f); // the stream starts from zero state
     f->top = true;
@@ -1383,13 +1397,32 @@ int gr4hip_iir_process(gr4hip_iir_t* f, const float* d_in, size_t n, float* d_ou
     GR4_REQUIRE(f, "iir_process: null handle");
     if (n == 0) return GR4HIP_OK;
     GR4_REQUIRE(d_in && d_out, "iir_process: null device pointer");
+    { // the kernels read the input through __restrict__ pointers, and a run of the segment-sequential kernel warms up on tiles that the run before it writes
+        const uintptr_t xi = reinterpret_cast<uintptr_t>(d_in), yi = reinterpret_cast<uintptr_t>(d_out), bytes = n * sizeof(float);
+        GR4_REQUIRE(xi + bytes <= yi || yi + bytes <= xi, "iir_process: the input and output ranges overlap (the cascade does not run in place)");
+    }
     if (const int rc = iir_state_on(f, as_stream(stream))) return rc; // a pending reset: onto this call's stream, in front of its launches
     if (f->top && f->algo_in_use == GR4HIP_IIR_SEQUENTIAL_F32) {
         hipLaunchKernelGGL(iir_sequential_kernel, dim3(1), dim3(64), 0, as_stream(stream), d_in, d_out, (long)n, f->seq, static_cast<float*>(f->d_seq_state.ptr));
         GR4_LAUNCH_CHECK();
+        iir_note(f, 4, std::max(f->seq.nb, f->seq.na) - 1, f->seq.nsec, 0, 0, 1, 1, 0);
         return GR4HIP_OK;
     }
+    f->last_path[0] = 0; // (a split handle's record is its parts'; a whole one writes its own below)
     return iir_process_parallel(f, d_in, n, d_out, stream);
+}
+
+// Test hook, not ABI (declared in no header): what the last gr4hip_iir_process call enqueued.  part 0 / 1: the halves of a split handle (a whole handle, and any
+// handle on GR4HIP_IIR_SEQUENTIAL_F32, has part 0 only) -> rec = {kernel, ORD, padded NSEC, warm_tiles, warm_chunks, tiles_per_wg, grid, nt}, kernel 1 = segment-
+// sequential runs, 2 = look-back single pass, 3 = three-pass, 4 = sequential float32.  part -1: rec[0] = 1 for a split handle, else 0.
+int gr4hip_internal_iir_last_path(const gr4hip_iir_t* f, int part, int* rec /*[8]*/) {
+    GR4_REQUIRE(f && rec && part >= -1 && part <= 1, "iir_last_path: bad argument");
+    if (part == -1) { std::memset(rec, 0, 8 * sizeof(int)); rec[0] = f->part[0] ? 1 : 0; return GR4HIP_OK; }
+    const gr4hip_iir* src = f;
+    if (f->part[0] && f->last_path[0] != 4) src = f->part[part];
+    else GR4_REQUIRE(part == 0, "iir_last_path: the handle has one part");
+    std::memcpy(rec, src->last_path, 8 * sizeof(int));
+    return GR4HIP_OK;
 }
 
 } // extern "C"

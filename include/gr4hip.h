@@ -119,7 +119,7 @@ const char* gr4hip_last_error(void); /* thread-local text of the last failure */
  * environment variable of the same name ONCE, when the library is first used, and can be changed afterwards with this call (atomic; process-wide).
  * Nothing here changes the meaning of a call -- choices that do (exact float32 FIR arithmetic, the rotator's phase recurrence, the chain's algorithm and
  * guard) are per-handle settings: gr4hip_fir_set_algo, gr4hip_rotator_set_algo, gr4hip_chain_create / gr4hip_chain_set_guard_mode.
- * Names: GR4HIP_FIR_NO_BF16X3, GR4HIP_FIR_NO_DECIM_FD, GR4HIP_IIR_THREE_PASS, GR4HIP_IIR_LOOKBACK, GR4HIP_IIR_NO_SPLIT, GR4HIP_FFT_BLUESTEIN_PIPELINE,
+ * Names: GR4HIP_FIR_NO_BF16X3, GR4HIP_FIR_NO_DECIM_FD, GR4HIP_IIR_THREE_PASS, GR4HIP_IIR_LOOKBACK, GR4HIP_IIR_NO_SPLIT, GR4HIP_IIR_SEQ_SLOTS (an integer), GR4HIP_FFT_BLUESTEIN_PIPELINE,
  * GR4HIP_FFT_NO_PIPELINE, GR4HIP_ROTATOR_LEAP, GR4HIP_ROTATOR_WALK, GR4HIP_CHAIN16, GR4HIP_FFT_SMOOTH_RUNTIME, GR4HIP_EWISE_NO_DIV_RCP. */
 int gr4hip_developer_switch(const char* name, int value);
 const char* gr4hip_status_string(int status);
@@ -244,7 +244,8 @@ int gr4hip_decimate(int dtype, const void* d_in, size_t n_in, size_t decim, void
 /* ------------------------------------------------------------------------------------------------ a3/a4
  * gr::filter::Filter<float>::processOne == cascade of sections through detail::computeFilter
  * (algorithm/.../filter/FilterTool.hpp:116-158, 244-246), and gr::filter::iir_filter<float, form>::processOne
- * (time_domain_filter.hpp:89-121) for nsections == 1.  b: [nsections][nb], a: [nsections][na], a[.][0] == 1.
+ * (time_domain_filter.hpp:89-121) for nsections == 1.  b: [nsections][nb], a: [nsections][na]; a[.][0] is taken as 1 whatever it holds (computeFilter never
+ * reads it: nothing is divided by it).  d_in[0 .. n) and d_out[0 .. n) must not overlap: the cascade does not run in place (GR4HIP_INVALID_ARGUMENT, nothing enqueued).
  * All four forms compute the same transfer function from zero state and are EVALUATED as direct form II (the parallel-in-time scan works on the DF-II
  * state); `form` is recorded for introspection only, so rounding can differ from the reference's DF_I / transposed forms in the last bits (the four forms
  * agree to 1e-5 upstream too, qa_filter.cpp:53-128).
@@ -492,7 +493,8 @@ int gr4hip_rotator_destroy(gr4hip_rotator_t* rot);
 /* ------------------------------------------------------------------------------------------------ float64 instantiations
  * The second registered type of the hot-path blocks: fir_filter<double> / iir_filter<double, form> (time_domain_filter.hpp:20, 57-60), FFT<double>
  * (fourier/fft.hpp:29: real double frames -> DataSet<double>) and Rotator<complex<double>> (Rotator.hpp:15).  Same semantics as the float32 entry points
- * above (history / state carried between calls, decimation = y[m D], all IIR forms evaluated as DF-II, FFT outputs of a real-input block: magnitude and
+ * above (history / state carried between calls, decimation = y[m D], all IIR forms evaluated as DF-II, an IIR section's a[0] taken as 1 whatever it holds -- not
+ * divided by, as in gr4hip_iir_create -- and gr4hip_iir64_process refusing overlapping input and output ranges like gr4hip_iir_process, FFT outputs of a real-input block: magnitude and
  * phase of bins 0 .. N/2-1, Re / Im of bins N/2 .. N-1), plain FP64 kernels.  Envelope: FIR <= 2048 taps, decim <= 32; IIR <= 8 state values (4 biquads,
  * or one section of order <= 8); FFT powers of two 2 .. 8192; anything else returns GR4HIP_UNSUPPORTED from create (the caller keeps its CPU path). */
 typedef struct gr4hip_fir64 gr4hip_fir64_t;

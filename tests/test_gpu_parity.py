@@ -1129,24 +1129,47 @@ def test_iir_status_is_clean_after_long_streams(G):
     f.reset()
 
 
-def test_iir_long_stream_crosses_block_scan_groups(G):
-    """2^24 + 2^22 + 5 samples: more than one 2048-block group of the block-level scan, odd tail; against the float64 oracle"""
+def _iir_record(G, f, part=0):
+    """what the last gr4hip_iir_process call enqueued for (a part of) the handle: (kernel, ORD, padded NSEC, warm_tiles, warm_chunks, tiles_per_wg, grid, nt), kernel
+    1 = segment-sequential runs, 2 = look-back single pass, 3 = three-pass, 4 = sequential float32 (the library's test hook; tests/test_gpu_iir_paths.py)"""
+    fn = G.capi.lib().gr4hip_internal_iir_last_path
+    fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    rec = (C.c_int * 8)()
+    assert fn(f._h, part, rec) == 0
+    return tuple(rec)
+
+
+@pytest.mark.parametrize("mode", ["runs", "three_pass"])
+def test_iir_long_stream_crosses_block_scan_groups(G, mode, devsw):
+    """2^24 + 2^22 + 5 samples = 2561 blocks, odd tail, against the float64 oracle.  "three_pass" (GR4HIP_IIR_THREE_PASS): more than one 2048-block group of the
+    block-level scan iir_pass_b; "runs": what such a span takes by default, the segment-sequential kernel with runs of several tiles per workgroup"""
     import gnuradio4_amd.blocks as B
     b, a = B.design_iir(0, 8, 0.05, float("nan"), 1.0, 0)  # Butterworth order 8 -> 4 biquads (BASELINE configs[2])
     n = (1 << 24) + (1 << 22) + 5
     x = O.signal_f32(7, n)
     truth = O.iir_cascade(O.make_sections([(bb, aa) for bb, aa in zip(b, a)]), x, O.DF_II, f64=True)
-    y = G.iir_filter(b, a).process_bulk(dev(x)).cpu().numpy()
+    if mode == "three_pass":
+        devsw("GR4HIP_IIR_THREE_PASS", 1)
+    blocks = -(-n // 8192)
+    f = G.iir_filter(b, a)
+    y = f.process_bulk(dev(x)).cpu().numpy()
+    rec = _iir_record(G, f)
+    if mode == "three_pass":
+        assert rec == (3, 2, 4, 0, 0, 1, blocks, 0) and blocks > 2048
+    else:
+        assert rec[:3] == (1, 2, 4) and rec[3] >= 1 and rec[5] == max(rec[3], -(-blocks // (4 * torch.cuda.get_device_properties(0).multi_processor_count))) and rec[6] == -(-blocks // rec[5])
     assert _rel(y, truth) <= TOL
     f2 = G.iir_filter(b, a)  # the same stream in two calls: state carried across
     y2 = np.concatenate([f2.process_bulk(dev(x[:n // 3])).cpu().numpy(), f2.process_bulk(dev(x[n // 3:])).cpu().numpy()])
+    assert _iir_record(G, f2)[0] == rec[0]
     assert _rel(y2, truth) <= TOL
 
 
 @pytest.mark.parametrize("kind", ["biquad4", "pole1", "order4"])
 def test_iir_single_pass_equals_three_pass(G, kind, devsw):
-    """the single-pass kernel (decoupled look-back over block states) and the three-pass kernels are two evaluations of the same scan: they must agree
-    far inside the parity tolerance on a span long enough for multi-window look-backs (> 64 blocks of 8192 samples), ragged, in two calls"""
+    """the single-pass kernel (decoupled look-back over block states, "one": GR4HIP_IIR_LOOKBACK -- all three filters fade fast and would take the segment-
+    sequential runs otherwise), the three-pass kernels and the default route ("runs") are three evaluations of the same scan: they must agree far inside the parity
+    tolerance on a span long enough for multi-window look-backs (> 64 blocks of 8192 samples), ragged, in two calls"""
     n = (1 << 21) + 12345
     x = G.synth_f32(n, seed=21)
     if kind == "biquad4":
@@ -1156,24 +1179,29 @@ def test_iir_single_pass_equals_three_pass(G, kind, devsw):
     else:
         b, a = np.array([[0.1, 0.2, 0.3, 0.2, 0.1]], np.float32), np.array([[1.0, -0.9, 0.5, -0.1, 0.02]], np.float32)
     out = {}
-    for mode in ("one", "three"):
-        if mode == "three":
-            devsw("GR4HIP_IIR_THREE_PASS", 1)
+    inst = {"biquad4": (2, 4), "pole1": (2, 2), "order4": (4, 1)}[kind]
+    for mode in ("runs", "one", "three"):
+        devsw("GR4HIP_IIR_LOOKBACK", int(mode == "one"))
+        devsw("GR4HIP_IIR_THREE_PASS", int(mode == "three"))
         f = G.iir_filter(b, a)
         y = torch.empty_like(x)
         cut = 700001
-        f.process_bulk(x[:cut], y[:cut])
-        f.process_bulk(x[cut:], y[cut:])
+        for lo, hi in ((0, cut), (cut, n)):
+            f.process_bulk(x[lo:hi], y[lo:hi])
+            rec = _iir_record(G, f)
+            assert rec[:3] == ({"runs": 1, "one": 2, "three": 3}[mode],) + inst, (mode, rec)
+            assert mode == "runs" or rec[3:] == (0, 0, 1, -(-(hi - lo) // 8192), 0), (mode, rec)
         out[mode] = y.double()
     rms = float(out["three"].pow(2).mean().sqrt())
     assert float((out["one"] - out["three"]).abs().max()) <= 2e-5 * rms
+    assert float((out["runs"] - out["three"]).abs().max()) <= 2e-5 * rms
 
 
 @pytest.mark.parametrize("pole", [0.7, 0.998, 0.999, 0.99999])
 def test_iir_segment_sequential_runs_match_the_lookback_and_the_oracle(G, pole, devsw):
-    """spans of >= 16 tiles take the segment-sequential kernel when the filter's memory fades inside 1, 2 or 4 tiles (poles 0.7 / 0.998 / 0.999 here;
-    0.99999 does not and stays on the look-back): same answers as the look-back kernel and the float64 oracle, in two calls so that run 0 of the second
-    call starts from the carried state and not from a warm-up"""
+    """every span takes the segment-sequential kernel when the filter's memory fades inside 1, 2 or 4 tiles (poles 0.7 / 0.998 / 0.999 here, asserted from
+    the path record; 0.99999 does not and stays on the look-back): same answers as the look-back kernel and the float64 oracle, in two calls so that run 0 of
+    the second call starts from the carried state and not from a warm-up"""
     n = (1 << 22) + (1 << 20) + 4321
     x = O.signal_f32(31, n)
     b, a = np.array([[1.0 - pole, 0.0, 0.0], [0.2, 0.3, 0.2]], np.float32), np.array([[1.0, -pole, 0.0], [1.0, -0.4, 0.2]], np.float32)
@@ -1183,8 +1211,17 @@ def test_iir_segment_sequential_runs_match_the_lookback_and_the_oracle(G, pole, 
         if mode == "lookback":
             devsw("GR4HIP_IIR_LOOKBACK", 1)
         f = G.iir_filter(b, a)
-        cut = (1 << 21) + 777  # both calls are hundreds of tiles: runs of several tiles behind a warm-up
-        out[mode] = np.concatenate([f.process_bulk(dev(x[:cut])).cpu().numpy(), f.process_bulk(dev(x[cut:])).cpu().numpy()])
+        cut = (1 << 21) + 777  # both calls are hundreds of tiles: each run as long as its warm-up (more tiles per run: tests/test_gpu_iir_paths.py)
+        ys = []
+        for lo, hi in ((0, cut), (cut, n)):
+            ys.append(f.process_bulk(dev(x[lo:hi])).cpu().numpy())
+            rec = _iir_record(G, f)
+            warm = {0.7: 1, 0.998: 2, 0.999: 4, 0.99999: 0}[pole]
+            if mode == "runs" and warm:
+                assert rec[:4] == (1, 2, 2, warm) and rec[4] == (32 if pole == 0.7 else 256) and rec[6] == -(-(-(-(hi - lo) // 8192)) // rec[5]), (pole, rec)
+            else:
+                assert rec == (2, 2, 2, 0, 0, 1, -(-(hi - lo) // 8192), 0), (pole, mode, rec)
+        out[mode] = np.concatenate(ys)
         f.status()
         assert _rel(out[mode], truth) <= TOL, mode
     rms = float(np.sqrt(np.mean(truth ** 2)))
@@ -3060,6 +3097,72 @@ def test_iir_filter_float64(G, kind):
     with pytest.raises(G.capi.Gr4HipError) as e:
         G.iir_filter(np.ones((5, 3)), np.ones((5, 3)), dtype=torch.float64)  # 10 state values
     assert e.value.status == G.capi.UNSUPPORTED
+
+
+_IIR64_CASES = [(1, 1), (2, 1), (3, 1), (4, 1), (5, 1), (6, 1), (7, 1), (8, 1), (1, 2), (2, 2), (3, 2), (4, 2), (1, 3), (2, 3), (1, 4), (2, 4), (1, 5), (1, 6), (1, 7), (1, 8)]
+
+
+@pytest.mark.parametrize("nsec,order", _IIR64_CASES, ids=[f"{s}x{o}" for s, o in _IIR64_CASES])
+def test_iir_filter_float64_every_instantiation(G, nsec, order):
+    """every (sections, order) pair of gr4hip_iir64_process's dispatch (GR4_IIR64_CASE, csrc/f64.hip): stable random sections (pole radii <= 0.95), spans of 1, 15, 16,
+    17 and 33 tiles plus a ragged tail -- the 16-tile groups of iir64_pass_b --, each in two calls on one handle; against scipy's lfilter section by section.
+    A direct-form section of order N loses about eps x kappa in ANY float64 evaluation, lfilter's included, with kappa = ||1 / A||_1 ||a||_1 (the gain from a rounding
+    error of the recurrence to its state, times the size of the terms that are rounded): a draw with kappa > 100 (clustered poles: one of order 6 came out at 3900, and
+    lfilter itself at 1.5e-13 from a long-double evaluation where the others stay at 1e-15) is drawn again, so that eps x kappa stays 40 times inside TOL64"""
+    import scipy.signal as sps
+    rng = np.random.default_rng(100 * nsec + order)
+    b, a = [], []
+    impulse = np.zeros(4000)
+    impulse[0] = 1.0
+    for _ in range(nsec):
+        while True:
+            poles = []
+            while len(poles) < order:
+                if order - len(poles) >= 2:
+                    r, th = rng.uniform(0.3, 0.95), rng.uniform(0.1, 3.0)
+                    poles += [r * np.exp(1j * th), r * np.exp(-1j * th)]
+                else:
+                    poles += [rng.uniform(-0.95, 0.95)]
+            aa, bb = np.real(np.poly(poles)), rng.uniform(-1, 1, order + 1) * 0.5
+            if np.sum(np.abs(sps.lfilter([1.0], aa, impulse))) * np.sum(np.abs(aa)) <= 100.0:
+                break
+        a.append(aa)
+        b.append(bb)
+    b, a = np.array(b), np.array(a)
+    tile, tail = 8192, 1234
+    n = 2 * (33 * tile + tail)
+    x = rng.standard_normal(n)
+    truth = x.copy()
+    for bb, aa in zip(b, a):
+        truth = sps.lfilter(bb, aa, truth)
+    for tiles in (1, 15, 16, 17, 33):
+        m = (tiles - 1) * tile + tail  # `tiles` tiles, the last one ragged
+        f = G.iir_filter(b, a, dtype=torch.float64)
+        y = np.concatenate([f.process_bulk(dev(x[:m])).cpu().numpy(), f.process_bulk(dev(x[m:2 * m])).cpu().numpy()])
+        assert y.dtype == np.float64 and _rel(y, truth[:2 * m]) <= TOL64, (tiles, _rel(y, truth[:2 * m]))
+
+
+def test_iir_a0_is_taken_as_one(G):
+    """a section with a[0] = 2: the reference's computeFilter never reads a[0] (FilterTool.hpp:116-158), nor does the oracle (oracle/gr4_oracle.h: "a[0] assumed 1") --
+    nothing is divided by it, on the float32 handle and on the float64 one alike"""
+    b, a = np.array([[0.2, 0.3, 0.2], [0.5, -0.1, 0.3]]), np.array([[2.0, -0.9, 0.5], [2.0, 0.3, 0.2]])
+    x = O.signal_f32(5, 3 * 8192 + 77)
+    a1 = a.copy()
+    a1[:, 0] = 1.0
+    truth = O.iir_cascade(O.make_sections([(bb, aa) for bb, aa in zip(b.astype(np.float32), a.astype(np.float32))]), x, O.DF_II, f64=True)
+    same = O.iir_cascade(O.make_sections([(bb, aa) for bb, aa in zip(b.astype(np.float32), a1.astype(np.float32))]), x, O.DF_II, f64=True)
+    assert np.array_equal(truth, same)  # (the oracle's reading)
+    cut = 8192 + 5
+    f32 = G.iir_filter(b, a)
+    y32 = np.concatenate([f32.process_bulk(dev(x[:cut])).cpu().numpy(), f32.process_bulk(dev(x[cut:])).cpu().numpy()])
+    assert _rel(y32, truth) <= TOL
+    fs = G.iir_filter(b, a)
+    fs.set_algo(G.capi.IIR_SEQUENTIAL_F32)
+    assert _rel(fs.process_bulk(dev(x)).cpu().numpy(), truth) <= TOL
+    f64 = G.iir_filter(b.astype(np.float32).astype(np.float64), a.astype(np.float32).astype(np.float64), dtype=torch.float64)
+    x64 = x.astype(np.float64)
+    y64 = np.concatenate([f64.process_bulk(dev(x64[:cut])).cpu().numpy(), f64.process_bulk(dev(x64[cut:])).cpu().numpy()])
+    assert _rel(y64, truth) <= TOL64
 
 
 @pytest.mark.parametrize("kind", ["biquad4", "narrow"])
