@@ -810,6 +810,83 @@ class IQDemodulator(_Handle):
         return tuple(o[:n_out] for o in outs)
 
 
+class PowerMetrics(_Handle):
+    """gr::electrical::PowerMetrics<float32, nPhases> (PowerEstimators.hpp:21-131) with the reference's setting names.  process_bulk(u, i) takes two
+    [n_phases, n] float32 tensors, n a multiple of `decimate` (a 1-D tensor is one phase; rows may be strided views, read in place), and returns
+    (P, Q, S, U_rms, I_rms), each [n_phases, n / decimate] (include/gr4hip.h "Power metrics").  set_params always re-initialises the filters
+    (settingsChanged, :95), reset() zeroes their states."""
+    _destroy = "gr4hip_powermetrics_destroy"
+    _names = ("sample_rate", "high_pass", "low_pass", "decimate")
+
+    def __init__(self, n_phases: int = 1, **settings):
+        super().__init__()
+        p = capi.PowerMetricsParams()
+        check(lib().gr4hip_powermetrics_params_default(C.byref(p)), "PowerMetrics")
+        p.n_phases = int(n_phases)
+        self._p = self._params(p, settings)
+        check(lib().gr4hip_powermetrics_create(C.byref(self._h), C.byref(self._p)), "PowerMetrics")
+
+    @staticmethod
+    def segment() -> int:
+        """samples per workgroup segment: where the kernels hand their carries over"""
+        return int(lib().gr4hip_powermetrics_segment())
+
+    def _params(self, p, settings):
+        for k, v in settings.items():
+            if k not in self._names:
+                raise TypeError(f"PowerMetrics: unknown setting '{k}'")
+            setattr(p, k, int(v) if k == "decimate" else v)
+        return p
+
+    @property
+    def n_phases(self) -> int:
+        return int(self._p.n_phases)
+
+    def __getattr__(self, name):
+        if name in type(self)._names:
+            return getattr(self.__dict__["_p"], name)
+        raise AttributeError(name)
+
+    def set_params(self, **settings):
+        """settingsChanged: every filter is rebuilt, whatever the update names"""
+        p = self._params(capi.PowerMetricsParams.from_buffer_copy(self._p), settings)
+        check(lib().gr4hip_powermetrics_set_params(self._h, C.byref(p)), "PowerMetrics.set_params")
+        self._p = p
+
+    def reset(self):
+        check(lib().gr4hip_powermetrics_reset(self._h), "PowerMetrics.reset")
+
+    def _rows(self, x):
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "PowerMetrics", "input must be a CUDA/HIP torch tensor (device-only path)")
+        if x.dim() == 1:
+            x = x.unsqueeze(0)
+        if x.dim() != 2 or x.dtype != torch.float32 or x.shape[0] != self.n_phases:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "PowerMetrics", f"inputs must be float32 tensors of shape [{self.n_phases}, n]")
+        if x.shape[1] > 1 and x.stride(1) != 1 or x.shape[0] > 1 and x.stride(0) < x.shape[1]:
+            x = x.contiguous()  # only rows of unit stride, a row stride apart, are read in place
+        return x
+
+    def process_bulk(self, u: torch.Tensor, i: torch.Tensor, outputs=("P", "Q", "S", "U_rms", "I_rms")):
+        """`outputs`: the ones to compute; the others come back as None (their pointers are NULL in the call)"""
+        u, i = self._rows(u), self._rows(i)
+        if u.shape != i.shape or u.device != i.device:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "PowerMetrics", "u and i must have one shape on one device")
+        n = u.shape[1]
+        stride = u.stride(0) if self.n_phases > 1 else max(n, 1)
+        if self.n_phases > 1 and i.stride(0) != stride:
+            i = i.contiguous()
+            if i.stride(0) != stride:
+                u = u.contiguous()
+                stride = n
+        n_out = n // int(self._p.decimate)
+        outs = [torch.empty((self.n_phases, n_out), dtype=torch.float32, device=u.device) if k in outputs else None for k in ("P", "Q", "S", "U_rms", "I_rms")]
+        ptr = [o.data_ptr() if o is not None else None for o in outs]
+        check(lib().gr4hip_powermetrics_process(self._h, u.data_ptr(), i.data_ptr(), stride, n, ptr[0], ptr[1], ptr[2], ptr[3], ptr[4], max(n_out, 1), None,
+                                                _stream()), "PowerMetrics.process")
+        return tuple(outs)
+
+
 def synth_c32(n: int, seed: int = 42, tone_frel: float = 0.1, tone_amp: float = 1.0, noise_amp: float = 1.0, device="cuda") -> torch.Tensor:
     out = torch.empty(n, dtype=torch.complex64, device=device)
     check(lib().gr4hip_synth_c32(out.data_ptr(), n, seed, tone_frel, tone_amp, noise_amp, _stream()), "synth_c32")

@@ -175,6 +175,14 @@ SIGNATURES = {
     "gr4hip_iqdemod_reset": (_i, [_vp]),
     "gr4hip_iqdemod_process": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _psz, _vp]),
     "gr4hip_iqdemod_destroy": (_i, [_vp]),
+    "gr4hip_powermetrics_params_default": (_i, [_vp]),
+    "gr4hip_powermetrics_check": (_i, [_vp]),
+    "gr4hip_powermetrics_segment": (_sz, []),
+    "gr4hip_powermetrics_create": (_i, [_pvp, _vp]),
+    "gr4hip_powermetrics_set_params": (_i, [_vp, _vp]),
+    "gr4hip_powermetrics_reset": (_i, [_vp]),
+    "gr4hip_powermetrics_process": (_i, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _psz, _vp]),
+    "gr4hip_powermetrics_destroy": (_i, [_vp]),
 }
 
 class FilterParams(C.Structure):
@@ -195,6 +203,11 @@ class IQDemodParams(C.Structure):
     """gr4hip_iqdemod_params: the settings of IQDemodulator<T> (FrequencyEstimator.hpp:423-429) plus the chunk"""
     _fields_ = [("sample_rate", _f), ("f_high_pass", _f), ("f_low_pass", _f), ("phase_unit", _i), ("invert_phase", _i), ("derivative_method", _i),
                 ("epsilon", _d), ("chunk", C.c_size_t)]
+
+
+class PowerMetricsParams(C.Structure):
+    """gr4hip_powermetrics_params: the settings of PowerMetrics<float, nPhases> (PowerEstimators.hpp:46-49) plus the number of phases"""
+    _fields_ = [("sample_rate", _f), ("high_pass", _f), ("low_pass", _f), ("decimate", C.c_size_t), ("n_phases", C.c_size_t)]
 
 
 LOWPASS, HIGHPASS, BANDPASS, BANDSTOP = range(4)

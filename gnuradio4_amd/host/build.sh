@@ -28,5 +28,6 @@ if stale $OUT/dump_signal_generator tests/dump_signal_generator.cpp; then $CXX -
 if stale $OUT/test_host_plugin tests/test_host_plugin.cpp; then $CXX -O2 tests/test_host_plugin.cpp -o $OUT/test_host_plugin -ldl & pids+=($!); fi
 if stale $OUT/test_host_freq_est tests/test_host_freq_est.cpp; then $CXX -O2 tests/test_host_freq_est.cpp -o $OUT/test_host_freq_est -ldl & pids+=($!); fi
 if stale $OUT/test_host_iq_demod tests/test_host_iq_demod.cpp; then $CXX -O2 tests/test_host_iq_demod.cpp -o $OUT/test_host_iq_demod -ldl & pids+=($!); fi
+if stale $OUT/test_host_power_metrics tests/test_host_power_metrics.cpp; then $CXX -O2 tests/test_host_power_metrics.cpp -o $OUT/test_host_power_metrics -ldl & pids+=($!); fi
 for p in "${pids[@]}"; do wait $p; done
 echo "built $(realpath $OUT)"

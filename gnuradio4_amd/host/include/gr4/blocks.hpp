@@ -484,6 +484,47 @@ using IQDemodulatorDecimating = IQDemodulator<T, Resampling<1024U, 1U, false>>;
 template <typename T, DerivativeMethod M>
 using IQDemodulatorFixed = IQDemodulator<T, Resampling<1024U, 1U, false>, Derivative<M, true>>;
 } // namespace gr::filter
+namespace gr::electrical {
+GR_REGISTER_BLOCK("gr::electrical::ThreePhasePowerMetrics", gr::electrical::PowerMetrics, ([T], 3UZ), [ float ])
+GR_REGISTER_BLOCK("gr::electrical::SinglePhasePowerMetrics", gr::electrical::PowerMetrics, ([T], 1UZ), [ float ])
+// PowerMetrics<T, nPhases> (blocks/electrical/.../PowerEstimators.hpp:21-131): per phase a voltage and a current input; active, reactive and apparent power and
+// the two RMS values, one output per chunk of `decimate` inputs.  Members, names and the reflected set are the reference's (:36-51: high_pass and low_pass are
+// public but not reflected).  Device-only: computed behind compute_domain gpu:hip (gr4hip_powermetrics_*, gr4/hip.hpp); off the device the work loop refuses
+// loudly (deviceOnly: work::Status::ERROR).  Every settings update rebuilds the filters (:95) and sets input_chunk_size = decimate (:79-81).
+template <typename T, std::size_t nPhases>
+    requires std::floating_point<T>
+struct PowerMetrics : Block<PowerMetrics<T, nPhases>, Resampling<100U, 1U, false>> {
+    using TParent = Block<PowerMetrics<T, nPhases>, Resampling<100U, 1U, false>>;
+    std::vector<PortIn<T>>  U{nPhases};
+    std::vector<PortIn<T>>  I{nPhases};
+    std::vector<PortOut<T>> P{nPhases};     // active power (in-phase)
+    std::vector<PortOut<T>> Q{nPhases};     // reactive power
+    std::vector<PortOut<T>> S{nPhases};     // apparent power
+    std::vector<PortOut<T>> U_rms{nPhases};
+    std::vector<PortOut<T>> I_rms{nPhases};
+    float      sample_rate = 10000.f, high_pass = 2.f, low_pass = 90.f; // (:46-48)
+    gr::Size_t decimate    = 100U;                                      // (:49)
+    gr::Size_t _decimate_in_force = 100U; // the last accepted value: a refused update leaves the block as it was
+    GR_MAKE_REFLECTABLE(PowerMetrics, U, I, P, Q, S, U_rms, I_rms, sample_rate, decimate);
+    void settingsChanged(const property_map&, const property_map&) {
+        if (decimate == 0U) {
+            decimate = _decimate_in_force;
+            throw std::invalid_argument("decimate must be at least 1");
+        }
+        _decimate_in_force     = decimate;
+        this->input_chunk_size = decimate; // initFilters (:79-81); the device handle rebuilds its filters on the new settings generation
+    }
+    work::Status deviceOnly() { // (the graph ends with ERROR: no numbers come out of the host path)
+        std::fprintf(stderr, "PowerMetrics: device-only block, needs compute_domain gpu:hip\n");
+        this->_log("PowerMetrics: device-only block, needs compute_domain gpu:hip");
+        return work::Status::ERROR;
+    }
+};
+template <typename T>
+using ThreePhasePowerMetrics = PowerMetrics<T, 3U>;
+template <typename T>
+using SinglePhasePowerMetrics = PowerMetrics<T, 1U>;
+} // namespace gr::electrical
 namespace gr::algorithm::window {
 enum class Type : int { None, Rectangular, Hamming, Hann, HannExp, Blackman, Nuttall, BlackmanHarris, BlackmanNuttall, FlatTop, Exponential, Kaiser }; // window.hpp:35 == GR4HIP_WIN_*
 inline constexpr std::array<std::string_view, 12> TypeList{"None", "Rectangular", "Hamming", "Hann", "HannExp", "Blackman", "Nuttall", "BlackmanHarris", "BlackmanNuttall", "FlatTop", "Exponential", "Kaiser"};

@@ -946,15 +946,41 @@ private:
             }
             return {requested, 0, work::Status::INSUFFICIENT_OUTPUT_ITEMS};
         }
-        const std::size_t nIn = k * ic, nOut = k * oc;
+        std::size_t nIn = k * ic, nOut = k * oc;
         // the chunk's tag: normally the one on its first sample; every tag of the chunk when it had to span some.  Settings-by-tag first
         // (Block.hpp:1979-1985), then the chunk is processed with the new settings
         property_map chunkTags;
-        each_in([&](auto& p) {
-            if (!p.connected()) return;
-            for (auto& kv : p.buffer->mergedTags(nIn)) chunkTags.insert_or_assign(kv.first, std::move(kv.second)); // identical tags on several inputs collapse
-        });
+        const auto   collectTags = [&](std::size_t n) {
+            chunkTags.clear();
+            each_in([&](auto& p) {
+                if (!p.connected()) return;
+                for (auto& kv : p.buffer->mergedTags(n)) chunkTags.insert_or_assign(kv.first, std::move(kv.second)); // identical tags on several inputs collapse
+            });
+        };
+        collectTags(nIn);
         if (!chunkTags.empty()) applyTagSettings(chunkTags);
+        // settings-by-tag may have changed the chunk itself (PowerMetrics: input_chunk_size = decimate): the samples from the tag on are chunked by the new
+        // sizes, within what was sized above (the next tag still starts a chunk).  A new chunk larger than that is one forced chunk: it may span later tags,
+        // which are then collected and applied with it like those of any forced chunk (and may change the chunk once more: nIn only grows, so this ends).
+        // A chunk that has to wait for more input returns with the settings applied; the tag is still in the buffer, and the next call finds its values
+        // equal to the active ones, which applyTagSettings does not count as a change.
+        for (std::size_t icNow = ic, ocNow = oc;;) {
+            const std::size_t ic2 = std::max<std::size_t>(1, input_chunk_size), oc2 = std::max<std::size_t>(1, output_chunk_size);
+            if (ic2 == icNow && oc2 == ocNow) break;
+            std::size_t have = std::numeric_limits<std::size_t>::max();
+            each_in([&](auto& p) { if (p.connected()) have = std::min(have, p.buffer->available()); });
+            std::size_t k2 = std::min(nIn / ic2, space / oc2);
+            if (k2 == 0) k2 = std::min({have / ic2, space / oc2, std::min(maxIn, requested) / ic2, std::size_t(1)});
+            if (k2 == 0) return {requested, 0, have / ic2 == 0 ? work::Status::INSUFFICIENT_INPUT_ITEMS : work::Status::INSUFFICIENT_OUTPUT_ITEMS};
+            const bool grew = k2 * ic2 > nIn;
+            nIn   = k2 * ic2;
+            nOut  = k2 * oc2;
+            icNow = ic2;
+            ocNow = oc2;
+            if (!grew) break;
+            collectTags(nIn);
+            applyTagSettings(chunkTags);
+        }
         work::Status      st = dispatch(nIn, nOut);
         if (st == work::Status::ERROR) return {requested, 0, st};
         if (!chunkTags.empty()) { // default forwarding (Block.hpp:1113-1263): "gr:" keys only, at the first output sample of the chunk

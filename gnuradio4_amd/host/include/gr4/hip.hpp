@@ -893,6 +893,66 @@ struct Kernel<gr::filter::IQDemodulator<T, Args...>> {
     }
 };
 
+// PowerMetrics<float, N>: 2 N inputs, 5 N outputs at the seam, like IQDemodulator: the N voltage and N current spans go to HBM as rows of one buffer in one copy,
+// one gr4hip_powermetrics_process, one copy back per output; an output no port of which is connected has a NULL pointer in the call and is not copied.  Every settings generation rebuilds
+// the handle's filters (settingsChanged, PowerEstimators.hpp:95).
+template <std::size_t N>
+struct Kernel<gr::electrical::PowerMetrics<float, N>> {
+    using B = gr::electrical::PowerMetrics<float, N>;
+    struct State final : Offload {
+        gr4hip_powermetrics_t* h = nullptr;
+        ~State() override { if (h) gr4hip_powermetrics_destroy(h); }
+    };
+    static gr4hip_powermetrics_params params(B& b) { return {b.sample_rate, b.high_pass, b.low_pass, static_cast<std::size_t>(b.decimate), N}; }
+    static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
+        try {
+            State*     st = offload_state<State>(blk);
+            const auto p  = params(blk);
+            if (!st->h) {
+                check(gr4hip_powermetrics_create(&st->h, &p), "gr4hip_powermetrics_create");
+                st->settings_generation = blk._settings_generation;
+            } else if (st->settings_generation != blk._settings_generation) {
+                check(gr4hip_powermetrics_set_params(st->h, &p), "gr4hip_powermetrics_set_params");
+                st->settings_generation = blk._settings_generation;
+            }
+            const std::size_t bi = nIn * sizeof(float), bo = nOut * sizeof(float);
+            char*             hin = static_cast<char*>(st->h_in.ensure(2 * N * bi));
+            for (std::size_t k = 0; k < N; ++k) {
+                std::memcpy(hin + k * bi, blk.U[k].buffer->read_span(nIn).data(), bi);
+                std::memcpy(hin + (N + k) * bi, blk.I[k].buffer->read_span(nIn).data(), bi);
+            }
+            char* din = static_cast<char*>(st->d_in.ensure(2 * N * bi));
+            check(gr4hip_memcpy_h2d(din, hin, 2 * N * bi, nullptr), "h2d");
+            std::vector<gr::PortOut<float>>* ports[5] = {&blk.P, &blk.Q, &blk.S, &blk.U_rms, &blk.I_rms};
+            float*                           dptr[5];
+            char*                            dout = static_cast<char*>(st->d_out.ensure(5 * N * bo));
+            for (std::size_t q = 0; q < 5; ++q) { // an output with no connected port of any phase is skipped
+                bool any = false;
+                for (auto& port : *ports[q]) any = any || port.connected();
+                dptr[q] = any ? reinterpret_cast<float*>(dout + q * N * bo) : nullptr;
+            }
+            std::size_t produced = 0;
+            check(gr4hip_powermetrics_process(st->h, reinterpret_cast<const float*>(din), reinterpret_cast<const float*>(din + N * bi), nIn, nIn, dptr[0], dptr[1], dptr[2],
+                                              dptr[3], dptr[4], nOut, &produced, nullptr),
+                  "gr4hip_powermetrics_process");
+            if (produced != nOut) throw std::runtime_error("PowerMetrics: the work loop must hand over whole chunks");
+            char* hout = static_cast<char*>(st->h_out.ensure(5 * N * bo));
+            for (std::size_t q = 0; q < 5; ++q)
+                if (dptr[q]) check(gr4hip_memcpy_d2h(hout + q * N * bo, dout + q * N * bo, N * bo, nullptr), "d2h");
+            check(gr4hip_stream_synchronize(nullptr), "sync");
+            for (std::size_t q = 0; q < 5; ++q) {
+                if (!dptr[q]) continue;
+                for (std::size_t k = 0; k < N; ++k)
+                    if ((*ports[q])[k].connected()) std::memcpy((*ports[q])[k].buffer->write_span(nOut).data(), hout + (q * N + k) * bo, bo);
+            }
+            return work::Status::OK;
+        } catch (const std::exception& e) {
+            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
+            return work::Status::ERROR; // never a silent host fallback
+        }
+    }
+};
+
 // ---- merged blocks (gr4/merge.hpp): the parts of a Merge<> become stages of one block; intermediates stay in HBM
 struct SeqStage final : Stage {
     std::unique_ptr<Stage> a, b;

@@ -74,6 +74,8 @@ const bool registered = [] {
     r.insert<FrequencyEstimatorFrequencyDomainDecimating<float>>(named<float>("gr::filter::FrequencyEstimatorFrequencyDomainDecimating"));
     r.insert<IQDemodulatorDecimating<float>>(named<float>("gr::filter::IQDemodulator", ", gr::Resampling<1024U, 1U, false>")); // FrequencyEstimator.hpp:385
     r.insert<IQDemodulatorDecimating<double>>(named<double>("gr::filter::IQDemodulator", ", gr::Resampling<1024U, 1U, false>"));
+    r.insert<gr::electrical::SinglePhasePowerMetrics<float>>(named<float>("gr::electrical::SinglePhasePowerMetrics")); // PowerEstimators.hpp:18-19
+    r.insert<gr::electrical::ThreePhasePowerMetrics<float>>(named<float>("gr::electrical::ThreePhasePowerMetrics"));
     r.insert<gr::blocks::fft::FFT<double, gr::DataSet<double>>>(named<double>("gr::blocks::fft::FFT"));
     r.insert<gr::blocks::fft::FFT<float>>(named<float>("gr::blocks::fft::FFT"));
     r.insert<gr::blocks::fft::FFT<std::complex<float>>>(named<std::complex<float>>("gr::blocks::fft::FFT"));

@@ -624,6 +624,48 @@ int gr4hip_iqdemod_process(gr4hip_iqdemod_t* h, const void* d_ref, const void* d
                            gr4hip_stream_t stream);
 int gr4hip_iqdemod_destroy(gr4hip_iqdemod_t* h);
 
+/* ------------------------------------------------------------------------------------------------ Power metrics (blocks/electrical/.../PowerEstimators.hpp:21-131)
+ * gr::electrical::PowerMetrics<float, nPhases>: per phase a voltage input u and a current input i; one output per chunk of `decimate` inputs on each of P (active
+ * power), Q (reactive), S (apparent), U_rms and I_rms.  Design notes: POWER_METRICS.md.  Restates processBulk (:97-130) exactly:
+ *   uh = HP(u), ih = HP(i): one biquad each, iir::designFilter<float>(HIGHPASS, {order 2, fHigh = high_pass, fs = sample_rate}, BUTTERWORTH) (:69-71); the
+ *   identity when high_pass <= 0 (:73).  ema_p = LP(uh ih), ema_u2 = LP(uh uh), ema_i2 = LP(ih ih): one biquad each, designFilter<float>(LOWPASS, {order 2,
+ *   fLow = min(0.5 sample_rate / decimate, low_pass)}) with the cutoff formed in double (:83-87).  Every filter runs in direct form II as Filter<float>::processOne
+ *   does (FilterTool.hpp:130-136).  At every sample whose index since the last re-initialisation is a multiple of decimate (:111, the FIRST sample of a chunk),
+ *   after that sample went through all filters: U_rms = sqrt(ema_u2), I_rms = sqrt(ema_i2), S = U_rms I_rms, Q = sqrt(max(S^2 - P^2, 0)), P = ema_p (:113-123).
+ *   A negative moving average (a second-order low-pass rings below zero behind a burst) gives NaN for that RMS and with it for S and Q, as math::sqrt and
+ *   std::max(NaN, 0) do.  The coefficients are gr4hip_iir_design's float ones, widened; every state, product and the final step are float64 and the outputs are
+ *   rounded to float once: where the reference's float direct-form-II states (about 1e6 times the signal at 2 Hz / 10 kHz) make its outputs noisy at the 1e-3
+ *   level, the device gives the float64 result.  A non-finite input poisons the filters it reaches until re-initialisation, as in the reference: from two samples
+ *   behind it every output of that phase that depends on the input is NaN (a bad u: all but I_rms; a bad i: all but U_rms); other phases are untouched.  All-zero
+ *   input gives exactly 0.
+ * d_u / d_i: n_phases rows of n_in floats, in_stride elements apart; every output: n_phases rows of n_in / decimate floats, out_stride apart; any output pointer
+ * may be NULL.  n_in == 0 is OK and writes nothing.
+ * GR4HIP_INVALID_ARGUMENT, checked on the host before any device work: a non-finite or non-positive sample_rate or low_pass, a non-finite high_pass or one
+ * >= sample_rate / 2, decimate == 0, n_phases outside 1 ... 16, n_in % decimate != 0, a stride smaller than its row, an input overlapping an output, a design
+ * that is not one biquad or has a pole outside the unit circle.  A pole ON the circle is taken: the float design of a cutoff below about 2e-4 sample_rate puts
+ * one at z = 1 exactly (1 + a1 + a2 rounds to 0; the low-pass then has b0 = 0 and gives 0, the high-pass becomes a first-order one), the reference runs such
+ * filters, and the exact carries need no decay.
+ * set_params always re-initialises (settingsChanged rebuilds every filter, :95; n_phases is fixed at create); reset zeroes the states.  Both are host-side notes
+ * applied by the next process call on its stream.  process queues its kernels and returns without waiting for them, with one exception: the handle keeps
+ * 160 bytes of carry scratch per phase and segment of the longest call so far, and a call longer than every earlier one frees and allocates it again, which
+ * waits for the whole device (hipFree).  A caller that must not stall makes its longest call first. */
+#define GR4HIP_POWERMETRICS_SEGMENT 4096 /* samples per workgroup segment: where the carries change hands (tests place their boundaries by it) */
+typedef struct gr4hip_powermetrics gr4hip_powermetrics_t;
+typedef struct {
+    float  sample_rate, high_pass, low_pass; /* (:46-48) */
+    size_t decimate;                         /* (:49) inputs per output, input_chunk_size */
+    size_t n_phases;                         /* nPhases */
+} gr4hip_powermetrics_params;
+int    gr4hip_powermetrics_params_default(gr4hip_powermetrics_params* p); /* 10 kHz, 2 Hz, 90 Hz, decimate 100, one phase */
+int    gr4hip_powermetrics_check(const gr4hip_powermetrics_params* p);    /* host only: the validation of create */
+size_t gr4hip_powermetrics_segment(void);                                 /* GR4HIP_POWERMETRICS_SEGMENT of the built library */
+int    gr4hip_powermetrics_create(gr4hip_powermetrics_t** h, const gr4hip_powermetrics_params* p);
+int    gr4hip_powermetrics_set_params(gr4hip_powermetrics_t* h, const gr4hip_powermetrics_params* p);
+int    gr4hip_powermetrics_reset(gr4hip_powermetrics_t* h);
+int    gr4hip_powermetrics_process(gr4hip_powermetrics_t* h, const float* d_u, const float* d_i, size_t in_stride, size_t n_in, float* d_P, float* d_Q, float* d_S,
+                                   float* d_Urms, float* d_Irms, size_t out_stride, size_t* n_out, gr4hip_stream_t stream);
+int    gr4hip_powermetrics_destroy(gr4hip_powermetrics_t* h);
+
 #ifdef __cplusplus
 }
 #endif
