@@ -16,7 +16,7 @@ constructor / call raises (Gr4HipError / ImportError) -- there is no CPU fallbac
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -885,6 +885,84 @@ class PowerMetrics(_Handle):
         check(lib().gr4hip_powermetrics_process(self._h, u.data_ptr(), i.data_ptr(), stride, n, ptr[0], ptr[1], ptr[2], ptr[3], ptr[4], max(n_out, 1), None,
                                                 _stream()), "PowerMetrics.process")
         return tuple(outs)
+
+
+class SchmittEdges(NamedTuple):
+    """the edges of one SchmittTrigger.process_bulk call, in order of `sample`: `count` edges were detected, the tensors hold the first min(count, capacity)"""
+    count: int
+    sample: torch.Tensor       # int64: index within the call's input at which processOne returned the edge
+    kind: torch.Tensor         # int32: 1 RISING, 2 FALLING (gr::trigger::EdgeDetection)
+    edge_idx: torch.Tensor     # int32: lastEdgeIdx
+    edge_offset: torch.Tensor  # float32: value(lastEdgeOffset)
+    n_fit: torch.Tensor        # int32: the regression's n (0 for NO, 2 for BASIC)
+    flags: torch.Tensor        # int32: kind_flags without the kind (capi.SCHMITT_DEGENERATE)
+
+
+class SchmittTrigger(_Handle):
+    """gr::trigger::SchmittTrigger<T, Method, 32> (algorithm/.../SchmittTrigger.hpp:39-357), the detector of gr::blocks::basic::SchmittTrigger
+    (blocks/basic/.../Trigger.hpp:45), for T in {int16, int32, float32, float64}: processOne applied to every sample once, in order, whatever the chunking into
+    calls (include/gr4hip.h "Schmitt trigger").  `method`: "NO_INTERPOLATION", "BASIC_LINEAR_INTERPOLATION", "LINEAR_INTERPOLATION" or the enum's number;
+    "POLYNOMIAL_INTERPOLATION" raises (UNSUPPORTED).  set_params resets the detector (settingsChanged, Trigger.hpp:76-80)."""
+    _destroy = "gr4hip_schmitt_destroy"
+    METHODS = ("NO_INTERPOLATION", "BASIC_LINEAR_INTERPOLATION", "LINEAR_INTERPOLATION", "POLYNOMIAL_INTERPOLATION")
+    _dtypes = {torch.int16: capi.I16, torch.int32: capi.I32, torch.float32: capi.F32, torch.float64: capi.F64}
+
+    def __init__(self, offset: float = 0.0, threshold: float = 1.0, method="NO_INTERPOLATION", dtype=torch.float32):
+        super().__init__()
+        if dtype not in self._dtypes:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "SchmittTrigger", f"dtype {dtype} (int16, int32, float32, float64)")
+        self.dtype = dtype
+        self._p = self._params(offset, threshold, method)
+        check(lib().gr4hip_schmitt_create(C.byref(self._h), C.byref(self._p)), "SchmittTrigger")
+
+    @staticmethod
+    def segment() -> int:
+        """samples per workgroup segment: where the kernels hand their carries over"""
+        return int(lib().gr4hip_schmitt_segment())
+
+    @staticmethod
+    def walk_tile() -> int:
+        """segments per workgroup of the carry walk: a longer call has its carries from several workgroups"""
+        return int(lib().gr4hip_schmitt_walk_tile())
+
+    def _params(self, offset, threshold, method):
+        if isinstance(method, str):
+            if method not in self.METHODS:
+                raise ValueError(f"SchmittTrigger: unknown method '{method}'")
+            method = self.METHODS.index(method)
+        return capi.SchmittParams(float(offset), float(threshold), int(method), self._dtypes[self.dtype])
+
+    offset = property(lambda self: self._p.offset)
+    threshold = property(lambda self: self._p.threshold)
+    method = property(lambda self: self.METHODS[self._p.method])
+
+    def set_params(self, offset=None, threshold=None, method=None):
+        p = self._params(self._p.offset if offset is None else offset, self._p.threshold if threshold is None else threshold,
+                         self._p.method if method is None else method)
+        check(lib().gr4hip_schmitt_set_params(self._h, C.byref(p)), "SchmittTrigger.set_params")
+        self._p = p
+
+    def reset(self):
+        check(lib().gr4hip_schmitt_reset(self._h), "SchmittTrigger.reset")
+
+    def process_bulk(self, x: torch.Tensor, capacity: Optional[int] = None) -> SchmittEdges:
+        """the edges of x (1-D, the handle's dtype); at most `capacity` (default len(x)) are returned, `count` says how many there were.  Reads the count back,
+        so it waits for the call's stream."""
+        x = _dev(x, "SchmittTrigger")
+        if x.dim() != 1 or x.dtype != self.dtype:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "SchmittTrigger", f"input must be a 1-D {self.dtype} tensor")
+        n = x.numel()
+        cap = n if capacity is None else int(capacity)
+        if cap < 0:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "SchmittTrigger", f"capacity {cap}")
+        buf = torch.empty((max(cap, 1), capi.SCHMITT_EDGE_BYTES // 4), dtype=torch.int32, device=x.device)
+        cnt = torch.empty(1, dtype=torch.int64, device=x.device)
+        check(lib().gr4hip_schmitt_process(self._h, x.data_ptr(), n, buf.data_ptr(), cap, cnt.data_ptr(), _stream()), "SchmittTrigger.process")
+        count = int(cnt.item())
+        e = buf[:min(count, cap)]
+        kf = e[:, 4]
+        return SchmittEdges(count, e[:, 0:2].contiguous().view(torch.int64).reshape(-1), kf & capi.SCHMITT_KIND_MASK, e[:, 2].clone(),
+                            e[:, 3].contiguous().view(torch.float32), e[:, 5].clone(), kf & ~capi.SCHMITT_KIND_MASK)
 
 
 def synth_c32(n: int, seed: int = 42, tone_frel: float = 0.1, tone_amp: float = 1.0, noise_amp: float = 1.0, device="cuda") -> torch.Tensor:

@@ -183,6 +183,15 @@ SIGNATURES = {
     "gr4hip_powermetrics_reset": (_i, [_vp]),
     "gr4hip_powermetrics_process": (_i, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _psz, _vp]),
     "gr4hip_powermetrics_destroy": (_i, [_vp]),
+    "gr4hip_schmitt_params_default": (_i, [_vp]),
+    "gr4hip_schmitt_check": (_i, [_vp]),
+    "gr4hip_schmitt_segment": (_sz, []),
+    "gr4hip_schmitt_walk_tile": (_sz, []),
+    "gr4hip_schmitt_create": (_i, [_pvp, _vp]),
+    "gr4hip_schmitt_set_params": (_i, [_vp, _vp]),
+    "gr4hip_schmitt_reset": (_i, [_vp]),
+    "gr4hip_schmitt_process": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "gr4hip_schmitt_destroy": (_i, [_vp]),
 }
 
 class FilterParams(C.Structure):
@@ -208,6 +217,16 @@ class IQDemodParams(C.Structure):
 class PowerMetricsParams(C.Structure):
     """gr4hip_powermetrics_params: the settings of PowerMetrics<float, nPhases> (PowerEstimators.hpp:46-49) plus the number of phases"""
     _fields_ = [("sample_rate", _f), ("high_pass", _f), ("low_pass", _f), ("decimate", C.c_size_t), ("n_phases", C.c_size_t)]
+
+
+SCHMITT_NO_INTERPOLATION, SCHMITT_BASIC_LINEAR_INTERPOLATION, SCHMITT_LINEAR_INTERPOLATION, SCHMITT_POLYNOMIAL_INTERPOLATION = range(4)
+SCHMITT_RISING, SCHMITT_FALLING, SCHMITT_KIND_MASK, SCHMITT_DEGENERATE = 1, 2, 3, 4
+SCHMITT_EDGE_BYTES = 24  # gr4hip_schmitt_edge: {int64 sample, int32 edge_idx, float edge_offset, uint32 kind_flags, uint32 n_fit}
+
+
+class SchmittParams(C.Structure):
+    """gr4hip_schmitt_params: offset and threshold of gr::trigger::SchmittTrigger (SchmittTrigger.hpp:45-46), its interpolation method and the sample type"""
+    _fields_ = [("offset", _d), ("threshold", _d), ("method", _i), ("dtype", _i)]
 
 
 LOWPASS, HIGHPASS, BANDPASS, BANDSTOP = range(4)

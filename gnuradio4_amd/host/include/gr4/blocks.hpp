@@ -525,6 +525,93 @@ using ThreePhasePowerMetrics = PowerMetrics<T, 3U>;
 template <typename T>
 using SinglePhasePowerMetrics = PowerMetrics<T, 1U>;
 } // namespace gr::electrical
+namespace gr::trigger {
+enum class InterpolationMethod : int { NO_INTERPOLATION = 0, BASIC_LINEAR_INTERPOLATION = 1, LINEAR_INTERPOLATION = 2, POLYNOMIAL_INTERPOLATION = 3 }; // SchmittTrigger.hpp:17-22
+enum class EdgeDetection : int { NONE = 0, RISING = 1, FALLING = 2 };                                                                                // (:24)
+} // namespace gr::trigger
+namespace gr::blocks::basic {
+GR_REGISTER_BLOCK("gr::blocks::basic::SchmittTriggerNoInterpolation", gr::blocks::basic::SchmittTrigger, ([T], gr::trigger::InterpolationMethod::NO_INTERPOLATION), [ std::int16_t, std::int32_t, float, double ])
+GR_REGISTER_BLOCK("gr::blocks::basic::SchmittTriggerBasic", gr::blocks::basic::SchmittTrigger, ([T], gr::trigger::InterpolationMethod::BASIC_LINEAR_INTERPOLATION), [ std::int16_t, std::int32_t, float, double ])
+GR_REGISTER_BLOCK("gr::blocks::basic::SchmittTrigger", gr::blocks::basic::SchmittTrigger, ([T], gr::trigger::InterpolationMethod::LINEAR_INTERPOLATION), [ std::int16_t, std::int32_t, float, double ])
+// SchmittTrigger<T, Method> (blocks/basic/.../Trigger.hpp:16-164): passes its samples through and publishes a tag {trigger_name, trigger_time,
+// trigger_time_error, trigger_offset, context} for every detected edge whose name is not empty.  Members, names and the reflected set are the reference's (:47-62).
+// Device-only: the detector (gr::trigger::SchmittTrigger<T, Method, 32>, algorithm/.../SchmittTrigger.hpp) runs behind compute_domain gpu:hip (gr4hip_schmitt_*,
+// gr4/hip.hpp); off the device the work loop refuses loudly.  SchmittTriggerPolynomial (:14) is not provided: the device has no Savitzky-Golay design.
+// _period and _now follow :68-74 and :141: sample_rate sets _period = uint64(1e6f / sample_rate), trigger_time sets _now = trigger_time + uint64(1e6f trigger_offset),
+// every sample adds _period; offset / threshold by settings reset the detector (:76-80).  start() / reset() (:83-89) read the wall clock into _now; this layer has
+// no lifecycle calls, so _now counts from 0 until trigger_time is set.
+// DEVIATIONS from the reference's processBulk (:91-163), stated here and in SCHMITT_TRIGGER.md:
+//   - the reference publishes up to an interpolated edge position and returns (:133-136), so the samples between that position and the detecting sample go
+//     through its detector a second time, and _now advances twice for them.  The device block feeds every sample to the detector exactly once and advances _now
+//     once per sample.  For NO_INTERPOLATION (edge position = detecting sample) the tag streams are identical; for the linear methods the device's tags are
+//     those of the detector class fed once.
+//   - several edges of one chunk are published together, where the reference returns after each.
+//   - an edge whose position sample + lastEdgeIdx lies in front of the chunk -- in front of what has been published -- is dropped, as the reference drops
+//     edgePosition < 0 (:146), and counted in _dropped_edges; the reference's second limit, edgePosition < nProcess, holds likewise.
+//   - the reference holds back the last N_HISTORY samples of a chunk (:93-98); the device handle carries the history across calls, so every sample is passed on.
+//   - trigger_time = _now(sample) - int64(relOffset) in signed arithmetic (the reference converts a negative float to uint64_t, :126, which is undefined).
+//   - forward_tag forwards the chunk's input tags the way this layer's work loop does for every block (the "gr:" keys, at the chunk's first sample).
+template <typename T, gr::trigger::InterpolationMethod Method>
+    requires(std::is_same_v<T, std::int16_t> || std::is_same_v<T, std::int32_t> || std::is_same_v<T, float> || std::is_same_v<T, double>)
+struct SchmittTrigger : Block<SchmittTrigger<T, Method>, NoTagPropagation> {
+    using value_t = T;
+    template <typename U, gr::fixed_string description = "", typename... Arguments>
+    using A = gr::Annotated<U, description, Arguments...>;
+    constexpr static std::size_t                 N_HISTORY = 32;
+    constexpr static trigger::InterpolationMethod kMethod   = Method;
+
+    PortIn<T>  in;
+    PortOut<T> out;
+
+    A<value_t, "offset", Doc<"trigger offset">, Visible>                                                                         offset{value_t(0)};
+    A<value_t, "threshold", Doc<"trigger threshold">, Visible>                                                                   threshold{value_t(1)};
+    A<std::string, "rising trigger", Doc<"trigger name generated on detected rising edge (N.B. \"\" omits trigger)">, Visible>   trigger_name_rising_edge{std::string("RISING")};
+    A<std::string, "falling trigger", Doc<"trigger name generated on detected falling edge (N.B. \"\" omits trigger)">, Visible> trigger_name_falling_edge{std::string("FALLING")};
+    A<float, "avg. sample rate", Visible>                                                                                        sample_rate = 1.f;
+
+    A<bool, "forward tags ", Doc<"false: emit only tags for detected edges">>                                                  forward_tag{true};
+    A<std::string, "trigger name", Doc<"last trigger used to synchronise time">>                                               trigger_name{std::string()};
+    A<std::uint64_t, "trigger time", Doc<"last trigger UTC time used for synchronisation (then sample counting)">, Unit<"ns">> trigger_time{0U};
+    A<float, "trigger offset", Doc<"last trigger offset time used for synchronisation (then sample counting)">, Unit<"s">>     trigger_offset{0.0f};
+    std::string                                                                                                                context = "";
+
+    GR_MAKE_REFLECTABLE(SchmittTrigger, in, out, offset, threshold, trigger_name_rising_edge, trigger_name_falling_edge, sample_rate, forward_tag, trigger_name, trigger_time, trigger_offset, context);
+
+    std::uint64_t _period{1U};
+    std::uint64_t _now{0U};
+    bool          _detector_changed = false; // offset / threshold named by an update since the device handle last took them: the detector is reset (:76-80)
+    std::size_t   _dropped_edges    = 0;     // edges whose position fell outside the chunk (:146)
+    std::size_t   _device_calls     = 0;     // chunks handed to the device
+
+    void settingsChanged(const property_map&, const property_map& newSettings) {
+        if (newSettings.contains("sample_rate")) _period = static_cast<std::uint64_t>(1e6f / sample_rate.value);
+        if (newSettings.contains("trigger_time")) _now = trigger_time.value + static_cast<std::uint64_t>(1e6f * trigger_offset.value);
+        if (newSettings.contains("offset") || newSettings.contains("threshold")) {
+            // what gr4hip_schmitt_check refuses (include/gr4hip.h), said here so that a program that only holds the block needs no library
+            const double o = static_cast<double>(offset.value), t = static_cast<double>(threshold.value);
+            bool         ok = std::isfinite(o) && std::isfinite(t) && t >= 0.0;
+            if constexpr (std::is_integral_v<T>) ok = ok && o + t <= static_cast<double>(std::numeric_limits<T>::max()) && o - t >= static_cast<double>(std::numeric_limits<T>::min());
+            if (!ok) throw std::invalid_argument("SchmittTrigger: threshold must be finite and not negative, and offset +- threshold must stay in the sample type's range");
+            _detector_changed = true;
+        }
+    }
+    [[nodiscard]] gr4hip_schmitt_params params() const {
+        constexpr int dtype = std::is_same_v<T, std::int16_t> ? GR4HIP_I16 : std::is_same_v<T, std::int32_t> ? GR4HIP_I32 : std::is_same_v<T, float> ? GR4HIP_F32 : GR4HIP_F64;
+        return {static_cast<double>(offset.value), static_cast<double>(threshold.value), static_cast<int>(Method), dtype};
+    }
+    work::Status processBulk(std::span<const T>, std::span<T>) { // (the graph ends with ERROR: nothing comes out of the host path)
+        std::fprintf(stderr, "SchmittTrigger: device-only block, needs compute_domain gpu:hip\n");
+        this->_log("SchmittTrigger: device-only block, needs compute_domain gpu:hip");
+        return work::Status::ERROR;
+    }
+};
+template <typename T>
+using SchmittTriggerNoInterpolation = SchmittTrigger<T, trigger::InterpolationMethod::NO_INTERPOLATION>;
+template <typename T>
+using SchmittTriggerBasic = SchmittTrigger<T, trigger::InterpolationMethod::BASIC_LINEAR_INTERPOLATION>;
+template <typename T>
+using SchmittTriggerLinear = SchmittTrigger<T, trigger::InterpolationMethod::LINEAR_INTERPOLATION>;
+} // namespace gr::blocks::basic
 namespace gr::algorithm::window {
 enum class Type : int { None, Rectangular, Hamming, Hann, HannExp, Blackman, Nuttall, BlackmanHarris, BlackmanNuttall, FlatTop, Exponential, Kaiser }; // window.hpp:35 == GR4HIP_WIN_*
 inline constexpr std::array<std::string_view, 12> TypeList{"None", "Rectangular", "Hamming", "Hann", "HannExp", "Blackman", "Nuttall", "BlackmanHarris", "BlackmanNuttall", "FlatTop", "Exponential", "Kaiser"};

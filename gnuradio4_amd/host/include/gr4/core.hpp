@@ -386,6 +386,8 @@ struct NoResampling {
     static constexpr std::size_t kIn = 1, kOut = 1;
     static constexpr bool        kIsConst = true, kEnabled = false;
 };
+// block argument (Block.hpp:676-683): the work loop forwards no input tags; the block publishes what it wants forwarded (basic/Trigger.hpp:18, 104-116)
+struct NoTagPropagation {};
 
 namespace detail {
 template <typename A>
@@ -412,6 +414,9 @@ struct Tag {
 };
 namespace tag {
 inline constexpr std::string_view SAMPLE_RATE = "sample_rate";
+// the trigger tags (Tag.hpp:167-174); like every default tag they travel under their wire key ("gr:trigger_name", ...)
+inline constexpr std::string_view TRIGGER_NAME = "trigger_name", TRIGGER_TIME = "trigger_time", TRIGGER_TIME_ERROR = "trigger_time_error", TRIGGER_OFFSET = "trigger_offset",
+                                  CONTEXT = "context";
 [[nodiscard]] inline std::string_view settingsKey(std::string_view wireKey) { return wireKey.starts_with(GR_TAG_PREFIX) ? wireKey.substr(GR_TAG_PREFIX.size()) : wireKey; } // "gr:x" -> "x"
 [[nodiscard]] inline std::string      wireKey(std::string_view bareKey) { return std::string(GR_TAG_PREFIX) + std::string(bareKey); }
 } // namespace tag
@@ -983,7 +988,7 @@ private:
         }
         work::Status      st = dispatch(nIn, nOut);
         if (st == work::Status::ERROR) return {requested, 0, st};
-        if (!chunkTags.empty()) { // default forwarding (Block.hpp:1113-1263): "gr:" keys only, at the first output sample of the chunk
+        if (!chunkTags.empty() && !(std::is_same_v<Args, NoTagPropagation> || ...)) { // default forwarding (Block.hpp:1113-1263): "gr:" keys only, at the first output sample of the chunk
             const property_map fwd = toOutputTags(chunkTags);
             each_out([&](auto& p) { if (p.connected()) p.buffer->publishTag(fwd, 0); });
         }

@@ -953,6 +953,82 @@ struct Kernel<gr::electrical::PowerMetrics<float, N>> {
     }
 };
 
+// SchmittTrigger<T, Method>: the chunk goes to HBM, one gr4hip_schmitt_process (room for an edge per sample), the count comes back, then that many edges.  The
+// samples pass through on the host, bit for bit.  Every edge with a non-empty name becomes a tag at sample + edge_idx (gr4/blocks.hpp states the deviations
+// from the reference's processBulk).  offset / threshold by settings reset the handle's detector; any other update leaves it alone.
+template <typename T, gr::trigger::InterpolationMethod Method>
+struct Kernel<gr::blocks::basic::SchmittTrigger<T, Method>> {
+    using B = gr::blocks::basic::SchmittTrigger<T, Method>;
+    struct State final : Offload {
+        gr4hip_schmitt_t* h = nullptr;
+        ~State() override { if (h) gr4hip_schmitt_destroy(h); }
+    };
+    static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
+        try {
+            State*     st = offload_state<State>(blk);
+            const auto p  = blk.params();
+            if (!st->h) {
+                check(gr4hip_schmitt_create(&st->h, &p), "gr4hip_schmitt_create");
+                blk._detector_changed = false;
+            } else if (blk._detector_changed) {
+                check(gr4hip_schmitt_set_params(st->h, &p), "gr4hip_schmitt_set_params");
+                blk._detector_changed = false;
+            }
+            ++blk._device_calls;
+            const std::size_t bi  = nIn * sizeof(T);
+            const auto        is  = blk.in.buffer->read_span(nIn);
+            char*             hin = static_cast<char*>(st->h_in.ensure(bi));
+            std::memcpy(hin, is.data(), bi);
+            char* din = static_cast<char*>(st->d_in.ensure(bi));
+            check(gr4hip_memcpy_h2d(din, hin, bi, nullptr), "h2d");
+            constexpr std::size_t head = 16; // the counter, then the edges
+            char*                 dout = static_cast<char*>(st->d_out.ensure(head + nIn * sizeof(gr4hip_schmitt_edge)));
+            check(gr4hip_schmitt_process(st->h, din, nIn, reinterpret_cast<gr4hip_schmitt_edge*>(dout + head), nIn, reinterpret_cast<unsigned long long*>(dout), nullptr),
+                  "gr4hip_schmitt_process");
+            char* hout = static_cast<char*>(st->h_out.ensure(head + nIn * sizeof(gr4hip_schmitt_edge)));
+            check(gr4hip_memcpy_d2h(hout, dout, head, nullptr), "d2h");
+            check(gr4hip_stream_synchronize(nullptr), "sync");
+            unsigned long long count = 0;
+            std::memcpy(&count, hout, sizeof count);
+            if (count > nIn) throw std::runtime_error("SchmittTrigger: more edges than samples");
+            if (count) {
+                check(gr4hip_memcpy_d2h(hout + head, dout + head, count * sizeof(gr4hip_schmitt_edge), nullptr), "d2h");
+                check(gr4hip_stream_synchronize(nullptr), "sync");
+            }
+            if (blk.out.connected()) {
+                std::memcpy(blk.out.buffer->write_span(nOut).data(), is.data(), bi);
+                if (blk.forward_tag.value) blk.out.buffer->publishTag(blk.toOutputTags(blk.in.buffer->mergedTags(nIn)), 0);
+            }
+            const auto* edges = reinterpret_cast<const gr4hip_schmitt_edge*>(hout + head);
+            for (unsigned long long k = 0; k < count; ++k) {
+                const gr4hip_schmitt_edge& e    = edges[k];
+                const std::string&         name = (e.kind_flags & GR4HIP_SCHMITT_KIND_MASK) == GR4HIP_SCHMITT_RISING ? blk.trigger_name_rising_edge.value : blk.trigger_name_falling_edge.value;
+                if (name.empty()) continue;
+                const std::int64_t pos = e.sample + e.edge_idx;
+                if (pos < 0 || pos >= static_cast<std::int64_t>(nIn)) { // (Trigger.hpp:146)
+                    ++blk._dropped_edges;
+                    continue;
+                }
+                const std::uint64_t now       = blk._now + (static_cast<std::uint64_t>(e.sample) + 1U) * blk._period; // (:141) _now += _period in front of every sample
+                const float         relOffset = (static_cast<float>(e.edge_idx) + e.edge_offset) * static_cast<float>(blk._period); // (:121-122)
+                const std::uint64_t time      = static_cast<std::uint64_t>(static_cast<std::int64_t>(now) - static_cast<std::int64_t>(relOffset));
+                if (blk.out.connected())
+                    blk.out.buffer->publishTag(property_map{{tag::wireKey(tag::TRIGGER_NAME), name},
+                                                            {tag::wireKey(tag::TRIGGER_TIME), time},
+                                                            {tag::wireKey(tag::TRIGGER_TIME_ERROR), std::uint64_t(0)},
+                                                            {tag::wireKey(tag::TRIGGER_OFFSET), relOffset},
+                                                            {tag::wireKey(tag::CONTEXT), blk.context}},
+                                               static_cast<std::size_t>(pos));
+            }
+            blk._now += static_cast<std::uint64_t>(nIn) * blk._period;
+            return work::Status::OK;
+        } catch (const std::exception& e) {
+            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
+            return work::Status::ERROR; // never a silent host fallback
+        }
+    }
+};
+
 // ---- merged blocks (gr4/merge.hpp): the parts of a Merge<> become stages of one block; intermediates stay in HBM
 struct SeqStage final : Stage {
     std::unique_ptr<Stage> a, b;

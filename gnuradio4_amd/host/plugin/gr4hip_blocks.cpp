@@ -46,6 +46,14 @@ void register_io(BlockRegistry& r) { // sources / sinks / converters so that a w
     r.insert<gr::hip::D2H<T>>(named<T>("gr::hip::D2H"));
 }
 
+template <typename T>
+void register_schmitt(BlockRegistry& r) { // basic/Trigger.hpp:11-13; SchmittTriggerPolynomial (:14) has no device implementation and is not registered
+    using namespace gr::blocks::basic;
+    r.insert<SchmittTriggerNoInterpolation<T>>(named<T>("gr::blocks::basic::SchmittTriggerNoInterpolation"));
+    r.insert<SchmittTriggerBasic<T>>(named<T>("gr::blocks::basic::SchmittTriggerBasic"));
+    r.insert<SchmittTriggerLinear<T>>(named<T>("gr::blocks::basic::SchmittTrigger"));
+}
+
 const bool registered = [] {
     BlockRegistry& r = grPluginInstance();
     using namespace gr::filter;
@@ -76,6 +84,7 @@ const bool registered = [] {
     r.insert<IQDemodulatorDecimating<double>>(named<double>("gr::filter::IQDemodulator", ", gr::Resampling<1024U, 1U, false>"));
     r.insert<gr::electrical::SinglePhasePowerMetrics<float>>(named<float>("gr::electrical::SinglePhasePowerMetrics")); // PowerEstimators.hpp:18-19
     r.insert<gr::electrical::ThreePhasePowerMetrics<float>>(named<float>("gr::electrical::ThreePhasePowerMetrics"));
+    register_schmitt<std::int16_t>(r); register_schmitt<std::int32_t>(r); register_schmitt<float>(r); register_schmitt<double>(r);
     r.insert<gr::blocks::fft::FFT<double, gr::DataSet<double>>>(named<double>("gr::blocks::fft::FFT"));
     r.insert<gr::blocks::fft::FFT<float>>(named<float>("gr::blocks::fft::FFT"));
     r.insert<gr::blocks::fft::FFT<std::complex<float>>>(named<std::complex<float>>("gr::blocks::fft::FFT"));

@@ -666,6 +666,72 @@ int    gr4hip_powermetrics_process(gr4hip_powermetrics_t* h, const float* d_u, c
                                    float* d_Urms, float* d_Irms, size_t out_stride, size_t* n_out, gr4hip_stream_t stream);
 int    gr4hip_powermetrics_destroy(gr4hip_powermetrics_t* h);
 
+/* ------------------------------------------------------------------------------------------------ Schmitt trigger (algorithm/.../SchmittTrigger.hpp:39-357)
+ * gr::trigger::SchmittTrigger<T, Method, 32>, the detector of gr::blocks::basic::SchmittTrigger (blocks/basic/.../Trigger.hpp:45: N_HISTORY = 32), for T in
+ * {int16, int32, float, double}: processOne (:103-222) applied to every sample of the stream exactly once, in order, whatever the chunking into calls; the
+ * output is the ordered list of the samples at which it returned RISING or FALLING, with lastEdgeIdx and value(lastEdgeOffset).  Design notes: SCHMITT_TRIGGER.md.
+ *   thresholds: upper = offset + threshold, lower = offset - threshold in the value type (:67).
+ *   a created or reset handle is a detector after reset() (:90-101): _lastState false, nothing accumulated, a history of 32 zeros (the first yPrev is 0).
+ *   NO_INTERPOLATION (:107-121): RISING where !_lastState and x >= upper, FALLING where _lastState and x <= lower; edge_idx 0, edge_offset 0, n_fit 0.
+ *   BASIC_LINEAR_INTERPOLATION (:124-163): the same edges; computeEdgePosition (:133-142) on float(yPrev), float(yCurr), float(offset): {0, 0} where the two
+ *     are equal, else crossingPos = -1 + (offset - y1) / (y2 - y1), edge_idx = round(crossingPos), edge_offset = crossingPos - edge_idx; n_fit 2.
+ *   LINEAR_INTERPOLATION (:166-222): the state is (_lastState, in zone, index at which the zone was entered), accumulatedSamples = i - i_entry + 1.  A zone is
+ *     entered only while none is open (yPrev <= lower && yCurr > lower while low, yPrev >= upper && yCurr < upper while high, :177-183), an edge needs an open
+ *     zone (:189-190) -- a stream that starts inside the band gives no edge until it has left it on the far side once --, a zone is abandoned where the sample
+ *     leaves the band on the near side (:215-217).  At an edge findCrossingIndexLinearRegression (:294-324) runs over the n = min(max(accumulated, 2), 32)
+ *     newest samples, newest first, in comp_t (T for float / double, float for the integer types), every operation rounded on its own in the reference's order;
+ *     relativeIndex = value_t(crossing) - value_t(n - 1) (:198; an integer T truncates the crossing, and its offset is 0), edge_idx = round(relativeIndex),
+ *     edge_offset = float(relativeIndex) - float(edge_idx) (:201-205); n_fit = n.
+ *   degenerate fits: a crossing that is not finite, or whose index does not fit int32 after round (an integer T: whose truncation or relativeIndex leaves T's
+ *     range), is undefined behaviour in the reference (a zero slope, a NaN in the window; for BASIC a NaN yPrev).  The device reports that edge with
+ *     GR4HIP_SCHMITT_DEGENERATE, edge_idx 0, edge_offset 0; the state flips as it does in the reference.
+ *   a NaN sample compares false everywhere and holds the state.
+ * d_in: n_in samples of params.dtype.  d_edges: room for `capacity` edges, written in order of `sample`; *d_n_edges (device memory) receives the number of edges
+ * DETECTED: only the first `capacity` are written, and the state advances over the whole call either way.  n_in == 0 is OK (*d_n_edges = 0).
+ * GR4HIP_UNSUPPORTED for POLYNOMIAL_INTERPOLATION (:224-289: it needs the Savitzky-Golay coefficient design, which this library does not have; no other method
+ * is taken in its place).  GR4HIP_INVALID_ARGUMENT, checked on the host before any device work: a non-finite offset, a non-finite or negative threshold, an
+ * unknown method or dtype, for the integer types a fractional offset / threshold or ones whose sum or difference leaves the type's range, for float ones that
+ * are not finite as float.  set_params resets the detector as settingsChanged does (Trigger.hpp:76-80; the dtype is fixed at create); reset is reset() (:90-101).
+ * Both are host-side notes applied by the next process call on its stream.  process queues its three launches and returns without waiting for them, with one
+ * exception: the handle keeps 56 bytes of scratch per segment of the longest call so far, and a call longer than every earlier one frees and allocates it
+ * again, which waits for the whole device (hipFree).  A caller that must not stall makes its longest call first. */
+#define GR4HIP_SCHMITT_SEGMENT 4096 /* samples per workgroup segment: where the carries change hands (tests place their boundaries by it) */
+/* the longest call: GR4HIP_INVALID_ARGUMENT beyond it, before any device work.  The carry walk's workgroups do not wait for one another: each composes the
+ * segments in front of its tile itself, so that work grows with the square of the call's length (83 us of a 1.36 ms call at 2^27 samples; SCHMITT_TRIGGER.md
+ * "Rates and limits").  A longer stream goes in several calls: the handle carries the state, and the edges are the same whatever the chunking. */
+#define GR4HIP_SCHMITT_MAX_SAMPLES 4294967296ULL /* 2^32 */
+typedef struct gr4hip_schmitt gr4hip_schmitt_t;
+typedef enum { /* gr::trigger::InterpolationMethod (:17-22) */
+    GR4HIP_SCHMITT_NO_INTERPOLATION = 0, GR4HIP_SCHMITT_BASIC_LINEAR_INTERPOLATION = 1, GR4HIP_SCHMITT_LINEAR_INTERPOLATION = 2,
+    GR4HIP_SCHMITT_POLYNOMIAL_INTERPOLATION = 3 /* GR4HIP_UNSUPPORTED */
+} gr4hip_schmitt_method;
+enum { /* kind_flags: the low two bits are gr::trigger::EdgeDetection (:24) */
+    GR4HIP_SCHMITT_RISING = 1, GR4HIP_SCHMITT_FALLING = 2, GR4HIP_SCHMITT_KIND_MASK = 3, GR4HIP_SCHMITT_DEGENERATE = 4
+};
+typedef struct {
+    double offset, threshold; /* _offset, _threshold (:45-46), converted to the value type */
+    int    method;            /* gr4hip_schmitt_method */
+    int    dtype;             /* GR4HIP_I16, GR4HIP_I32, GR4HIP_F32 or GR4HIP_F64 (Trigger.hpp:20-22) */
+} gr4hip_schmitt_params;
+typedef struct {
+    int64_t  sample;      /* index within this call's d_in of the sample at which processOne returned the edge */
+    int32_t  edge_idx;    /* lastEdgeIdx (:56) */
+    float    edge_offset; /* value(lastEdgeOffset) (:57) */
+    uint32_t kind_flags;
+    uint32_t n_fit;       /* the regression's n (:194); 0 for NO, 2 for BASIC */
+} gr4hip_schmitt_edge;    /* 24 bytes */
+int    gr4hip_schmitt_params_default(gr4hip_schmitt_params* p); /* offset 0, threshold 1 (:45-46), NO_INTERPOLATION, float */
+int    gr4hip_schmitt_check(const gr4hip_schmitt_params* p);    /* host only: the validation of create */
+size_t gr4hip_schmitt_segment(void);                            /* GR4HIP_SCHMITT_SEGMENT of the built library */
+size_t gr4hip_schmitt_walk_tile(void);                          /* segments per workgroup of the carry walk: a call of more than this many segments has its carries
+                                                                   from more than one workgroup, each composing the segments in front of its tile (tests size by it) */
+int    gr4hip_schmitt_create(gr4hip_schmitt_t** h, const gr4hip_schmitt_params* p);
+int    gr4hip_schmitt_set_params(gr4hip_schmitt_t* h, const gr4hip_schmitt_params* p);
+int    gr4hip_schmitt_reset(gr4hip_schmitt_t* h);
+int    gr4hip_schmitt_process(gr4hip_schmitt_t* h, const void* d_in, size_t n_in, gr4hip_schmitt_edge* d_edges, size_t capacity, unsigned long long* d_n_edges,
+                              gr4hip_stream_t stream);
+int    gr4hip_schmitt_destroy(gr4hip_schmitt_t* h);
+
 #ifdef __cplusplus
 }
 #endif
