@@ -965,6 +965,73 @@ class SchmittTrigger(_Handle):
                             e[:, 3].contiguous().view(torch.float32), e[:, 5].clone(), kf & ~capi.SCHMITT_KIND_MASK)
 
 
+class SvdDenoiser(_Handle):
+    """gr::filter::SvdDenoiser<T> (blocks/filter/.../SvdDenoiser.hpp:14-91) for T in {float32, float64, complex64, complex128} with the reference's setting
+    names and defaults (the two thresholds default to eps of T's real type): Hankel-SVD low-rank denoising, processOne applied to every sample once, in order,
+    whatever the chunking into calls (include/gr4hip.h "SVD denoiser", SVD_DENOISER.md).  set_params resets, as setParameters does (SvdFilter.hpp:221-229)."""
+    _destroy = "gr4hip_svddenoise_destroy"
+    _names = ("window_size", "hankel_rows", "max_rank", "relative_threshold", "absolute_threshold", "energy_fraction", "hop_fraction")
+    _ints = ("window_size", "hankel_rows", "max_rank")
+    _dtypes = {torch.float32: capi.F32, torch.float64: capi.F64, torch.complex64: capi.C32, torch.complex128: capi.C64}
+
+    def __init__(self, dtype=torch.float32, **settings):
+        super().__init__()
+        if dtype not in self._dtypes:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "SvdDenoiser", f"dtype {dtype} (float32, float64, complex64, complex128)")
+        self.dtype = dtype
+        p = capi.SvdDenoiseParams()
+        check(lib().gr4hip_svddenoise_params_default(C.byref(p), self._dtypes[dtype]), "SvdDenoiser")
+        self._p = self._params(p, settings)
+        check(lib().gr4hip_svddenoise_create(C.byref(self._h), C.byref(self._p)), "SvdDenoiser")
+
+    @staticmethod
+    def windows_per_group() -> int:
+        """windows per workgroup of the kernel"""
+        return int(lib().gr4hip_svddenoise_windows_per_group())
+
+    def _params(self, p, settings):
+        for k, v in settings.items():
+            if k not in self._names:
+                raise TypeError(f"SvdDenoiser: unknown setting '{k}'")
+            setattr(p, k, int(v) if k in self._ints else float(v))
+        return p
+
+    def __getattr__(self, name):
+        if name in type(self)._names:
+            return getattr(self.__dict__["_p"], name)
+        raise AttributeError(name)
+
+    def set_params(self, **settings):
+        p = self._params(capi.SvdDenoiseParams.from_buffer_copy(self._p), settings)
+        check(lib().gr4hip_svddenoise_set_params(self._h, C.byref(p)), "SvdDenoiser.set_params")
+        self._p = p
+
+    def reset(self):
+        check(lib().gr4hip_svddenoise_reset(self._h), "SvdDenoiser.reset")
+
+    def process_bulk(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        x = _dev(x, "SvdDenoiser")
+        if x.dim() != 1 or x.dtype != self.dtype:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "SvdDenoiser", f"input must be a 1-D {self.dtype} tensor")
+        n = x.numel()
+        y = _out(out, n, self.dtype, x, "SvdDenoiser.process")
+        check(lib().gr4hip_svddenoise_process(self._h, x.data_ptr(), n, y.data_ptr(), _stream()), "SvdDenoiser.process")
+        return y[:n]
+
+    def stats(self):
+        """(windows started since the handle was made, windows among them that gave NaN: a non-finite sample, or sweeps that did not converge); waits for the
+        stream of the handle's last call"""
+        w, nc = C.c_ulonglong(0), C.c_ulonglong(0)
+        check(lib().gr4hip_svddenoise_stats(self._h, C.byref(w), C.byref(nc)), "SvdDenoiser.stats")
+        return int(w.value), int(nc.value)
+
+    def sweeps(self) -> int:
+        """Jacobi sweeps of all windows since the handle was made; waits as stats() does"""
+        s = C.c_ulonglong(0)
+        check(lib().gr4hip_svddenoise_sweeps(self._h, C.byref(s)), "SvdDenoiser.sweeps")
+        return int(s.value)
+
+
 def synth_c32(n: int, seed: int = 42, tone_frel: float = 0.1, tone_amp: float = 1.0, noise_amp: float = 1.0, device="cuda") -> torch.Tensor:
     out = torch.empty(n, dtype=torch.complex64, device=device)
     check(lib().gr4hip_synth_c32(out.data_ptr(), n, seed, tone_frel, tone_amp, noise_amp, _stream()), "synth_c32")

@@ -192,6 +192,16 @@ SIGNATURES = {
     "gr4hip_schmitt_reset": (_i, [_vp]),
     "gr4hip_schmitt_process": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     "gr4hip_schmitt_destroy": (_i, [_vp]),
+    "gr4hip_svddenoise_params_default": (_i, [_vp, _i]),
+    "gr4hip_svddenoise_check": (_i, [_vp]),
+    "gr4hip_svddenoise_windows_per_group": (_sz, []),
+    "gr4hip_svddenoise_create": (_i, [_pvp, _vp]),
+    "gr4hip_svddenoise_set_params": (_i, [_vp, _vp]),
+    "gr4hip_svddenoise_reset": (_i, [_vp]),
+    "gr4hip_svddenoise_process": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "gr4hip_svddenoise_stats": (_i, [_vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
+    "gr4hip_svddenoise_sweeps": (_i, [_vp, C.POINTER(C.c_ulonglong)]),
+    "gr4hip_svddenoise_destroy": (_i, [_vp]),
 }
 
 class FilterParams(C.Structure):
@@ -227,6 +237,15 @@ SCHMITT_EDGE_BYTES = 24  # gr4hip_schmitt_edge: {int64 sample, int32 edge_idx, f
 class SchmittParams(C.Structure):
     """gr4hip_schmitt_params: offset and threshold of gr::trigger::SchmittTrigger (SchmittTrigger.hpp:45-46), its interpolation method and the sample type"""
     _fields_ = [("offset", _d), ("threshold", _d), ("method", _i), ("dtype", _i)]
+
+
+SVDDENOISE_MAX_WINDOW, SVDDENOISE_MAX_WINDOW_COMPLEX = 128, 64
+
+
+class SvdDenoiseParams(C.Structure):
+    """gr4hip_svddenoise_params: the sample type and the seven settings of gr::filter::SvdDenoiser<T> (SvdDenoiser.hpp:37-51)"""
+    _fields_ = [("dtype", _i), ("window_size", C.c_size_t), ("hankel_rows", C.c_size_t), ("max_rank", C.c_uint64), ("relative_threshold", _d),
+                ("absolute_threshold", _d), ("energy_fraction", _d), ("hop_fraction", _d)]
 
 
 LOWPASS, HIGHPASS, BANDPASS, BANDSTOP = range(4)

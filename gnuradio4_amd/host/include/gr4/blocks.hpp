@@ -483,6 +483,57 @@ template <typename T>
 using IQDemodulatorDecimating = IQDemodulator<T, Resampling<1024U, 1U, false>>;
 template <typename T, DerivativeMethod M>
 using IQDemodulatorFixed = IQDemodulator<T, Resampling<1024U, 1U, false>, Derivative<M, true>>;
+
+GR_REGISTER_BLOCK(gr::filter::SvdDenoiser, [T], [ float, double, std::complex<float>, std::complex<double> ])
+// SvdDenoiser<T> (blocks/filter/.../SvdDenoiser.hpp:14-91): Hankel-SVD low-rank denoising, one output per input.  Members, names, defaults and the reflected set
+// are the reference's (:34-53).  Device-only: the windows are decomposed behind compute_domain gpu:hip (gr4hip_svddenoise_*, gr4/hip.hpp, SVD_DENOISER.md); off
+// the device the work loop refuses loudly.  Any update that names one of the seven settings is setParameters (:76-86), which resets the stream's history; what
+// gr4hip_svddenoise_check refuses is refused here, and a window beyond the device kernel's limits fails the work loop (GR4HIP_UNSUPPORTED), never a host path.
+template <typename T>
+    requires(std::floating_point<T> || std::is_same_v<T, std::complex<float>> || std::is_same_v<T, std::complex<double>>)
+struct SvdDenoiser : Block<SvdDenoiser<T>> {
+    using RealT = std::conditional_t<std::is_same_v<T, float> || std::is_same_v<T, std::complex<float>>, float, double>;
+
+    PortIn<T>  in;
+    PortOut<T> out;
+
+    Annotated<gr::Size_t, "window size", Doc<"analysis window size (samples)">>                   window_size = 64U;
+    Annotated<gr::Size_t, "Hankel rows", Doc<"number of Hankel matrix rows (0 = window_size/2)">> hankel_rows = 0U;
+    Annotated<gr::Size_t, "max rank", Doc<"maximum singular values to keep (max = no limit)">>    max_rank    = std::numeric_limits<gr::Size_t>::max();
+    Annotated<RealT, "relative threshold", Doc<"minimum ratio sigma_i/sigma_0 to keep">, Unit<"ratio">>             relative_threshold = std::numeric_limits<RealT>::epsilon();
+    Annotated<RealT, "absolute threshold", Doc<"minimum absolute value of sigma_i to keep">>                        absolute_threshold = std::numeric_limits<RealT>::epsilon();
+    Annotated<RealT, "energy fraction", Doc<"fraction of total energy to retain (1.0 = all)">, Unit<"ratio">>       energy_fraction    = RealT{1};
+    Annotated<RealT, "hop fraction", Doc<"SVD recomputation interval as fraction of window_size">, Unit<"ratio">>   hop_fraction       = RealT{0.25};
+
+    GR_MAKE_REFLECTABLE(SvdDenoiser, in, out, window_size, hankel_rows, max_rank, relative_threshold, absolute_threshold, energy_fraction, hop_fraction);
+
+    bool        _parameters_changed = false; // an update named a setting since the device handle last took them: setParameters, a reset (:76-86)
+    std::size_t _device_calls       = 0;     // chunks handed to the device
+
+    void settingsChanged(const property_map&, const property_map& newSettings) {
+        if (newSettings.contains("window_size") || newSettings.contains("hankel_rows") || newSettings.contains("max_rank") || newSettings.contains("relative_threshold") ||
+            newSettings.contains("absolute_threshold") || newSettings.contains("energy_fraction") || newSettings.contains("hop_fraction")) {
+            // what gr4hip_svddenoise_check refuses (include/gr4hip.h), said here so that a program that only holds the block needs no library
+            const double rel = static_cast<double>(relative_threshold.value), ab = static_cast<double>(absolute_threshold.value);
+            const double ef = static_cast<double>(energy_fraction.value), hf = static_cast<double>(hop_fraction.value);
+            const std::size_t W = std::max<std::size_t>(window_size.value, 2);
+            if (!(std::isfinite(rel) && rel >= 0.0 && std::isfinite(ab) && ab >= 0.0 && std::isfinite(ef) && std::isfinite(hf) && hf >= 0.0 && hf <= 1.0 && hankel_rows.value <= W))
+                throw std::invalid_argument("SvdDenoiser: thresholds must be finite and not negative, energy_fraction finite, hop_fraction in [0, 1], hankel_rows <= window_size");
+            _parameters_changed = true;
+        }
+    }
+    [[nodiscard]] gr4hip_svddenoise_params params() const {
+        constexpr int dtype = std::is_same_v<T, float> ? GR4HIP_F32 : std::is_same_v<T, double> ? GR4HIP_F64 : std::is_same_v<T, std::complex<float>> ? GR4HIP_C32 : GR4HIP_C64;
+        return {dtype, static_cast<std::size_t>(window_size.value), static_cast<std::size_t>(hankel_rows.value), static_cast<std::uint64_t>(max_rank.value),
+                static_cast<double>(relative_threshold.value), static_cast<double>(absolute_threshold.value), static_cast<double>(energy_fraction.value),
+                static_cast<double>(hop_fraction.value)};
+    }
+    work::Status processBulk(std::span<const T>, std::span<T>) { // (the graph ends with ERROR: nothing comes out of the host path)
+        std::fprintf(stderr, "SvdDenoiser: device-only block, needs compute_domain gpu:hip\n");
+        this->_log("SvdDenoiser: device-only block, needs compute_domain gpu:hip");
+        return work::Status::ERROR;
+    }
+};
 } // namespace gr::filter
 namespace gr::electrical {
 GR_REGISTER_BLOCK("gr::electrical::ThreePhasePowerMetrics", gr::electrical::PowerMetrics, ([T], 3UZ), [ float ])

@@ -1029,6 +1029,49 @@ struct Kernel<gr::blocks::basic::SchmittTrigger<T, Method>> {
     }
 };
 
+// SvdDenoiser<T>: the chunk goes to HBM, one gr4hip_svddenoise_process, the same number of samples comes back.  The handle carries the history and the position
+// within the hop across chunks, so the outputs do not depend on how the scheduler cuts the stream.  An update that names one of the block's settings is
+// setParameters (SvdDenoiser.hpp:76-86): gr4hip_svddenoise_set_params, which resets.
+template <typename T>
+struct Kernel<gr::filter::SvdDenoiser<T>> {
+    using B = gr::filter::SvdDenoiser<T>;
+    struct State final : Offload {
+        gr4hip_svddenoise_t* h = nullptr;
+        ~State() override { if (h) gr4hip_svddenoise_destroy(h); }
+    };
+    static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
+        try {
+            State*     st = offload_state<State>(blk);
+            const auto p  = blk.params();
+            if (!st->h) {
+                check(gr4hip_svddenoise_create(&st->h, &p), "gr4hip_svddenoise_create");
+                blk._parameters_changed = false;
+            } else if (blk._parameters_changed) {
+                check(gr4hip_svddenoise_set_params(st->h, &p), "gr4hip_svddenoise_set_params");
+                blk._parameters_changed = false;
+            }
+            if (nOut != nIn) throw std::runtime_error("SvdDenoiser: one output per input");
+            ++blk._device_calls;
+            const std::size_t bytes = nIn * sizeof(T);
+            const auto        is    = blk.in.buffer->read_span(nIn);
+            char*             hin   = static_cast<char*>(st->h_in.ensure(bytes));
+            std::memcpy(hin, is.data(), bytes);
+            char* din  = static_cast<char*>(st->d_in.ensure(bytes));
+            char* dout = static_cast<char*>(st->d_out.ensure(bytes));
+            check(gr4hip_memcpy_h2d(din, hin, bytes, nullptr), "h2d");
+            check(gr4hip_svddenoise_process(st->h, din, nIn, dout, nullptr), "gr4hip_svddenoise_process");
+            char* hout = static_cast<char*>(st->h_out.ensure(bytes));
+            check(gr4hip_memcpy_d2h(hout, dout, bytes, nullptr), "d2h");
+            check(gr4hip_stream_synchronize(nullptr), "sync");
+            if (blk.out.connected()) std::memcpy(blk.out.buffer->write_span(nOut).data(), hout, bytes);
+            return work::Status::OK;
+        } catch (const std::exception& e) {
+            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
+            return work::Status::ERROR; // never a silent host fallback
+        }
+    }
+};
+
 // ---- merged blocks (gr4/merge.hpp): the parts of a Merge<> become stages of one block; intermediates stay in HBM
 struct SeqStage final : Stage {
     std::unique_ptr<Stage> a, b;

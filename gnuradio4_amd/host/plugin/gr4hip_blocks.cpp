@@ -85,6 +85,10 @@ const bool registered = [] {
     r.insert<gr::electrical::SinglePhasePowerMetrics<float>>(named<float>("gr::electrical::SinglePhasePowerMetrics")); // PowerEstimators.hpp:18-19
     r.insert<gr::electrical::ThreePhasePowerMetrics<float>>(named<float>("gr::electrical::ThreePhasePowerMetrics"));
     register_schmitt<std::int16_t>(r); register_schmitt<std::int32_t>(r); register_schmitt<float>(r); register_schmitt<double>(r);
+    r.insert<SvdDenoiser<float>>(named<float>("gr::filter::SvdDenoiser")); // SvdDenoiser.hpp:12
+    r.insert<SvdDenoiser<double>>(named<double>("gr::filter::SvdDenoiser"));
+    r.insert<SvdDenoiser<std::complex<float>>>(named<std::complex<float>>("gr::filter::SvdDenoiser"));
+    r.insert<SvdDenoiser<std::complex<double>>>(named<std::complex<double>>("gr::filter::SvdDenoiser"));
     r.insert<gr::blocks::fft::FFT<double, gr::DataSet<double>>>(named<double>("gr::blocks::fft::FFT"));
     r.insert<gr::blocks::fft::FFT<float>>(named<float>("gr::blocks::fft::FFT"));
     r.insert<gr::blocks::fft::FFT<std::complex<float>>>(named<std::complex<float>>("gr::blocks::fft::FFT"));

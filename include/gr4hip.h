@@ -732,6 +732,52 @@ int    gr4hip_schmitt_process(gr4hip_schmitt_t* h, const void* d_in, size_t n_in
                               gr4hip_stream_t stream);
 int    gr4hip_schmitt_destroy(gr4hip_schmitt_t* h);
 
+/* ------------------------------------------------------------------------------------------------ SVD denoiser (blocks/filter/.../SvdDenoiser.hpp:14-91)
+ * gr::filter::SvdDenoiser<T> over gr::algorithm::svd_filter::SvdDenoiser<T> (algorithm/filter/SvdFilter.hpp:143-236) for T in {float, double, complex<float>,
+ * complex<double>}, with the Default boundary policy and default value 0 the block always uses (SvdDenoiser.hpp:58-66).  Design notes: SVD_DENOISER.md.
+ *   W = max(window_size, 2), L = hankel_rows ? hankel_rows : W / 2, K = W - L + 1, hop = max(1, size_t(RealT(W) * hop_fraction)) with the product in RealT
+ *   (SvdFilter.hpp:183), delay = (W - 1) / 2, safe = min(W - 1 - delay, W > hop ? W - hop : 0) (:174-176).
+ *   processOne (:190-202) on every sample of the stream exactly once, whatever the chunking into calls: at every sample whose index n since the last reset is a
+ *   multiple of hop the window w[0 .. W) -- the last W samples ending at n, oldest first, zeros in front of the stream -- gives H[i][j] = w[i + j]; its singular
+ *   values sigma_0 >= sigma_1 >= ... rounded to RealT go through computeEffectiveRank (:43-65) in RealT arithmetic, k = min(max(rank, 1), min(L, K)); d[0 .. W) is
+ *   the anti-diagonal average (hankelAverage) of the rank-k approximation (:72-115) and samples n ... n + hop - 1 output d[safe .. safe + hop), rounded to T.
+ *   The device computes the singular triplets in float64 for all four types (one-sided Jacobi), so for float it gives the exact low-rank answer rounded once.
+ *   An all-zero window gives zeros.  A window that holds a non-finite sample, or whose Jacobi sweeps did not converge within their fixed bound, gives quiet NaN for
+ *   all of its hop outputs and is counted.
+ * GR4HIP_INVALID_ARGUMENT, checked on the host before any device work: a non-finite or negative relative_threshold or absolute_threshold, a non-finite
+ * energy_fraction, a hop_fraction that is not finite or outside [0, 1] (hop > W: the reference copies past its window, :178), hankel_rows > W (the reference's
+ * hankel() throws), an unknown dtype, d_in and d_out overlapping (a later window reads inputs an earlier window's outputs would have overwritten).
+ * GR4HIP_UNSUPPORTED from check / create / set_params: W > GR4HIP_SVDDENOISE_MAX_WINDOW for float / double, W > GR4HIP_SVDDENOISE_MAX_WINDOW_COMPLEX for the
+ * complex types (the matrix lives in LDS with one lane per column); the caller keeps its CPU path.
+ * set_params is setParameters (:221-229), which resets; reset is reset() (:204-212): the history is zeros again and nothing is pending.  Both are host-side notes
+ * applied by the next process call on its stream.  process queues one launch and returns without waiting for it; n_out == n_in, n_in == 0 is OK.  The handle
+ * carries the last W - 1 inputs and the outputs of the current hop on the device, and the position within the hop on the host.
+ * stats: windows started since create (host count) and, of those, the ones that gave NaN (device counter): it queues a copy behind the handle's last process call,
+ * on that call's stream, into page-locked memory and waits for that stream only. */
+#define GR4HIP_SVDDENOISE_MAX_WINDOW 128
+#define GR4HIP_SVDDENOISE_MAX_WINDOW_COMPLEX 64
+typedef struct gr4hip_svddenoise gr4hip_svddenoise_t;
+typedef struct {
+    int      dtype;              /* GR4HIP_F32, GR4HIP_F64, GR4HIP_C32 or GR4HIP_C64 (SvdDenoiser.hpp:12) */
+    size_t   window_size;        /* (:37) */
+    size_t   hankel_rows;        /* (:38) 0: window_size / 2 */
+    uint64_t max_rank;           /* (:39) */
+    double   relative_threshold; /* (:41) converted to RealT */
+    double   absolute_threshold; /* (:44) converted to RealT */
+    double   energy_fraction;    /* (:47) converted to RealT */
+    double   hop_fraction;       /* (:50) converted to RealT */
+} gr4hip_svddenoise_params;
+int    gr4hip_svddenoise_params_default(gr4hip_svddenoise_params* p, int dtype); /* (:37-51) 64, 0, max, eps(RealT), eps(RealT), 1, 0.25: the thresholds depend on dtype */
+int    gr4hip_svddenoise_check(const gr4hip_svddenoise_params* p);               /* host only: the validation of create */
+size_t gr4hip_svddenoise_windows_per_group(void);                                /* windows per workgroup of the built library (1: one wave per window) */
+int    gr4hip_svddenoise_create(gr4hip_svddenoise_t** h, const gr4hip_svddenoise_params* p);   /* the block's start() (:69-74) */
+int    gr4hip_svddenoise_set_params(gr4hip_svddenoise_t* h, const gr4hip_svddenoise_params* p); /* settingsChanged (:76-86) -> setParameters: a reset */
+int    gr4hip_svddenoise_reset(gr4hip_svddenoise_t* h);                                          /* reset() (:88) */
+int    gr4hip_svddenoise_process(gr4hip_svddenoise_t* h, const void* d_in, size_t n_in, void* d_out, gr4hip_stream_t stream); /* processOne (:90) per sample */
+int    gr4hip_svddenoise_stats(gr4hip_svddenoise_t* h, unsigned long long* windows, unsigned long long* not_converged);
+int    gr4hip_svddenoise_sweeps(gr4hip_svddenoise_t* h, unsigned long long* sweeps); /* Jacobi sweeps of all windows since create (as stats: waits for the handle's stream) */
+int    gr4hip_svddenoise_destroy(gr4hip_svddenoise_t* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,145 @@
+"""SvdDenoiser on the host side: gr4hip_svddenoise_check's validation (the same as create's, before any device work), the defaults, the window limits, the
+exported symbols, the plugin's four registered names with the reference's members (gnuradio4_amd/host/tests/test_host_svd_denoiser.cpp), the loud failure of
+the device-only block without a GPU and in the host domain, and -- on the GPU -- the C++ block in a graph source -> denoiser -> sink against the oracle."""
+import ctypes as C
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import oracle_lib as O
+import svd_denoiser_oracle as SV
+
+ROOT = O.ROOT
+BIN = os.path.join(ROOT, "build", "host", "test_host_svd_denoiser")
+PLUGIN = os.path.join(ROOT, "gnuradio4_amd", "libgr4hip_blocks.so")
+DTYPES = {"f32": 8, "f64": 9, "c32": 10, "c64": 11}  # GR4HIP_F32 ... GR4HIP_C64
+
+
+@pytest.fixture(scope="module")
+def L():
+    from gnuradio4_amd import capi
+    return capi.lib()
+
+
+@pytest.fixture(scope="module")
+def prog():
+    subprocess.check_call(["bash", os.path.join(ROOT, "gnuradio4_amd", "host", "build.sh")], stdout=subprocess.DEVNULL)
+    return BIN
+
+
+def _params(L, base="f32", **kw):
+    from gnuradio4_amd import capi
+    p = capi.SvdDenoiseParams()
+    assert L.gr4hip_svddenoise_params_default(C.byref(p), DTYPES[base]) == 0
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+@pytest.mark.parametrize("dtype", list(DTYPES))
+def test_defaults_are_the_blocks(L, dtype):
+    from gnuradio4_amd import capi
+    assert (capi.F32, capi.F64, capi.C32, capi.C64) == (8, 9, 10, 11)
+    p = _params(L, dtype)
+    d = SV.defaults(dtype)  # SvdDenoiser.hpp:37-51
+    assert p.dtype == DTYPES[dtype]
+    for k, v in d.items():
+        assert getattr(p, k) == v, k
+    assert L.gr4hip_svddenoise_check(C.byref(p)) == 0
+    assert L.gr4hip_svddenoise_params_default(C.byref(p), 7) == capi.INVALID_ARGUMENT
+    assert L.gr4hip_svddenoise_params_default(None, 8) == capi.INVALID_ARGUMENT
+
+
+@pytest.mark.parametrize("kw", [dict(relative_threshold=-1e-9), dict(relative_threshold=math.nan), dict(relative_threshold=math.inf), dict(absolute_threshold=-1.0),
+                                dict(absolute_threshold=math.nan), dict(absolute_threshold=math.inf), dict(energy_fraction=math.nan), dict(energy_fraction=-math.inf),
+                                dict(hop_fraction=math.nan), dict(hop_fraction=math.inf), dict(hop_fraction=-0.01), dict(hop_fraction=1.0001),
+                                dict(window_size=32, hankel_rows=33), dict(window_size=0, hankel_rows=3), dict(dtype=0), dict(dtype=7), dict(dtype=12), dict(dtype=99)])
+def test_every_rejection_before_device_work(L, kw):
+    from gnuradio4_amd import capi
+    for dtype in ("f32", "c64"):
+        p = _params(L, dtype, **kw)
+        assert L.gr4hip_svddenoise_check(C.byref(p)) == capi.INVALID_ARGUMENT, kw
+        h = C.c_void_p()
+        assert L.gr4hip_svddenoise_create(C.byref(h), C.byref(p)) == capi.INVALID_ARGUMENT and not h.value
+    assert L.gr4hip_svddenoise_check(None) == capi.INVALID_ARGUMENT
+
+
+def test_what_the_reference_takes_is_taken(L):
+    for kw in (dict(window_size=0), dict(window_size=1), dict(window_size=2), dict(hop_fraction=0.0), dict(hop_fraction=1.0), dict(energy_fraction=-1.0),
+               dict(energy_fraction=7.0), dict(relative_threshold=0.0, absolute_threshold=0.0), dict(max_rank=0), dict(window_size=32, hankel_rows=32),
+               dict(window_size=32, hankel_rows=1), dict(window_size=2, hankel_rows=2)):
+        for dtype in DTYPES:
+            assert L.gr4hip_svddenoise_check(C.byref(_params(L, dtype, **kw))) == 0, (kw, dtype)
+
+
+def test_windows_beyond_the_limits_are_unsupported(L):
+    from gnuradio4_amd import capi
+    assert (capi.SVDDENOISE_MAX_WINDOW, capi.SVDDENOISE_MAX_WINDOW_COMPLEX) == (128, 64)
+    hdr = open(os.path.join(ROOT, "include", "gr4hip.h")).read()
+    assert "#define GR4HIP_SVDDENOISE_MAX_WINDOW 128\n" in hdr and "#define GR4HIP_SVDDENOISE_MAX_WINDOW_COMPLEX 64\n" in hdr
+    for dtype, limit in (("f32", 128), ("f64", 128), ("c32", 64), ("c64", 64)):
+        assert L.gr4hip_svddenoise_check(C.byref(_params(L, dtype, window_size=limit))) == 0
+        assert L.gr4hip_svddenoise_check(C.byref(_params(L, dtype, window_size=limit, hankel_rows=1))) == 0
+        for W in (limit + 1, 4096):
+            p = _params(L, dtype, window_size=W)
+            assert L.gr4hip_svddenoise_check(C.byref(p)) == capi.UNSUPPORTED
+            h = C.c_void_p()
+            assert L.gr4hip_svddenoise_create(C.byref(h), C.byref(p)) == capi.UNSUPPORTED and not h.value
+            assert "window_size" in L.gr4hip_last_error().decode()
+    # an invalid setting is reported as such, whatever the window
+    assert L.gr4hip_svddenoise_check(C.byref(_params(L, "f32", window_size=4096, hop_fraction=2.0))) == capi.INVALID_ARGUMENT
+
+
+def test_symbols_and_python_names(L):
+    import gnuradio4_amd as G
+    for name in ("params_default", "check", "windows_per_group", "create", "set_params", "reset", "process", "stats", "sweeps", "destroy"):
+        assert hasattr(L, f"gr4hip_svddenoise_{name}")
+    assert "SvdDenoiser" in G.__all__
+    assert G.SvdDenoiser.windows_per_group() == int(L.gr4hip_svddenoise_windows_per_group()) >= 1
+    assert G.SvdDenoiser._names == tuple(SV.defaults("f32"))
+
+
+def test_plugin_makes_the_four_types_with_the_references_members(prog):
+    r = subprocess.run([prog, PLUGIN, "host"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "all checks passed (compute_domain host)" in r.stdout
+    assert "169 registrations" in open(os.path.join(ROOT, "INTEGRATION.md")).read()
+
+
+# ------------------------------------------------------------------------------------------------ the graphs
+def test_host_domain_fails_loudly(prog, tmp_path):
+    np.array(SV.case("A", "f32")[0]).tofile(tmp_path / "x.f32")
+    r = subprocess.run([prog, PLUGIN, "host", str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 3, (r.returncode, r.stdout, r.stderr)
+    assert "device-only" in r.stderr
+
+
+def test_device_block_fails_loudly_without_gpu(prog, tmp_path):
+    import torch
+    if torch.cuda.is_available():
+        return  # (with a device the same command is test_graphs_on_the_device)
+    np.array(SV.case("A", "f32")[0]).tofile(tmp_path / "x.f32")
+    r = subprocess.run([prog, PLUGIN, "gpu:hip:0", str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 3, (r.returncode, r.stdout, r.stderr)
+
+
+@pytest.mark.gpu
+def test_graphs_on_the_device(prog, tmp_path):
+    """source -> SvdDenoiser<float32> -> sink on gpu:hip:0 as a fresh child process with case A's input and settings: the outputs against the oracle on its settled
+    windows (1e-5 of the window's peak), and the same bits from calls of 50 samples as from large chunks"""
+    x, want = SV.case("A", "f32")
+    np.array(x).tofile(tmp_path / "x.f32")
+    r = subprocess.run([prog, PLUGIN, "gpu:hip:0", str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    print(r.stdout)
+    calls = {line.split(":")[0]: int(line.split(" samples, ")[1].split(" device calls")[0]) for line in r.stdout.splitlines() if " device calls" in line}
+    whole, small = (np.fromfile(tmp_path / f"{g}.f32", np.float32) for g in ("whole", "small"))
+    assert whole.size == small.size == x.size
+    assert np.array_equal(whole.view(np.int32), small.view(np.int32))
+    assert calls["small"] >= x.size // 50 > calls["whole"]
+    m = want.mask()
+    err = np.abs(whole.astype(np.float64) - want.y) / np.maximum(want.peak(), 1e-300)
+    assert err[m].max() <= 1e-5
