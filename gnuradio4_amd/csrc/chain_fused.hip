@@ -153,17 +153,13 @@ __device__ __forceinline__ int addrA(int row, int col) { return row * kRowA + co
 
 // pass B (p = 32, radix 16): butterfly (c, k) gathers S1[k][c + 16 r], twiddles by W_512^{r k}, scatters to S2[c][32 q + k]
 __device__ __forceinline__ void passB_compute_store(float2* S, float2 (&w)[16], const float2 (&tw)[16], int c, int k) {
-#pragma unroll
-    for (int r = 1; r < 16; ++r) w[r] = cmul(w[r], tw[r]);
-    fft16<1>(w);
+    fft16_tw<1>(w, tw);
 #pragma unroll
     for (int q = 0; q < 16; ++q) S[c * kRowB + 32 * q + k] = w[perm16(q)];
 }
 // same, twiddles from an LDS table [16][32] (the windowed kernel has no registers left for a resident set)
 __device__ __forceinline__ void passB_table_store(float2* S, float2 (&w)[16], const float2* twl, int c, int k) {
-#pragma unroll
-    for (int r = 1; r < 16; ++r) w[r] = cmul(w[r], twl[r * 32 + k]);
-    fft16<1>(w);
+    fft16_tw<1>(w, [&](int r) { return twl[r * 32 + k]; });
 #pragma unroll
     for (int q = 0; q < 16; ++q) S[c * kRowB + 32 * q + k] = w[perm16(q)];
 }
@@ -171,9 +167,7 @@ __device__ __forceinline__ void passB_table_store(float2* S, float2 (&w)[16], co
 __device__ __forceinline__ void passC(const float2* S, float2 (&g)[16], const float2 (&tw)[16], int i3) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) g[r] = S[r * kRowB + i3];
-#pragma unroll
-    for (int r = 1; r < 16; ++r) g[r] = cmul(g[r], tw[r]);
-    fft16<1>(g);
+    fft16_tw<1>(g, tw);
 }
 
 // phase fence: keeps hipcc's scheduler from overlapping independent phases (which costs more registers than the 128 a lane has
@@ -690,16 +684,16 @@ __device__ __forceinline__ void chain_fd_body(ChainFdArgs& a, const ChainFdMulti
         }                                                                                   \
     } while (0)
             // ---- X pass B: twiddles W_512^{r k}, 16-point DFT, scatter to S2[c][32 q + k]
-#pragma unroll
-            for (int g = 0; g < 5; ++g) {
-                GR4_MF(g);
-#pragma unroll
-                for (int r = 3 * g + 1; r < 3 * g + 4; ++r) w[r] = cmul(w[r], WIN ? twBl[r * 32 + kb] : twBr[r]);
-            }
+            // (the twiddles ride in the first butterflies, fft16_tw: slot 0 the three plain products, then two slots per butterfly)
+            auto twB = [&](int r) { return WIN ? twBl[r * 32 + kb] : twBr[r]; };
+            GR4_MF(0);
+            fft16_tw_pre<1>(w, twB);
 #pragma unroll
             for (int n2 = 0; n2 < 4; ++n2) {
-                GR4_MF(5 + n2);
-                fft16_s1<1>(w, n2);
+                GR4_MF(1 + 2 * n2);
+                fft16_tw_s1a<1>(w, twB, n2);
+                GR4_MF(2 + 2 * n2);
+                fft16_tw_s1b<1>(w, twB, n2);
             }
             GR4_MF(9);
             fft16_twa<1>(w);

@@ -75,6 +75,47 @@ __device__ __forceinline__ void fft16(float2* v) {
     for (int k1 = 0; k1 < 4; ++k1) fft16_s2<ST>(v, k1);
 }
 
+// fft16 behind a twiddle layer: the 16-point DFT of tw(r) v[r ST] (r = 1 .. 15, slot 0 untwiddled) from the UNtwiddled values.  A first-step butterfly needs the sum and
+// the difference of a twiddled pair, a' +- w b: the product then the two sums are 4 + 4 instructions; s = a' + w b as two fma chains and d = 2 a' - s are 4 + 2 (one more
+// rounding in d: eps |s| instead of eps |d|).  Both pairs of each of the four first-step butterflies: 16 instructions fewer per transform.  tw(r) is called once per r,
+// where the product is formed (a register array or a table read).  The steps, callable in pieces like fft16's (the fused pass B interleaves them with MFMA issues):
+//   fft16_tw_pre, then fft16_tw_s1a(n2), fft16_tw_s1b(n2) for n2 = 0 .. 3, then fft16_twa, fft16_twb, fft16_s2(k1) as in fft16
+__device__ __forceinline__ float2 cmuladd(float2 b, float2 w, float2 a) { return make_float2(fmaf(b.x, w.x, fmaf(-b.y, w.y, a.x)), fmaf(b.x, w.y, fmaf(b.y, w.x, a.y))); } // a + w b
+__device__ __forceinline__ float2 twice_minus(float2 a, float2 s) { return make_float2(fmaf(2.0f, a.x, -s.x), fmaf(2.0f, a.y, -s.y)); }                                   // 2 a - s
+template <int ST, typename TW>
+__device__ __forceinline__ void fft16_tw_pre(float2* v, TW&& tw) { // the `a` of the pairs (n2, n2 + 8), n2 = 1 .. 3
+#pragma unroll
+    for (int r = 1; r < 4; ++r) v[r * ST] = cmul(v[r * ST], tw(r));
+}
+template <int ST, typename TW>
+__device__ __forceinline__ void fft16_tw_s1a(float2* v, TW&& tw, int n2) { // pair (n2, n2 + 8) -> t0, t1 of bfly4 in place; slot n2 + 4 twiddled
+    const float2 a = v[n2 * ST], s = cmuladd(v[(n2 + 8) * ST], tw(n2 + 8), a);
+    v[n2 * ST]       = s;
+    v[(n2 + 8) * ST] = twice_minus(a, s);
+    v[(n2 + 4) * ST] = cmul(v[(n2 + 4) * ST], tw(n2 + 4));
+}
+template <int ST, typename TW>
+__device__ __forceinline__ void fft16_tw_s1b(float2* v, TW&& tw, int n2) { // pair (n2 + 4, n2 + 12) -> t2, t3, then the second half of bfly4
+    const float2 t0 = v[n2 * ST], t1 = v[(n2 + 8) * ST], c = v[(n2 + 4) * ST];
+    const float2 t2 = cmuladd(v[(n2 + 12) * ST], tw(n2 + 12), c), t3 = mulmi(twice_minus(c, t2));
+    v[n2 * ST] = cadd(t0, t2); v[(n2 + 8) * ST] = csub(t0, t2); v[(n2 + 4) * ST] = cadd(t1, t3); v[(n2 + 12) * ST] = csub(t1, t3);
+}
+template <int ST, typename TW>
+__device__ __forceinline__ void fft16_tw(float2* v, TW&& tw) {
+    fft16_tw_pre<ST>(v, tw);
+#pragma unroll
+    for (int n2 = 0; n2 < 4; ++n2) {
+        fft16_tw_s1a<ST>(v, tw, n2);
+        fft16_tw_s1b<ST>(v, tw, n2);
+    }
+    fft16_twa<ST>(v);
+    fft16_twb<ST>(v);
+#pragma unroll
+    for (int k1 = 0; k1 < 4; ++k1) fft16_s2<ST>(v, k1);
+}
+template <int ST>
+__device__ __forceinline__ void fft16_tw(float2* v, const float2 (&tw)[16]) { fft16_tw<ST>(v, [&](int r) { return tw[r]; }); }
+
 // multiply v[r] by b^r (r = 1..15) given the table values b^1 and b^2
 __device__ __forceinline__ void apply_powers(float2 (&v)[16], float2 b1, float2 b2) {
     // two interleaved chains (odd / even powers) stepping by b^2: 14 multiplies, only three powers live at any time
@@ -92,9 +133,11 @@ __device__ __forceinline__ void apply_powers(float2 (&v)[16], float2 b1, float2 
     }
 }
 
-// value of the neighbouring lane (lane ^ 1) through DPP quad_perm [1,0,3,2]: no LDS traffic
+// value of the neighbouring lane (lane ^ 1) through DPP quad_perm [1,0,3,2]: no LDS traffic.  bound_ctrl = true: a quad_perm under full row and bank masks reads a
+// valid lane of the own quad in every lane, so the `old` operand is never what comes out -- with bound_ctrl = false hipcc still has to build it (a v_mov_b32 vN, 0 in
+// front of every v_mov_b32_dpp, one per exchanged component), with true it does not
 __device__ __forceinline__ float lane_xor1(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));
 }
 
 // W_32^k = (cos(2 pi k / 32), -sin(2 pi k / 32)); k is a compile-time constant after unrolling, so the switch folds
