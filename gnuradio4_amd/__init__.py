@@ -5,9 +5,9 @@ libgr4hip.so (include/gr4hip.h).  torch is used only for device memory, streams 
 """
 from . import capi  # noqa: F401
 from .blocks import (FFT, BasicDecimatingFilter, BasicFilter, Chain, Decimator, FirBatched, FrequencyEstimatorFrequencyDomain, FrequencyEstimatorTimeDomain, IQDemodulator,
-                     Merged, PowerMetrics, Rotator, SchmittEdges, SchmittTrigger, SvdDenoiser, fir_filter, fir_interpolator, iir_filter,  # noqa: F401
+                     Merged, PowerMetrics, Rotator, SchmittEdges, SchmittTrigger, SignalGenerator, SvdDenoiser, fir_filter, fir_interpolator, iir_filter,  # noqa: F401
                      math_const, math_nary, synth_c32, synth_draws, synth_f32)
 
 __all__ = ["capi", "fir_filter", "fir_interpolator", "iir_filter", "BasicFilter", "BasicDecimatingFilter", "Decimator", "FirBatched", "FFT", "Chain", "Merged", "Rotator",
-           "FrequencyEstimatorTimeDomain", "FrequencyEstimatorFrequencyDomain", "IQDemodulator", "PowerMetrics", "SchmittTrigger", "SchmittEdges", "SvdDenoiser",
+           "FrequencyEstimatorTimeDomain", "FrequencyEstimatorFrequencyDomain", "IQDemodulator", "PowerMetrics", "SchmittTrigger", "SchmittEdges", "SvdDenoiser", "SignalGenerator",
            "math_const", "math_nary", "synth_c32", "synth_draws", "synth_f32"]

@@ -1032,6 +1032,75 @@ class SvdDenoiser(_Handle):
         return int(s.value)
 
 
+class SignalGenerator(_Handle):
+    """gr::basic::SignalGenerator<T> (blocks/basic/.../SignalGenerator.hpp:25-87) as a device source for T in {float32, float64, complex64, int16}: sample n is what
+    the n-th generateSample() of the reference's core returns, whatever the cutting into calls (include/gr4hip.h "Signal generator", SIGNAL_GENERATOR.md).
+    `signal_type`: one of capi.SIGGEN_TYPES or its number.  configure is settingsChanged (noise re-seeded, phasor restarted, time keeps running); reset also
+    zeroes the time."""
+    _destroy = "gr4hip_siggen_destroy"
+    _names = ("signal_type", "sample_rate", "frequency", "amplitude", "offset", "phase", "seed")
+    _dtypes = {torch.float32: capi.F32, torch.float64: capi.F64, torch.complex64: capi.C32, torch.int16: capi.I16}
+
+    def __init__(self, signal_type="Sin", dtype=torch.float32, sample_rate=1000., frequency=1., amplitude=1., offset=0., phase=0., seed=0):
+        super().__init__()
+        if dtype not in self._dtypes:
+            raise capi.Gr4HipError(capi.UNSUPPORTED, "SignalGenerator", f"dtype {dtype} (float32, float64, complex64, int16)")
+        self.dtype = dtype
+        self._p = self._params(capi.SigGenParams(self._dtypes[dtype], 1, 1000., 1., 1., 0., 0., 0),
+                               dict(signal_type=signal_type, sample_rate=sample_rate, frequency=frequency, amplitude=amplitude, offset=offset, phase=phase, seed=seed))
+        check(lib().gr4hip_siggen_create(C.byref(self._h), C.byref(self._p)), "SignalGenerator")
+
+    @staticmethod
+    def run() -> int:
+        """consecutive samples one lane generates"""
+        return int(lib().gr4hip_siggen_run())
+
+    @staticmethod
+    def tile() -> int:
+        """samples of one workgroup: where the generator's start states change hands"""
+        return int(lib().gr4hip_siggen_tile())
+
+    def _params(self, p, settings):
+        for k, v in settings.items():
+            if k not in self._names:
+                raise TypeError(f"SignalGenerator: unknown setting '{k}'")
+            if k == "signal_type":
+                if isinstance(v, str):
+                    if v not in capi.SIGGEN_TYPES:
+                        raise ValueError(f"SignalGenerator: unknown signal type '{v}'")
+                    v = capi.SIGGEN_TYPES.index(v)
+                p.signal_type = int(v)
+            elif k == "seed":
+                p.seed = int(v) & 0xFFFFFFFFFFFFFFFF
+            else:
+                setattr(p, k, float(v))
+        return p
+
+    def __getattr__(self, name):
+        if name in type(self)._names:
+            v = getattr(self.__dict__["_p"], name)
+            return capi.SIGGEN_TYPES[v] if name == "signal_type" else v
+        raise AttributeError(name)
+
+    def configure(self, **settings):
+        p = self._params(capi.SigGenParams.from_buffer_copy(self._p), settings)
+        check(lib().gr4hip_siggen_configure(self._h, C.byref(p)), "SignalGenerator.configure")
+        self._p = p
+
+    def reset(self):
+        check(lib().gr4hip_siggen_reset(self._h), "SignalGenerator.reset")
+
+    def generate_into(self, out: torch.Tensor) -> torch.Tensor:
+        """the next out.numel() samples into `out` (a contiguous 1-D device tensor of the handle's dtype), on the current stream; returns without waiting"""
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dim() != 1 or out.dtype != self.dtype or not out.is_contiguous():
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "SignalGenerator", f"out must be a contiguous 1-D {self.dtype} device tensor")
+        check(lib().gr4hip_siggen_process(self._h, out.data_ptr(), out.numel(), _stream()), "SignalGenerator.generate")
+        return out
+
+    def generate(self, n: int, device="cuda") -> torch.Tensor:
+        return self.generate_into(torch.empty(int(n), dtype=self.dtype, device=device))
+
+
 def synth_c32(n: int, seed: int = 42, tone_frel: float = 0.1, tone_amp: float = 1.0, noise_amp: float = 1.0, device="cuda") -> torch.Tensor:
     out = torch.empty(n, dtype=torch.complex64, device=device)
     check(lib().gr4hip_synth_c32(out.data_ptr(), n, seed, tone_frel, tone_amp, noise_amp, _stream()), "synth_c32")

@@ -202,6 +202,16 @@ SIGNATURES = {
     "gr4hip_svddenoise_stats": (_i, [_vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "gr4hip_svddenoise_sweeps": (_i, [_vp, C.POINTER(C.c_ulonglong)]),
     "gr4hip_svddenoise_destroy": (_i, [_vp]),
+    "gr4hip_siggen_check": (_i, [_vp]),
+    "gr4hip_siggen_create": (_i, [_pvp, _vp]),
+    "gr4hip_siggen_configure": (_i, [_vp, _vp]),
+    "gr4hip_siggen_reset": (_i, [_vp]),
+    "gr4hip_siggen_process": (_i, [_vp, _vp, _sz, _vp]),
+    "gr4hip_siggen_destroy": (None, [_vp]),
+    "gr4hip_siggen_run": (_sz, []),
+    "gr4hip_siggen_tile": (_sz, []),
+    "gr4hip_siggen_jump_host": (_i, [C.POINTER(C.c_ulonglong), C.c_ulonglong, C.POINTER(C.c_ulonglong)]),
+    "gr4hip_siggen_time_host": (_i, [_i, _f, C.c_ulonglong, _sz, C.POINTER(C.c_double)]),
 }
 
 class FilterParams(C.Structure):
@@ -246,6 +256,15 @@ class SvdDenoiseParams(C.Structure):
     """gr4hip_svddenoise_params: the sample type and the seven settings of gr::filter::SvdDenoiser<T> (SvdDenoiser.hpp:37-51)"""
     _fields_ = [("dtype", _i), ("window_size", C.c_size_t), ("hankel_rows", C.c_size_t), ("max_rank", C.c_uint64), ("relative_threshold", _d),
                 ("absolute_threshold", _d), ("energy_fraction", _d), ("hop_fraction", _d)]
+
+
+SIGGEN_TYPES = ["Const", "Sin", "Cos", "Square", "Saw", "Triangle", "FastSin", "FastCos", "UniformNoise", "TriangularNoise", "GaussianNoise"]
+
+
+class SigGenParams(C.Structure):
+    """gr4hip_siggen_params: the sample type and the settings of gr::basic::SignalGenerator<T> (SignalGenerator.hpp:40-47)"""
+    _fields_ = [("dtype", _i), ("signal_type", _i), ("sample_rate", _f), ("frequency", _f), ("amplitude", _f), ("offset", _f), ("phase", _f),
+                ("seed", C.c_ulonglong)]
 
 
 LOWPASS, HIGHPASS, BANDPASS, BANDSTOP = range(4)

@@ -36,6 +36,7 @@ enum DevSwitch {
     kDevFirNoDecimF16,        // GR4HIP_FIR_NO_DECIM_F16: the frequency-domain decimate-by-8 kernel where the default takes the f16 band-form one (fir_decim_f16.hip)
     kDevFftBluesteinGeneric,  // GR4HIP_FFT_BLUESTEIN_GENERIC: the chirp convolution on the run-time radix-8 passes (one frame per workgroup) instead of the compile-time 16 x 16 x R3 plan
     kDevFftFourStep64k,       // GR4HIP_FFT_FOUR_STEP_64K: 65536-point transforms through the three-kernel four-step pipeline instead of the two-kernel 256 x 256 form
+    kDevSiggenGaussPermille,  // GR4HIP_SIGGEN_GAUSS_PERMILLE: an integer; non-zero: the Gaussian signal generator launches this many attempts per 1000 needed pairs (0: its own formula); the tests reach the tail kernel with it
     kDevSwitchCount
 };
 int dev_switch(DevSwitch s);

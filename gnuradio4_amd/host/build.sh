@@ -31,5 +31,6 @@ if stale $OUT/test_host_iq_demod tests/test_host_iq_demod.cpp; then $CXX -O2 tes
 if stale $OUT/test_host_power_metrics tests/test_host_power_metrics.cpp; then $CXX -O2 tests/test_host_power_metrics.cpp -o $OUT/test_host_power_metrics -ldl & pids+=($!); fi
 if stale $OUT/test_host_schmitt_trigger tests/test_host_schmitt_trigger.cpp; then $CXX -O2 tests/test_host_schmitt_trigger.cpp -o $OUT/test_host_schmitt_trigger -ldl & pids+=($!); fi
 if stale $OUT/test_host_svd_denoiser tests/test_host_svd_denoiser.cpp; then $CXX -O2 tests/test_host_svd_denoiser.cpp -o $OUT/test_host_svd_denoiser -ldl & pids+=($!); fi
+if stale $OUT/test_host_signal_generator tests/test_host_signal_generator.cpp; then $CXX -O2 tests/test_host_signal_generator.cpp -o $OUT/test_host_signal_generator $LINK & pids+=($!); fi
 for p in "${pids[@]}"; do wait $p; done
 echo "built $(realpath $OUT)"

@@ -160,6 +160,8 @@ struct SignalGenerator : Block<SignalGenerator<T>> {
     std::size_t                _count = 0;
     signal_generator::Noise<F> _noise;
     bool                       _configured = false;
+    bool                       _device_configure = false, _device_reset = false; // compute_domain gpu:hip: what the device handle has not been told yet
+    std::size_t                _device_calls = 0;
 
     void configure() {
         using signal_generator::Type;
@@ -175,9 +177,18 @@ struct SignalGenerator : Block<SignalGenerator<T>> {
         _count   = 0;
         _noise.seed(seed);
         _configured = true;
+        _device_configure = true;
     }
     void settingsChanged(const property_map&, const property_map&) { configure(); } // (the time base keeps running across a settings change, as upstream)
-    void reset() { _t = 0; configure(); }
+    void reset() { _t = 0; configure(); _device_reset = true; }
+    [[nodiscard]] gr4hip_siggen_params params() const {
+        int dtype = GR4HIP_F64;
+        if constexpr (std::is_same_v<T, float>) dtype = GR4HIP_F32;
+        else if constexpr (std::is_same_v<T, std::complex<float>>) dtype = GR4HIP_C32;
+        else if constexpr (std::is_same_v<T, std::int16_t>) dtype = GR4HIP_I16;
+        else if constexpr (!std::is_same_v<T, double>) dtype = -1; // no device implementation: gr4hip_siggen_check refuses it
+        return gr4hip_siggen_params{dtype, static_cast<int>(signal_type), sample_rate, frequency, amplitude, offset, phase, seed};
+    }
 
     [[nodiscard]] F tone() const {
         using signal_generator::Type;
@@ -251,7 +262,16 @@ struct SignalGenerator : Block<SignalGenerator<T>> {
         if (n_samples_max) n = std::min<std::size_t>(n, n_samples_max - _n);
         if (n == 0) return {requested, 0, work::Status::INSUFFICIENT_OUTPUT_ITEMS};
         auto span = out.buffer->write_span(n);
-        for (std::size_t i = 0; i < n; ++i) span[i] = generateSample();
+        if (this->_domain.is_device()) { // the chunk is generated in HBM (gr4hip_siggen_process, gr4/hip.hpp) and copied to this edge: never a silent host fallback
+            if constexpr (hip::HasKernel<SignalGenerator>) {
+                if (hip::Kernel<SignalGenerator>::generate(*this, span.data(), n) != work::Status::OK) return {requested, 0, work::Status::ERROR};
+            } else {
+                this->_log("SignalGenerator: compute_domain '" + this->compute_domain + "' needs gr4/hip.hpp");
+                return {requested, 0, work::Status::ERROR};
+            }
+        } else {
+            for (std::size_t i = 0; i < n; ++i) span[i] = generateSample();
+        }
         out.buffer->publish(n);
         _n += n;
         return {requested, n, work::Status::OK};

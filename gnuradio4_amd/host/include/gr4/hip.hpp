@@ -1072,6 +1072,43 @@ struct Kernel<gr::filter::SvdDenoiser<T>> {
     }
 };
 
+// SignalGenerator<T> (a source: its customWork comes here with the span of its CPU-domain edge): the chunk is generated in HBM by gr4hip_siggen_process and copied
+// to the edge.  The handle is made at the first chunk -- start(): configure + reset (SignalGenerator.hpp:57-61) -- and told of every later settingsChanged / reset
+// in front of the chunk that follows it.  The values are those of the host body (FastSin / FastCos: the closed-form phasor, include/gr4hip.h).
+template <typename T>
+struct Kernel<gr::basic::SignalGenerator<T>> {
+    using B = gr::basic::SignalGenerator<T>;
+    struct State final : Offload {
+        gr4hip_siggen_t* h = nullptr;
+        ~State() override { if (h) gr4hip_siggen_destroy(h); }
+    };
+    static work::Status generate(B& blk, T* host, std::size_t n) {
+        try {
+            State*     st = offload_state<State>(blk);
+            const auto p  = blk.params();
+            if (!st->h) {
+                check(gr4hip_siggen_create(&st->h, &p), "gr4hip_siggen_create");
+            } else {
+                if (blk._device_configure) check(gr4hip_siggen_configure(st->h, &p), "gr4hip_siggen_configure");
+                if (blk._device_reset) check(gr4hip_siggen_reset(st->h), "gr4hip_siggen_reset");
+            }
+            blk._device_configure = blk._device_reset = false;
+            ++blk._device_calls;
+            const std::size_t bytes = n * sizeof(T);
+            char*             dout  = static_cast<char*>(st->d_out.ensure(bytes));
+            check(gr4hip_siggen_process(st->h, dout, n, nullptr), "gr4hip_siggen_process");
+            char* hout = static_cast<char*>(st->h_out.ensure(bytes));
+            check(gr4hip_memcpy_d2h(hout, dout, bytes, nullptr), "d2h");
+            check(gr4hip_stream_synchronize(nullptr), "sync");
+            std::memcpy(host, hout, bytes);
+            return work::Status::OK;
+        } catch (const std::exception& e) {
+            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
+            return work::Status::ERROR; // never a silent host fallback
+        }
+    }
+};
+
 // ---- merged blocks (gr4/merge.hpp): the parts of a Merge<> become stages of one block; intermediates stay in HBM
 struct SeqStage final : Stage {
     std::unique_ptr<Stage> a, b;
@@ -1666,6 +1703,67 @@ struct D2H : Block<D2H<T>> {
             this->_log(std::string("D2H failed: ") + e.what());
             return work::Status::ERROR;
         }
+    }
+};
+
+// gr::basic::SignalGenerator<T> with a GPU-domain output port: the samples are generated straight into the device ring's write span (gr4hip_siggen_process on the
+// span's device pointer) -- no copy, no staging -- and a block with a GPU-domain input behind it reads them where they were written.  Settings as
+// SignalGenerator<T> (SignalGenerator.hpp:40-47) plus the sample budget n_samples_max (0: free-running) and the device.
+template <typename T>
+struct SignalSource : Block<SignalSource<T>> {
+    PortOut<T, GPU>                       out;
+    gr::basic::signal_generator::Type     signal_type = gr::basic::signal_generator::Type::Sin;
+    float                                 sample_rate = 1000.f, frequency = 1.f, amplitude = 1.f, offset = 0.f, phase = 0.f;
+    std::uint64_t                         seed          = 0;
+    Size_t                                n_samples_max = 0;
+    Size_t                                device        = 0;
+    GR_MAKE_REFLECTABLE(SignalSource, out, signal_type, sample_rate, frequency, amplitude, offset, phase, seed, n_samples_max, device);
+    gr4hip_siggen_t* _h      = nullptr;
+    gr4hip_stream_t  _stream = nullptr;
+    bool             _configure = false;
+    std::size_t      _n = 0, _launches = 0;
+
+    SignalSource() = default;
+    SignalSource(const SignalSource&)            = delete;
+    SignalSource& operator=(const SignalSource&) = delete;
+    ~SignalSource() {
+        if (_h) gr4hip_siggen_destroy(_h);
+        if (_stream) gr4hip_stream_destroy(_stream);
+    }
+    [[nodiscard]] gr4hip_siggen_params params() const {
+        gr::basic::SignalGenerator<T> b;
+        b.signal_type = signal_type; b.sample_rate = sample_rate; b.frequency = frequency; b.amplitude = amplitude; b.offset = offset; b.phase = phase; b.seed = seed;
+        return b.params();
+    }
+    void settingsChanged(const property_map&, const property_map&) {
+        const auto p = params();
+        if (gr4hip_siggen_check(&p) != GR4HIP_OK) throw std::invalid_argument(std::string("SignalSource: ") + gr4hip_last_error());
+        _configure = true;
+    }
+    work::Result customWork(std::size_t requested) {
+        if (n_samples_max && _n >= n_samples_max) return {requested, 0, work::Status::DONE};
+        if (!out.connected()) return {requested, 0, work::Status::ERROR};
+        std::size_t n = std::min(out.buffer->free_space(), requested);
+        if (n_samples_max) n = std::min<std::size_t>(n, n_samples_max - _n);
+        if (n == 0) return {requested, 0, work::Status::INSUFFICIENT_OUTPUT_ITEMS};
+        try {
+            check(gr4hip_set_device(static_cast<int>(device)), "gr4hip_set_device");
+            if (!_stream) check(gr4hip_stream_create(&_stream), "gr4hip_stream_create");
+            const auto p = params();
+            if (!_h) check(gr4hip_siggen_create(&_h, &p), "gr4hip_siggen_create");
+            else if (_configure) check(gr4hip_siggen_configure(_h, &p), "gr4hip_siggen_configure");
+            _configure = false;
+            auto span = out.buffer->write_span(n); // device pointers, contiguous across the wrap
+            check(gr4hip_siggen_process(_h, span.data(), n, _stream), "gr4hip_siggen_process");
+            check(gr4hip_stream_synchronize(_stream), "sync"); // the span is published only once the samples are there
+            ++_launches;
+        } catch (const std::exception& e) {
+            this->_log(std::string("SignalSource failed: ") + e.what());
+            return {requested, 0, work::Status::ERROR};
+        }
+        out.buffer->publish(n);
+        _n += n;
+        return {requested, n, work::Status::OK};
     }
 };
 

@@ -54,6 +54,12 @@ void register_schmitt(BlockRegistry& r) { // basic/Trigger.hpp:11-13; SchmittTri
     r.insert<SchmittTriggerLinear<T>>(named<T>("gr::blocks::basic::SchmittTrigger"));
 }
 
+template <typename T>
+void register_signal_generator(BlockRegistry& r) { // basic/SignalGenerator.hpp:25 registers every fundamental type; the four with a device implementation are offered
+    r.insert<gr::basic::SignalGenerator<T>>(named<T>("gr::basic::SignalGenerator"));
+    r.insert<gr::hip::SignalSource<T>>(named<T>("gr::hip::SignalSource"));
+}
+
 const bool registered = [] {
     BlockRegistry& r = grPluginInstance();
     using namespace gr::filter;
@@ -89,6 +95,7 @@ const bool registered = [] {
     r.insert<SvdDenoiser<double>>(named<double>("gr::filter::SvdDenoiser"));
     r.insert<SvdDenoiser<std::complex<float>>>(named<std::complex<float>>("gr::filter::SvdDenoiser"));
     r.insert<SvdDenoiser<std::complex<double>>>(named<std::complex<double>>("gr::filter::SvdDenoiser"));
+    register_signal_generator<float>(r); register_signal_generator<double>(r); register_signal_generator<std::complex<float>>(r); register_signal_generator<std::int16_t>(r);
     r.insert<gr::blocks::fft::FFT<double, gr::DataSet<double>>>(named<double>("gr::blocks::fft::FFT"));
     r.insert<gr::blocks::fft::FFT<float>>(named<float>("gr::blocks::fft::FFT"));
     r.insert<gr::blocks::fft::FFT<std::complex<float>>>(named<std::complex<float>>("gr::blocks::fft::FFT"));

@@ -120,7 +120,8 @@ const char* gr4hip_last_error(void); /* thread-local text of the last failure */
  * Nothing here changes the meaning of a call -- choices that do (exact float32 FIR arithmetic, the rotator's phase recurrence, the chain's algorithm and
  * guard) are per-handle settings: gr4hip_fir_set_algo, gr4hip_rotator_set_algo, gr4hip_chain_create / gr4hip_chain_set_guard_mode.
  * Names: GR4HIP_FIR_NO_BF16X3, GR4HIP_FIR_NO_DECIM_FD, GR4HIP_IIR_THREE_PASS, GR4HIP_IIR_LOOKBACK, GR4HIP_IIR_NO_SPLIT, GR4HIP_IIR_SEQ_SLOTS (an integer), GR4HIP_FFT_BLUESTEIN_PIPELINE,
- * GR4HIP_FFT_NO_PIPELINE, GR4HIP_ROTATOR_LEAP, GR4HIP_ROTATOR_WALK, GR4HIP_CHAIN16, GR4HIP_FFT_SMOOTH_RUNTIME, GR4HIP_EWISE_NO_DIV_RCP. */
+ * GR4HIP_FFT_NO_PIPELINE, GR4HIP_ROTATOR_LEAP, GR4HIP_ROTATOR_WALK, GR4HIP_CHAIN16, GR4HIP_FFT_SMOOTH_RUNTIME, GR4HIP_EWISE_NO_DIV_RCP, GR4HIP_SIGGEN_GAUSS_PERMILLE (an integer:
+ * the attempts the Gaussian signal generator launches per 1000 needed pairs, 0 = its own formula; whatever it launches, the values are the same). */
 int gr4hip_developer_switch(const char* name, int value);
 const char* gr4hip_status_string(int status);
 int         gr4hip_device_count(int* count);
@@ -777,6 +778,57 @@ int    gr4hip_svddenoise_process(gr4hip_svddenoise_t* h, const void* d_in, size_
 int    gr4hip_svddenoise_stats(gr4hip_svddenoise_t* h, unsigned long long* windows, unsigned long long* not_converged);
 int    gr4hip_svddenoise_sweeps(gr4hip_svddenoise_t* h, unsigned long long* sweeps); /* Jacobi sweeps of all windows since create (as stats: waits for the handle's stream) */
 int    gr4hip_svddenoise_destroy(gr4hip_svddenoise_t* h);
+
+/* ------------------------------------------------------------------------------------------------ Signal generator (blocks/basic/.../SignalGenerator.hpp:25-87)
+ * gr::basic::SignalGenerator<T> as a device source for T in {float, double, complex<float>, int16}: sample n of the stream is what the n-th call of
+ * SignalGeneratorCore<T>::generateSample() returns (SignalGenerator.hpp:68-83; NOT the bulk fill() / fillComplex(), which round differently), whatever the cutting
+ * of the stream into calls.  Design notes and measured bounds: SIGNAL_GENERATOR.md.
+ *   compute type F (SignalGeneratorCore.hpp:27-41): double for the scalar types, float for complex<float>; the float settings are cast to F.
+ *   time (ToneGenerator.hpp:47,224-225): t_0 = 0, t_{n+1} = fl(t_n + fl(1 / sample_rate)) in F, reproduced exactly from a host-built table of linear segments that
+ *     covers 2^64 samples -- including the stall of F = float near n = 2^24 at 1 kHz, where the increment rounds to nothing.  Only tone samples advance it.
+ *   tones (:235-255; complex :77-102): Const, Sin, Cos, Square, Saw, Triangle evaluated in F operation by operation; frequency <= 0 makes every tone Const (:48).
+ *   FastSin / FastCos (:216-232): the reference multiplies a phasor by a rounded rotation once per sample and renormalises every 65536 samples.  DEVIATION: the device
+ *     evaluates the closed form of the same rounded constants in float64, |rot|^(k mod 65536) exp(j (arg p0 + k arg rot)) with k the samples since configure (the
+ *     magnitude starts at |p0| before the first renormalisation), and rounds once.  It differs from the recurrence by the recurrence's own rounding walk: at most
+ *     1.2e-4 (complex<float>) and 6.3e-12 (double) over the first 200 000 samples at 37.5 Hz / 1 kHz, amplitude 1.5; the walk grows with the stream.
+ *   noise (NoiseGenerator.hpp:78,112-118,157-164; Xoshiro256pp.hpp:32-66): one xoshiro256++ stream seeded by splitmix64; Uniform 2 u01 - 1, Triangular u01 + u01 - 1,
+ *     complex: real part first; Gaussian by Marsaglia's polar method with the cached second variate (GaussianNoise.hpp:33-55), complex {A (g1 / sqrt2) + O, A (g2 / sqrt2)}.
+ *     Bit for bit for Uniform and Triangular; Gaussian up to the device's log.  The stream's state lives on the device: a call continues it without a host round trip.
+ *   integer T: truncated and clamped (SignalGeneratorCore.hpp:49-60).
+ * check (host only; also the first step of create / configure): GR4HIP_INVALID_ARGUMENT for a non-finite setting, sample_rate <= 0, an unknown signal type or dtype,
+ *   and for a sample_rate whose reciprocal is not finite in F.  DEVIATION: the reference would compute with inf / NaN there.  GR4HIP_UNSUPPORTED for every other
+ *   registered sample type.
+ * create is the block's start(): configure + reset.  configure is settingsChanged (the mirror's, gr4/blocks.hpp): the noise is re-seeded, the spare dropped, the
+ *   phasor and its count start again; the time base keeps running (from the current time with the new tick when sample_rate changed); dtype is fixed.  reset also
+ *   zeroes the time.  Both are host-side notes that the next process call applies on its stream.
+ * process queues a fixed number of launches (1 for Const and the tones, 2 for Uniform / Triangular, 4 for Gaussian; the first call after create / configure /
+ *   reset also carries the new seed state and time table to the device, as the arguments of small launches) and returns without waiting; d_out needs the
+ *   alignment of its sample type only (4 bytes for complex<float>); n == 0 is a no-op; n <= 2^40 per call.
+ * GR4HIP_SIGGEN_GAUSS_PERMILLE (gr4hip_developer_switch) sets how many attempts the parallel Gaussian kernels test per 1000 needed pairs; a tail kernel, queued in
+ *   every call, finishes sequentially what they did not give, so the values do not depend on it. */
+typedef struct gr4hip_siggen gr4hip_siggen_t;
+typedef enum { /* SignalGeneratorCore.hpp:16 */
+    GR4HIP_SIGGEN_CONST = 0, GR4HIP_SIGGEN_SIN, GR4HIP_SIGGEN_COS, GR4HIP_SIGGEN_SQUARE, GR4HIP_SIGGEN_SAW, GR4HIP_SIGGEN_TRIANGLE, GR4HIP_SIGGEN_FAST_SIN,
+    GR4HIP_SIGGEN_FAST_COS, GR4HIP_SIGGEN_UNIFORM_NOISE, GR4HIP_SIGGEN_TRIANGULAR_NOISE, GR4HIP_SIGGEN_GAUSSIAN_NOISE
+} gr4hip_siggen_type;
+typedef struct {
+    int                dtype;       /* GR4HIP_F32, GR4HIP_F64, GR4HIP_C32 or GR4HIP_I16 */
+    int                signal_type; /* gr4hip_siggen_type */
+    float              sample_rate, frequency, amplitude, offset, phase; /* SignalGenerator.hpp:40-46 */
+    unsigned long long seed;        /* (:47) */
+} gr4hip_siggen_params;
+int    gr4hip_siggen_check(const gr4hip_siggen_params* p);                            /* host only: the validation of create */
+int    gr4hip_siggen_create(gr4hip_siggen_t** h, const gr4hip_siggen_params* p);      /* start() (SignalGenerator.hpp:57-61): configure + reset */
+int    gr4hip_siggen_configure(gr4hip_siggen_t* h, const gr4hip_siggen_params* p);    /* settingsChanged (:63-66): the time keeps running */
+int    gr4hip_siggen_reset(gr4hip_siggen_t* h);                                       /* reset() (SignalGeneratorCore.hpp:90-93) */
+int    gr4hip_siggen_process(gr4hip_siggen_t* h, void* d_out, size_t n, gr4hip_stream_t stream); /* n x generateSample() (:68-83, SignalGeneratorCore.hpp:95-106) */
+void   gr4hip_siggen_destroy(gr4hip_siggen_t* h);
+size_t gr4hip_siggen_run(void);  /* consecutive samples one lane generates */
+size_t gr4hip_siggen_tile(void); /* samples of one workgroup: where the start states change hands */
+/* host-only helpers (no device): the xoshiro256++ state n_draws draws further on (Xoshiro256pp.hpp:41-52 applied n_draws times, through the T^(2^k) matrices), and
+ * the reference's time t_n (ToneGenerator.hpp:224-225) for n = n0 .. n0 + count - 1 from the segment table, as double (exact for F = float) */
+int    gr4hip_siggen_jump_host(const unsigned long long in[4], unsigned long long n_draws, unsigned long long out[4]);
+int    gr4hip_siggen_time_host(int dtype, float sample_rate, unsigned long long n0, size_t count, double* t_out);
 
 #ifdef __cplusplus
 }
