@@ -1101,6 +1101,147 @@ class SignalGenerator(_Handle):
         return self.generate_into(torch.empty(int(n), dtype=self.dtype, device=device))
 
 
+class Converter(_Handle):
+    """The type-converter blocks of blocks/basic/.../ConverterBlocks.hpp:13-277 on the device (include/gr4hip.h "Type converters", CONVERTERS.md): one launch per
+    call, every pointer with the alignment of its element type only.  `process_bulk` takes one tensor per input port and returns a tensor, or a tuple for the
+    two-output kinds.  set_prologue / set_epilogue take a Merged program of the input / output dtype: a run of per-sample neighbours rides in this launch."""
+    _destroy = "gr4hip_convert_destroy"
+
+    def __init__(self, kind, in_dtype, out_dtype=None, scale=1.0):
+        super().__init__()
+        self.kind = capi.CONVERT_KINDS.index(kind) if isinstance(kind, str) else int(kind)
+        if in_dtype not in _DTYPE_ID:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "Converter", f"dtype {in_dtype}")
+        self._p = capi.ConvertParams()
+        check(lib().gr4hip_convert_params_default(C.byref(self._p), self.kind, _DTYPE_ID[in_dtype]), "Converter")
+        if out_dtype is not None:
+            if out_dtype not in _DTYPE_ID:
+                raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "Converter", f"dtype {out_dtype}")
+            self._p.out_dtype = _DTYPE_ID[out_dtype]
+        self._p.scale = float(scale)
+        check(lib().gr4hip_convert_create(C.byref(self._h), C.byref(self._p)), "Converter")
+        self.in_dtype, self.out_dtype = in_dtype, _TORCH_DTYPE[self._p.out_dtype]
+        n_in, n_out, ic, oc = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
+        check(lib().gr4hip_convert_ports(self._h, C.byref(n_in), C.byref(n_out), C.byref(ic), C.byref(oc)), "Converter.ports")
+        self.n_inputs, self.n_outputs, self.in_chunk, self.out_chunk = n_in.value, n_out.value, ic.value, oc.value
+
+    def tile(self) -> int:
+        """items one workgroup of the aligned body converts"""
+        return int(lib().gr4hip_convert_tile(C.byref(self._p)))
+
+    @property
+    def scale(self) -> float:
+        return self._p.scale
+
+    def set_scale(self, scale):
+        check(lib().gr4hip_convert_set_scale(self._h, float(scale)), "Converter.set_scale")
+        self._p.scale = float(scale)
+
+    def reset(self):
+        check(lib().gr4hip_convert_reset(self._h), "Converter.reset")
+
+    def set_prologue(self, prog: Optional["Merged"]):
+        check(lib().gr4hip_convert_set_prologue(self._h, prog._h if prog is not None else None), "Converter.set_prologue")
+
+    def set_epilogue(self, prog: Optional["Merged"]):
+        check(lib().gr4hip_convert_set_epilogue(self._h, prog._h if prog is not None else None), "Converter.set_epilogue")
+
+    def process_bulk(self, *inputs: torch.Tensor, out=None, connected: Optional[Sequence[bool]] = None):
+        """`out`: a tensor (or one per output port) to write into; `connected`: False for an output port left unconnected (its entry of the result is None)"""
+        if len(inputs) != self.n_inputs:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "Converter", f"{self.n_inputs} input port(s), got {len(inputs)}")
+        ins = [_dev(x, "Converter") for x in inputs]
+        if any(x.dtype != self.in_dtype or x.numel() != ins[0].numel() for x in ins):
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "Converter", f"every input must be {self.in_dtype} and of one length")
+        n_in = ins[0].numel()
+        if n_in % self.in_chunk:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "Converter", f"the input comes in chunks of {self.in_chunk} (got {n_in})")
+        n_out = n_in // self.in_chunk * self.out_chunk
+        connected = [True] * self.n_outputs if connected is None else list(connected)
+        given = [None] * self.n_outputs if out is None else [out] if isinstance(out, torch.Tensor) else list(out)
+        if len(connected) != self.n_outputs or len(given) != self.n_outputs:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "Converter", f"{self.n_outputs} output port(s)")
+        outs = [_out(given[q], n_out, self.out_dtype, ins[0], "Converter") if connected[q] else None for q in range(self.n_outputs)]
+        pin = (C.c_void_p * self.n_inputs)(*[x.data_ptr() for x in ins])
+        pout = (C.c_void_p * self.n_outputs)(*[o.data_ptr() if o is not None else None for o in outs])
+        written = C.c_size_t(0)
+        check(lib().gr4hip_convert_process(self._h, pin, pout, n_in, C.byref(written), _stream()), "Converter.process")
+        assert written.value == n_out
+        return outs[0] if self.n_outputs == 1 else tuple(outs)
+
+
+class Convert(Converter):
+    """Convert<T, R> (ConverterBlocks.hpp:15-33): static_cast<R>(input)"""
+
+    def __init__(self, in_dtype, out_dtype):
+        super().__init__("Convert", in_dtype, out_dtype)
+
+
+class ScalingConvert(Converter):
+    """ScalingConvert<T, R> (:37-59): static_cast<R>(input * scale), scale of type T"""
+
+    def __init__(self, in_dtype, out_dtype, scale=1.0):
+        super().__init__("ScalingConvert", in_dtype, out_dtype, scale)
+
+
+class _OneType(Converter):
+    def __init__(self, dtype):
+        super().__init__(type(self).__name__, dtype)
+
+
+class _TwoTypes(Converter):
+    def __init__(self, in_dtype, out_dtype):
+        super().__init__(type(self).__name__, in_dtype, out_dtype)
+
+
+class Abs(_OneType):
+    """Abs<T> (:63-81)"""
+
+
+class Real(_OneType):
+    """Real<T> (:100-111)"""
+
+
+class Imag(_OneType):
+    """Imag<T> (:85-96)"""
+
+
+class Arg(_OneType):
+    """Arg<T> (:115-126)"""
+
+
+class RadiansToDegree(_OneType):
+    """RadiansToDegree<T> (:130-143)"""
+
+
+class DegreeToRadians(_OneType):
+    """DegreeToRadians<T> (:147-160)"""
+
+
+class ToRealImag(_OneType):
+    """ToRealImag<T> (:164-178): process_bulk returns (real, imag)"""
+
+
+class RealImagToComplex(_OneType):
+    """RealImagToComplex<T> (:182-195): process_bulk(real, imag)"""
+
+
+class ToMagPhase(_OneType):
+    """ToMagPhase<T> (:199-213): process_bulk returns (mag, phase)"""
+
+
+class MagPhaseToComplex(_OneType):
+    """MagPhaseToComplex<T> (:217-231): process_bulk(mag, phase)"""
+
+
+class ComplexToInterleaved(_TwoTypes):
+    """ComplexToInterleaved<T, R> (:235-254): two output elements per input sample"""
+
+
+class InterleavedToComplex(_TwoTypes):
+    """InterleavedToComplex<T, R> (:258-277): one output sample per two input elements"""
+
+
 def synth_c32(n: int, seed: int = 42, tone_frel: float = 0.1, tone_amp: float = 1.0, noise_amp: float = 1.0, device="cuda") -> torch.Tensor:
     out = torch.empty(n, dtype=torch.complex64, device=device)
     check(lib().gr4hip_synth_c32(out.data_ptr(), n, seed, tone_frel, tone_amp, noise_amp, _stream()), "synth_c32")

@@ -212,6 +212,17 @@ SIGNATURES = {
     "gr4hip_siggen_tile": (_sz, []),
     "gr4hip_siggen_jump_host": (_i, [C.POINTER(C.c_ulonglong), C.c_ulonglong, C.POINTER(C.c_ulonglong)]),
     "gr4hip_siggen_time_host": (_i, [_i, _f, C.c_ulonglong, _sz, C.POINTER(C.c_double)]),
+    "gr4hip_convert_params_default": (_i, [_vp, _i, _i]),
+    "gr4hip_convert_params_check": (_i, [_vp]),
+    "gr4hip_convert_create": (_i, [_pvp, _vp]),
+    "gr4hip_convert_destroy": (_i, [_vp]),
+    "gr4hip_convert_set_scale": (_i, [_vp, _d]),
+    "gr4hip_convert_reset": (_i, [_vp]),
+    "gr4hip_convert_ports": (_i, [_vp, _psz, _psz, _psz, _psz]),
+    "gr4hip_convert_process": (_i, [_vp, _pvp, _pvp, _sz, _psz, _vp]),
+    "gr4hip_convert_set_prologue": (_i, [_vp, _vp]),
+    "gr4hip_convert_set_epilogue": (_i, [_vp, _vp]),
+    "gr4hip_convert_tile": (_sz, [_vp]),
 }
 
 class FilterParams(C.Structure):
@@ -265,6 +276,15 @@ class SigGenParams(C.Structure):
     """gr4hip_siggen_params: the sample type and the settings of gr::basic::SignalGenerator<T> (SignalGenerator.hpp:40-47)"""
     _fields_ = [("dtype", _i), ("signal_type", _i), ("sample_rate", _f), ("frequency", _f), ("amplitude", _f), ("offset", _f), ("phase", _f),
                 ("seed", C.c_ulonglong)]
+
+
+CONVERT_KINDS = ["Convert", "ScalingConvert", "Abs", "Real", "Imag", "Arg", "RadiansToDegree", "DegreeToRadians", "ToRealImag", "RealImagToComplex", "ToMagPhase",
+                 "MagPhaseToComplex", "ComplexToInterleaved", "InterleavedToComplex"]  # gr4hip_convert_kind, under the reference's block names
+
+
+class ConvertParams(C.Structure):
+    """gr4hip_convert_params: which of the fourteen converter blocks (ConverterBlocks.hpp), its port types and ScalingConvert's scale"""
+    _fields_ = [("kind", _i), ("in_dtype", _i), ("out_dtype", _i), ("scale", _d)]
 
 
 LOWPASS, HIGHPASS, BANDPASS, BANDSTOP = range(4)

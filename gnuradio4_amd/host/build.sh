@@ -4,7 +4,7 @@ set -e
 cd "$(dirname "$0")"
 OUT=../../build/host
 mkdir -p $OUT
-HDRS="include/gr4/core.hpp include/gr4/blocks.hpp include/gr4/merge.hpp include/gr4/hip.hpp include/gr4/plugin.hpp include/gr4/grc.hpp ../../include/gr4hip.h"
+HDRS="include/gr4/core.hpp include/gr4/converter_ops.hpp include/gr4/blocks.hpp include/gr4/merge.hpp include/gr4/hip.hpp include/gr4/plugin.hpp include/gr4/grc.hpp ../../include/gr4hip.h"
 CXX="g++ -std=c++20 -Wall -Wextra -Iinclude"
 LINK="-L.. -lgr4hip -Wl,-rpath,\$ORIGIN/../../gnuradio4_amd -Wl,-rpath,/opt/rocm/lib"
 stale() { # target sources...
@@ -19,8 +19,15 @@ if stale $OUT/test_host_cpu tests/test_host_cpu.cpp; then $CXX -O2 tests/test_ho
 if stale $OUT/test_host_fanin tests/test_host_fanin.cpp; then $CXX -O2 tests/test_host_fanin.cpp -o $OUT/test_host_fanin $LINK & pids+=($!); fi
 if stale $OUT/test_host_device tests/test_host_device.cpp; then $CXX -O2 tests/test_host_device.cpp -o $OUT/test_host_device $LINK & pids+=($!); fi
 # the plugin (gr_plugin_make / gr_plugin_free) next to libgr4hip.so, and a loader test that links neither
-if stale ../libgr4hip_blocks.so plugin/gr4hip_blocks.cpp; then
-  $CXX -O1 -fPIC -shared -fvisibility=hidden plugin/gr4hip_blocks.cpp -o ../libgr4hip_blocks.so -L.. -lgr4hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,/opt/rocm/lib & pids+=($!)
+# (the 246 converter block types are twelve translation units of the plugin, compiled side by side; the plugin is linked once everything is built)
+PLUGIN_OBJS=""
+if stale ../libgr4hip_blocks.so plugin/gr4hip_blocks.cpp plugin/gr4hip_converters.cpp; then
+  PLUGIN_OBJS="$OUT/plugin_main.o"
+  $CXX -O1 -fPIC -fvisibility=hidden -c plugin/gr4hip_blocks.cpp -o $OUT/plugin_main.o & pids+=($!)
+  for k in 0 1 2 3 4 5 6 7 8 9 10 11; do
+    PLUGIN_OBJS="$PLUGIN_OBJS $OUT/plugin_conv$k.o"
+    $CXX -O1 -fPIC -fvisibility=hidden -DGR4HIP_CONVERTER_PART=$k -c plugin/gr4hip_converters.cpp -o $OUT/plugin_conv$k.o & pids+=($!)
+  done
 fi
 if stale $OUT/bench_host_feed tests/bench_host_feed.cpp; then $CXX -O2 tests/bench_host_feed.cpp -o $OUT/bench_host_feed $LINK & pids+=($!); fi
 if stale $OUT/bench_host_fanin tests/bench_host_fanin.cpp; then $CXX -O2 tests/bench_host_fanin.cpp -o $OUT/bench_host_fanin $LINK & pids+=($!); fi
@@ -32,5 +39,7 @@ if stale $OUT/test_host_power_metrics tests/test_host_power_metrics.cpp; then $C
 if stale $OUT/test_host_schmitt_trigger tests/test_host_schmitt_trigger.cpp; then $CXX -O2 tests/test_host_schmitt_trigger.cpp -o $OUT/test_host_schmitt_trigger -ldl & pids+=($!); fi
 if stale $OUT/test_host_svd_denoiser tests/test_host_svd_denoiser.cpp; then $CXX -O2 tests/test_host_svd_denoiser.cpp -o $OUT/test_host_svd_denoiser -ldl & pids+=($!); fi
 if stale $OUT/test_host_signal_generator tests/test_host_signal_generator.cpp; then $CXX -O2 tests/test_host_signal_generator.cpp -o $OUT/test_host_signal_generator $LINK & pids+=($!); fi
+if stale $OUT/test_host_converter tests/test_host_converter.cpp; then $CXX -O1 tests/test_host_converter.cpp -o $OUT/test_host_converter $LINK & pids+=($!); fi
 for p in "${pids[@]}"; do wait $p; done
+if [ -n "$PLUGIN_OBJS" ]; then $CXX -fPIC -shared -fvisibility=hidden $PLUGIN_OBJS -o ../libgr4hip_blocks.so -L.. -lgr4hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,/opt/rocm/lib; fi
 echo "built $(realpath $OUT)"

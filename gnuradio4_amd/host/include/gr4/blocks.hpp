@@ -8,6 +8,7 @@
 #include <numbers>
 
 #include "../../../../include/gr4hip.h" // host-side design functions only (gr4hip_fir_design / gr4hip_iir_design / gr4hip_window_create: no device needed)
+#include "converter_ops.hpp"
 #include "core.hpp"
 
 namespace gr::testing {
@@ -1096,3 +1097,265 @@ private:
     }
 };
 } // namespace gr::blocks::fft
+
+// ---- the type-converter blocks (blocks/basic/.../ConverterBlocks.hpp:13-277) under the reference's names and port names.  The host bodies are the reference's
+// expressions with the integer / cast rules of gr4/converter_ops.hpp where its C++ is undefined (CONVERTERS.md), the same header the device kernels use: the two
+// domains of a block agree on every input.  Ports that are not called in / out go through hostWork() (the default work loop knows only that pair).
+namespace gr::blocks::type::converter {
+namespace ops = gr4::converter_ops;
+namespace detail {
+template <typename T> struct base_value { using type = T; };
+template <typename T> struct base_value<std::complex<T>> { using type = T; };
+template <typename T> using base_value_t = typename base_value<T>::type; // meta::fundamental_base_value_type_t
+template <typename T> concept complex_like = gr::detail::is_complex<T>::value;
+template <typename T> concept interleavable = std::floating_point<T> || std::is_same_v<T, std::int8_t> || std::is_same_v<T, std::int16_t>;
+
+template <typename P>
+std::span<typename P::value_type> out_span(P& port, std::size_t n, std::vector<typename P::value_type>& scratch) {
+    if (port.connected()) return port.buffer->write_span(n);
+    scratch.resize(n);
+    return scratch;
+}
+template <typename B, typename PI, typename PO>
+work::Status map11(B& b, PI& in, PO& out, std::size_t n) {
+    std::vector<typename PO::value_type> s;
+    const auto is = in.buffer->read_span(n);
+    auto       os = out_span(out, n, s);
+    for (std::size_t i = 0; i < n; ++i) os[i] = b.processOne(is[i]);
+    return work::Status::OK;
+}
+template <typename B, typename PI, typename PO>
+work::Status map12(B& b, PI& in, PO& out0, PO& out1, std::size_t n) {
+    std::vector<typename PO::value_type> s0, s1;
+    const auto is = in.buffer->read_span(n);
+    auto       o0 = out_span(out0, n, s0), o1 = out_span(out1, n, s1);
+    for (std::size_t i = 0; i < n; ++i) std::tie(o0[i], o1[i]) = b.processOne(is[i]);
+    return work::Status::OK;
+}
+template <typename B, typename PI, typename PO>
+work::Status map21(B& b, PI& in0, PI& in1, PO& out, std::size_t n) {
+    std::vector<typename PO::value_type> s;
+    const auto i0 = in0.buffer->read_span(n), i1 = in1.buffer->read_span(n);
+    auto       os = out_span(out, n, s);
+    for (std::size_t i = 0; i < n; ++i) os[i] = b.processOne(i0[i], i1[i]);
+    return work::Status::OK;
+}
+} // namespace detail
+
+GR_REGISTER_BLOCK(gr::blocks::type::converter::Convert, ([T], [U]), [ uint8_t, uint16_t, uint32_t, uint64_t, int8_t, int16_t, int32_t, int64_t, float, double ], [ uint8_t, uint16_t, uint32_t, uint64_t, int8_t, int16_t, int32_t, int64_t, float, double ])
+template <typename T, typename R>
+    requires std::is_arithmetic_v<T> && std::is_arithmetic_v<R>
+struct Convert : Block<Convert<T, R>> { // (:15-33)
+    PortIn<T>  in;
+    PortOut<R> out;
+    GR_MAKE_REFLECTABLE(Convert, in, out);
+    static constexpr int kConvertKind = GR4HIP_CONVERT; // the device kernel family of this block (gr4/hip.hpp)
+    auto inPorts() { return std::tie(in); }
+    auto outPorts() { return std::tie(out); }
+    [[nodiscard]] constexpr R processOne(const T& input) const noexcept { return ops::cast<R>(input); }
+};
+
+GR_REGISTER_BLOCK(gr::blocks::type::converter::ScalingConvert, ([T], [U]), [ uint8_t, uint16_t, uint32_t, uint64_t, int8_t, int16_t, int32_t, int64_t, float, double ], [ uint8_t, uint16_t, uint32_t, uint64_t, int8_t, int16_t, int32_t, int64_t, float, double ])
+template <typename T, typename R>
+    requires std::is_arithmetic_v<T> && std::is_arithmetic_v<R>
+struct ScalingConvert : Block<ScalingConvert<T, R>> { // (:37-59): R output = R(input * scale), the product in the promoted type
+    PortIn<T>  in;
+    PortOut<R> out;
+    T          scale = static_cast<T>(1);
+    GR_MAKE_REFLECTABLE(ScalingConvert, in, out, scale);
+    static constexpr int kConvertKind = GR4HIP_SCALING_CONVERT; // the device kernel family of this block (gr4/hip.hpp)
+    auto inPorts() { return std::tie(in); }
+    auto outPorts() { return std::tie(out); }
+    [[nodiscard]] constexpr R processOne(const T& input) const noexcept { return ops::cast<R>(ops::mul<T>(input, scale)); }
+};
+
+GR_REGISTER_BLOCK(gr::blocks::type::converter::Abs, [T], [ uint8_t, uint16_t, uint32_t, uint64_t, int8_t, int16_t, int32_t, int64_t, float, double, std::complex<float>, std::complex<double> ])
+template <typename T>
+    requires std::is_arithmetic_v<T> || detail::complex_like<T>
+struct Abs : Block<Abs<T>> { // (:63-81)
+    using R = detail::base_value_t<T>;
+    PortIn<T>  in;
+    PortOut<R> abs;
+    GR_MAKE_REFLECTABLE(Abs, in, abs);
+    static constexpr int kConvertKind = GR4HIP_CONVERT_ABS; // the device kernel family of this block (gr4/hip.hpp)
+    auto inPorts() { return std::tie(in); }
+    auto outPorts() { return std::tie(abs); }
+    [[nodiscard]] R processOne(T input) const noexcept {
+        if constexpr (std::is_integral_v<T>) return ops::abs_int<T>(input);
+        else return static_cast<R>(std::abs(input));
+    }
+    work::Status hostWork(std::size_t nIn, std::size_t) { return detail::map11(*this, in, abs, nIn); }
+};
+
+GR_REGISTER_BLOCK(gr::blocks::type::converter::Imag, [T], [ std::complex<float>, std::complex<double> ])
+template <detail::complex_like T>
+struct Imag : Block<Imag<T>> { // (:85-96)
+    using R = detail::base_value_t<T>;
+    PortIn<T>  in;
+    PortOut<R> imag;
+    GR_MAKE_REFLECTABLE(Imag, in, imag);
+    static constexpr int kConvertKind = GR4HIP_CONVERT_IMAG; // the device kernel family of this block (gr4/hip.hpp)
+    auto inPorts() { return std::tie(in); }
+    auto outPorts() { return std::tie(imag); }
+    [[nodiscard]] constexpr R processOne(T input) const noexcept { return std::imag(input); }
+    work::Status hostWork(std::size_t nIn, std::size_t) { return detail::map11(*this, in, imag, nIn); }
+};
+
+GR_REGISTER_BLOCK(gr::blocks::type::converter::Real, [T], [ std::complex<float>, std::complex<double> ])
+template <detail::complex_like T>
+struct Real : Block<Real<T>> { // (:100-111)
+    using R = detail::base_value_t<T>;
+    PortIn<T>  in;
+    PortOut<R> real;
+    GR_MAKE_REFLECTABLE(Real, in, real);
+    static constexpr int kConvertKind = GR4HIP_CONVERT_REAL; // the device kernel family of this block (gr4/hip.hpp)
+    auto inPorts() { return std::tie(in); }
+    auto outPorts() { return std::tie(real); }
+    [[nodiscard]] constexpr R processOne(T input) const noexcept { return std::real(input); }
+    work::Status hostWork(std::size_t nIn, std::size_t) { return detail::map11(*this, in, real, nIn); }
+};
+
+GR_REGISTER_BLOCK(gr::blocks::type::converter::Arg, [T], [ std::complex<float>, std::complex<double> ])
+template <detail::complex_like T>
+struct Arg : Block<Arg<T>> { // (:115-126)
+    using R = detail::base_value_t<T>;
+    PortIn<T>  in;
+    PortOut<R> arg;
+    GR_MAKE_REFLECTABLE(Arg, in, arg);
+    static constexpr int kConvertKind = GR4HIP_CONVERT_ARG; // the device kernel family of this block (gr4/hip.hpp)
+    auto inPorts() { return std::tie(in); }
+    auto outPorts() { return std::tie(arg); }
+    [[nodiscard]] R processOne(T input) const noexcept { return std::arg(input); }
+    work::Status hostWork(std::size_t nIn, std::size_t) { return detail::map11(*this, in, arg, nIn); }
+};
+
+GR_REGISTER_BLOCK(gr::blocks::type::converter::RadiansToDegree, [T], [ float, double ])
+template <std::floating_point T>
+struct RadiansToDegree : Block<RadiansToDegree<T>> { // (:130-143): a division, then a multiplication
+    PortIn<T>  rad;
+    PortOut<T> deg;
+    GR_MAKE_REFLECTABLE(RadiansToDegree, rad, deg);
+    static constexpr int kConvertKind = GR4HIP_RADIANS_TO_DEGREE; // the device kernel family of this block (gr4/hip.hpp)
+    auto inPorts() { return std::tie(rad); }
+    auto outPorts() { return std::tie(deg); }
+    [[nodiscard]] constexpr T processOne(const T& radians) const noexcept { return (radians / std::numbers::pi_v<T>)*static_cast<T>(180); }
+    work::Status hostWork(std::size_t nIn, std::size_t) { return detail::map11(*this, rad, deg, nIn); }
+};
+
+GR_REGISTER_BLOCK(gr::blocks::type::converter::DegreeToRadians, [T], [ float, double ])
+template <std::floating_point T>
+struct DegreeToRadians : Block<DegreeToRadians<T>> { // (:147-160)
+    PortIn<T>  deg;
+    PortOut<T> rad;
+    GR_MAKE_REFLECTABLE(DegreeToRadians, deg, rad);
+    static constexpr int kConvertKind = GR4HIP_DEGREE_TO_RADIANS; // the device kernel family of this block (gr4/hip.hpp)
+    auto inPorts() { return std::tie(deg); }
+    auto outPorts() { return std::tie(rad); }
+    [[nodiscard]] constexpr T processOne(const T& degree) const noexcept { return (degree / static_cast<T>(180)) * std::numbers::pi_v<T>; }
+    work::Status hostWork(std::size_t nIn, std::size_t) { return detail::map11(*this, deg, rad, nIn); }
+};
+
+GR_REGISTER_BLOCK(gr::blocks::type::converter::ToRealImag, [T], [ std::complex<float>, std::complex<double> ])
+template <detail::complex_like T>
+struct ToRealImag : Block<ToRealImag<T>> { // (:164-178)
+    using R = detail::base_value_t<T>;
+    PortIn<T>  in;
+    PortOut<R> real;
+    PortOut<R> imag;
+    GR_MAKE_REFLECTABLE(ToRealImag, in, real, imag);
+    static constexpr int kConvertKind = GR4HIP_TO_REAL_IMAG; // the device kernel family of this block (gr4/hip.hpp)
+    auto inPorts() { return std::tie(in); }
+    auto outPorts() { return std::tie(real, imag); }
+    [[nodiscard]] constexpr std::tuple<R, R> processOne(T complexIn) const noexcept { return {std::real(complexIn), std::imag(complexIn)}; }
+    work::Status hostWork(std::size_t nIn, std::size_t) { return detail::map12(*this, in, real, imag, nIn); }
+};
+
+// DEVIATION: the reference's registration macros of the next three blocks repeat the name ToRealImag (:180, :197, :215); each is registered under its own name here
+GR_REGISTER_BLOCK(gr::blocks::type::converter::RealImagToComplex, [T], [ float, double ])
+template <std::floating_point T>
+struct RealImagToComplex : Block<RealImagToComplex<T>> { // (:182-195)
+    using R = std::complex<T>;
+    PortIn<T>  real;
+    PortIn<T>  imag;
+    PortOut<R> out;
+    GR_MAKE_REFLECTABLE(RealImagToComplex, real, imag, out);
+    static constexpr int kConvertKind = GR4HIP_REAL_IMAG_TO_COMPLEX; // the device kernel family of this block (gr4/hip.hpp)
+    auto inPorts() { return std::tie(real, imag); }
+    auto outPorts() { return std::tie(out); }
+    [[nodiscard]] constexpr R processOne(T re, T im) const noexcept { return {re, im}; }
+    work::Status hostWork(std::size_t nIn, std::size_t) { return detail::map21(*this, real, imag, out, nIn); }
+};
+
+GR_REGISTER_BLOCK(gr::blocks::type::converter::ToMagPhase, [T], [ std::complex<float>, std::complex<double> ])
+template <detail::complex_like T>
+struct ToMagPhase : Block<ToMagPhase<T>> { // (:199-213)
+    using R = detail::base_value_t<T>;
+    PortIn<T>  in;
+    PortOut<R> mag;
+    PortOut<R> phase;
+    GR_MAKE_REFLECTABLE(ToMagPhase, in, mag, phase);
+    static constexpr int kConvertKind = GR4HIP_TO_MAG_PHASE; // the device kernel family of this block (gr4/hip.hpp)
+    auto inPorts() { return std::tie(in); }
+    auto outPorts() { return std::tie(mag, phase); }
+    [[nodiscard]] std::tuple<R, R> processOne(T complexIn) const noexcept { return {static_cast<R>(std::abs(complexIn)), static_cast<R>(std::arg(complexIn))}; }
+    work::Status hostWork(std::size_t nIn, std::size_t) { return detail::map12(*this, in, mag, phase, nIn); }
+};
+
+GR_REGISTER_BLOCK(gr::blocks::type::converter::MagPhaseToComplex, [T], [ float, double ])
+template <std::floating_point T>
+struct MagPhaseToComplex : Block<MagPhaseToComplex<T>> { // (:217-231): {r cos theta, r sin theta} (std::polar's value without its precondition on r)
+    using R = std::complex<T>;
+    PortIn<T>  mag;
+    PortIn<T>  phase;
+    PortOut<R> out;
+    GR_MAKE_REFLECTABLE(MagPhaseToComplex, mag, phase, out);
+    static constexpr int kConvertKind = GR4HIP_MAG_PHASE_TO_COMPLEX; // the device kernel family of this block (gr4/hip.hpp)
+    auto inPorts() { return std::tie(mag, phase); }
+    auto outPorts() { return std::tie(out); }
+    [[nodiscard]] R processOne(T r, T theta) const noexcept { return {r * std::cos(theta), r * std::sin(theta)}; }
+    work::Status hostWork(std::size_t nIn, std::size_t) { return detail::map21(*this, mag, phase, out, nIn); }
+};
+
+// (the templates' constraint, wider than the reference's registration: the int8 / int16 variants are registered too -- the interleaved I/Q of an SDR or ADC)
+GR_REGISTER_BLOCK(gr::blocks::type::converter::ComplexToInterleaved, ([T], [U]), [ std::complex<float>, std::complex<double> ], [ float, double, int8_t, int16_t ])
+template <detail::complex_like T, detail::interleavable R>
+struct ComplexToInterleaved : Block<ComplexToInterleaved<T, R>, Resampling<1U, 2U, true>> { // (:235-254)
+    PortIn<T>  in;
+    PortOut<R> interleaved;
+    GR_MAKE_REFLECTABLE(ComplexToInterleaved, in, interleaved);
+    static constexpr int kConvertKind = GR4HIP_COMPLEX_TO_INTERLEAVED; // the device kernel family of this block (gr4/hip.hpp)
+    auto inPorts() { return std::tie(in); }
+    auto outPorts() { return std::tie(interleaved); }
+    [[nodiscard]] constexpr work::Status processBulk(std::span<const T> complexInput, std::span<R> interleavedOut) const noexcept {
+        for (std::size_t i = 0; i < complexInput.size(); ++i) {
+            interleavedOut[2 * i]     = ops::cast<R>(complexInput[i].real());
+            interleavedOut[2 * i + 1] = ops::cast<R>(complexInput[i].imag());
+        }
+        return work::Status::OK;
+    }
+    work::Status hostWork(std::size_t nIn, std::size_t nOut) {
+        std::vector<R> s;
+        return processBulk(in.buffer->read_span(nIn), detail::out_span(interleaved, nOut, s));
+    }
+};
+
+GR_REGISTER_BLOCK(gr::blocks::type::converter::InterleavedToComplex, ([T], [U]), [ float, double, int8_t, int16_t ], [ std::complex<float>, std::complex<double> ])
+template <detail::interleavable T, detail::complex_like R>
+struct InterleavedToComplex : Block<InterleavedToComplex<T, R>, Resampling<2U, 1U, true>> { // (:258-277)
+    PortIn<T>  interleaved;
+    PortOut<R> out;
+    GR_MAKE_REFLECTABLE(InterleavedToComplex, interleaved, out);
+    static constexpr int kConvertKind = GR4HIP_INTERLEAVED_TO_COMPLEX; // the device kernel family of this block (gr4/hip.hpp)
+    auto inPorts() { return std::tie(interleaved); }
+    auto outPorts() { return std::tie(out); }
+    [[nodiscard]] constexpr work::Status processBulk(std::span<const T> interleavedInput, std::span<R> complexOut) const noexcept {
+        for (std::size_t i = 0; i < complexOut.size(); ++i)
+            complexOut[i] = R{static_cast<typename R::value_type>(interleavedInput[2 * i]), static_cast<typename R::value_type>(interleavedInput[2 * i + 1])};
+        return work::Status::OK;
+    }
+    work::Status hostWork(std::size_t nIn, std::size_t nOut) {
+        std::vector<R> s;
+        return processBulk(interleaved.buffer->read_span(nIn), detail::out_span(out, nOut, s));
+    }
+};
+} // namespace gr::blocks::type::converter

@@ -1033,6 +1033,8 @@ public:
             for (auto& p : d.in) ins.push_back(p.buffer->read_span(nIn));
             std::span<T> os = d.out.buffer->write_span(nOut);
             return d.processBulk(std::span<const std::span<const T>>(ins), os);
+        } else if constexpr (requires { d.hostWork(nIn, nOut); }) { // ports under other names (the converter blocks: abs, real / imag, rad / deg, mag / phase, interleaved)
+            return d.hostWork(nIn, nOut);
         } else if constexpr (requires { d.deviceOnly(); }) { // a device-only block of another port shape (IQDemodulator: 2 in, 3 out): refuses, no host fallback
             return d.deviceOnly();
         } else {

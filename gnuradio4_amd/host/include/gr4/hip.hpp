@@ -432,6 +432,67 @@ struct EwiseStage final : Stage {
     }
 };
 
+// a type-converter block (ConverterBlocks.hpp; gr4hip_convert_*) with one input and one output: element sizes and chunks differ between the two sides.  A
+// neighbouring run of per-sample blocks rides in its launch: as prologue where the program's dtype is the input's, as epilogue where it is the output's.
+struct ConverterStage final : Stage {
+    gr4hip_convert_params p;
+    gr4hip_convert_t*     h = nullptr;
+    EwiseProgram          pre, post;
+    std::string           _kind;
+    static constexpr const char* kKinds[14] = {"Convert", "ScalingConvert", "Abs", "Real", "Imag", "Arg", "RadiansToDegree", "DegreeToRadians", "ToRealImag", "RealImagToComplex",
+                                               "ToMagPhase", "MagPhaseToComplex", "ComplexToInterleaved", "InterleavedToComplex"};
+    static constexpr const char* kTypes[12] = {"u8", "u16", "u32", "u64", "i8", "i16", "i32", "i64", "f32", "f64", "c32", "c64"};
+    explicit ConverterStage(const gr4hip_convert_params& params) : p(params) {
+        static constexpr std::size_t bytes[12] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 8, 16};
+        check(gr4hip_convert_create(&h, &p), "gr4hip_convert_create");
+        std::size_t n_in = 0, n_out = 0;
+        check(gr4hip_convert_ports(h, &n_in, &n_out, &in_chunk, &out_chunk), "gr4hip_convert_ports");
+        if (n_in != 1 || n_out != 1) { gr4hip_convert_destroy(h); throw std::invalid_argument("ConverterStage: one input and one output (the two-port kinds go through the seam)"); }
+        in_bytes  = bytes[std::clamp(p.in_dtype, 0, 11)];
+        out_bytes = bytes[std::clamp(p.out_dtype, 0, 11)];
+        pre.dtype  = p.in_dtype;
+        post.dtype = p.out_dtype;
+        name();
+    }
+    ~ConverterStage() override { gr4hip_convert_destroy(h); }
+    void name() {
+        _kind = std::string("convert_") + kKinds[std::clamp(p.kind, 0, 13)] + "_" + kTypes[std::clamp(p.in_dtype, 0, 11)] + "_" + kTypes[std::clamp(p.out_dtype, 0, 11)];
+        std::string s;
+        if (!pre.empty()) s += "pre: " + pre.describe();
+        if (!post.empty()) s += std::string(s.empty() ? "" : "; ") + "post: " + post.describe();
+        if (!s.empty()) _kind += "[" + s + "]";
+    }
+    void apply() { // the handle copies the programs
+        gr4hip_ewise_t* a = pre.empty() ? nullptr : pre.make();
+        gr4hip_ewise_t* b = post.empty() ? nullptr : post.make();
+        const int       ra = gr4hip_convert_set_prologue(h, a), rb = gr4hip_convert_set_epilogue(h, b);
+        if (a) gr4hip_ewise_destroy(a);
+        if (b) gr4hip_ewise_destroy(b);
+        check(ra, "gr4hip_convert_set_prologue");
+        check(rb, "gr4hip_convert_set_epilogue");
+        name();
+    }
+    std::string_view kind() const override { return _kind; }
+    bool absorb(const EwiseProgram& prog, bool before) override {
+        if (prog.dtype != (before ? p.in_dtype : p.out_dtype)) return false;
+        if (before) pre.prepend(prog); else post.append(prog);
+        apply();
+        return true;
+    }
+    void clear_absorbed() override {
+        if (pre.empty() && post.empty()) return;
+        pre.ops.clear();
+        post.ops.clear();
+        apply();
+    }
+    void set_scale(double s) { p.scale = s; if (p.kind == GR4HIP_SCALING_CONVERT) check(gr4hip_convert_set_scale(h, s), "gr4hip_convert_set_scale"); }
+    int enqueue(const void* in, std::size_t n, void* out, std::size_t* n_out, gr4hip_stream_t s) override {
+        const void* ins[1]  = {in};
+        void*       outs[1] = {out};
+        return gr4hip_convert_process(h, ins, outs, n, n_out, s);
+    }
+};
+
 // iir_filter<float, form> (one section with the user's b, a) and designed cascades
 struct IirStage final : Stage {
     gr4hip_iir_t*      h = nullptr;
@@ -885,6 +946,68 @@ struct Kernel<gr::filter::IQDemodulator<T, Args...>> {
                 if (port->connected()) std::memcpy(port->buffer->write_span(nOut).data(), hout + k * bo, bo);
                 ++k;
             }
+            return work::Status::OK;
+        } catch (const std::exception& e) {
+            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
+            return work::Status::ERROR; // never a silent host fallback
+        }
+    }
+};
+
+// The converter blocks (gr::blocks::type::converter, gr4/blocks.hpp): every kind goes through the seam -- each input span to HBM, ONE gr4hip_convert_process, each
+// CONNECTED output back (an unconnected port is a NULL pointer in the call and is not copied, as PowerMetrics) -- and the one-input / one-output kinds also give a
+// ConverterStage, for GPU-domain runs and hip::plan.
+template <typename B>
+    requires requires { B::kConvertKind; }
+struct Kernel<B> {
+    using InTuple  = decltype(std::declval<B&>().inPorts());
+    using OutTuple = decltype(std::declval<B&>().outPorts());
+    static constexpr std::size_t NI = std::tuple_size_v<InTuple>, NO = std::tuple_size_v<OutTuple>;
+    using TI = typename std::decay_t<std::tuple_element_t<0, InTuple>>::value_type;
+    using TO = typename std::decay_t<std::tuple_element_t<0, OutTuple>>::value_type;
+    struct State final : Offload {
+        gr4hip_convert_t* h = nullptr;
+        ~State() override { if (h) gr4hip_convert_destroy(h); }
+    };
+    static gr4hip_convert_params params(B& b) {
+        gr4hip_convert_params p{B::kConvertKind, dtype_of<TI>(), dtype_of<TO>(), 1.0};
+        if constexpr (requires { b.scale; }) p.scale = static_cast<double>(b.scale);
+        return p;
+    }
+    static std::unique_ptr<Stage> make_stage(B& b) requires(NI == 1 && NO == 1) { return std::make_unique<ConverterStage>(params(b)); }
+    static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
+        try {
+            State*     st = offload_state<State>(blk);
+            const auto p  = params(blk);
+            if (!st->h) {
+                check(gr4hip_convert_create(&st->h, &p), "gr4hip_convert_create");
+                st->settings_generation = blk._settings_generation;
+            } else if (st->settings_generation != blk._settings_generation) {
+                if (p.kind == GR4HIP_SCALING_CONVERT) check(gr4hip_convert_set_scale(st->h, p.scale), "gr4hip_convert_set_scale");
+                st->settings_generation = blk._settings_generation;
+            }
+            const std::size_t bi = nIn * sizeof(TI), bo = nOut * sizeof(TO);
+            const auto        up = [](std::size_t b) { return (b + 255) / 256 * 256; }; // every port's region starts 256-byte aligned
+            char*             hin = static_cast<char*>(st->h_in.ensure(NI * up(bi)));
+            char*             din = static_cast<char*>(st->d_in.ensure(NI * up(bi)));
+            char*             dout = static_cast<char*>(st->d_out.ensure(NO * up(bo)));
+            char*             hout = static_cast<char*>(st->h_out.ensure(NO * up(bo)));
+            const void*       ins[NI];
+            void*             outs[NO];
+            bool              wired[NO];
+            std::size_t       k = 0;
+            std::apply([&](auto&... port) { ((std::memcpy(hin + k * up(bi), port.buffer->read_span(nIn).data(), bi), ins[k] = din + k * up(bi), ++k), ...); }, blk.inPorts());
+            check(gr4hip_memcpy_h2d(din, hin, (NI - 1) * up(bi) + bi, nullptr), "h2d");
+            k = 0;
+            std::apply([&](auto&... port) { ((wired[k] = port.connected(), outs[k] = wired[k] ? dout + k * up(bo) : nullptr, ++k), ...); }, blk.outPorts());
+            std::size_t produced = 0;
+            check(gr4hip_convert_process(st->h, ins, outs, nIn, &produced, nullptr), "gr4hip_convert_process");
+            if (produced != nOut) throw std::runtime_error("converter: the work loop must hand over whole chunks");
+            for (k = 0; k < NO; ++k)
+                if (wired[k]) check(gr4hip_memcpy_d2h(hout + k * up(bo), dout + k * up(bo), bo, nullptr), "d2h");
+            check(gr4hip_stream_synchronize(nullptr), "sync");
+            k = 0;
+            std::apply([&](auto&... port) { ((wired[k] ? (void)std::memcpy(port.buffer->write_span(nOut).data(), hout + k * up(bo), bo) : (void)0, ++k), ...); }, blk.outPorts());
             return work::Status::OK;
         } catch (const std::exception& e) {
             blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());

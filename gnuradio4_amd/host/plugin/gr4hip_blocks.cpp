@@ -60,6 +60,14 @@ void register_signal_generator(BlockRegistry& r) { // basic/SignalGenerator.hpp:
     r.insert<gr::hip::SignalSource<T>>(named<T>("gr::hip::SignalSource"));
 }
 
+} // namespace
+// the converter blocks (ConverterBlocks.hpp:13-256; gr4hip_converters.cpp): a work loop per registered block type costs seconds of compile time, so the 246 types
+// are compiled as twelve translation units side by side
+#define GR4HIP_CONVERTER_PART(k) void gr4hip_register_converters_##k(gr::BlockRegistry&);
+GR4HIP_CONVERTER_PART(0) GR4HIP_CONVERTER_PART(1) GR4HIP_CONVERTER_PART(2) GR4HIP_CONVERTER_PART(3) GR4HIP_CONVERTER_PART(4) GR4HIP_CONVERTER_PART(5)
+GR4HIP_CONVERTER_PART(6) GR4HIP_CONVERTER_PART(7) GR4HIP_CONVERTER_PART(8) GR4HIP_CONVERTER_PART(9) GR4HIP_CONVERTER_PART(10) GR4HIP_CONVERTER_PART(11)
+namespace {
+using namespace gr;
 const bool registered = [] {
     BlockRegistry& r = grPluginInstance();
     using namespace gr::filter;
@@ -103,6 +111,9 @@ const bool registered = [] {
     r.insert<gr::hip::OnDevice<fir_filter<float>>>(named<float>("gr::hip::OnDevice<gr::filter::fir_filter", ">"));
     r.insert<gr::hip::OnDevice<fir_filter<std::complex<float>>>>(named<std::complex<float>>("gr::hip::OnDevice<gr::filter::fir_filter", ">"));
     r.insert<gr::hip::OnDevice<gr::blocks::fft::PowerSpectrum<std::complex<float>>>>(named<std::complex<float>>("gr::hip::OnDevice<gr::blocks::fft::PowerSpectrum", ">"));
+    gr4hip_register_converters_0(r); gr4hip_register_converters_1(r); gr4hip_register_converters_2(r); gr4hip_register_converters_3(r);
+    gr4hip_register_converters_4(r); gr4hip_register_converters_5(r); gr4hip_register_converters_6(r); gr4hip_register_converters_7(r);
+    gr4hip_register_converters_8(r); gr4hip_register_converters_9(r); gr4hip_register_converters_10(r); gr4hip_register_converters_11(r);
     gr::hip::register_provider(); // edges with EdgeParameters{.domain = "gpu:hip:i"} get pinned pages once the plugin is loaded
     return true;
 }();

@@ -830,6 +830,52 @@ size_t gr4hip_siggen_tile(void); /* samples of one workgroup: where the start st
 int    gr4hip_siggen_jump_host(const unsigned long long in[4], unsigned long long n_draws, unsigned long long out[4]);
 int    gr4hip_siggen_time_host(int dtype, float sample_rate, unsigned long long n0, size_t count, double* t_out);
 
+/* ------------------------------------------------------------------------------------------------ Type converters (blocks/basic/.../ConverterBlocks.hpp:13-277)
+ * The fourteen blocks of gr::blocks::type::converter as ONE streaming kernel family: load -> optional prologue program -> conversion -> optional epilogue program ->
+ * store.  Semantics, deviations and measured bounds: CONVERTERS.md.  An ITEM is what one processOne call consumes per input port: one sample, except for the two
+ * interleaved kinds, whose interleaved port carries two elements per item (Resampling<1, 2, true> / <2, 1, true>, :237, :260).
+ *   Convert / ScalingConvert (:15-59): static_cast<R>(input * scale), the product in the PROMOTED type of T (int for the 8- and 16-bit types), scale of type T
+ *     (1 for Convert: x * 1 is x bit for bit, so both kinds share one set of kernels).  All 10 x 10 arithmetic pairs.
+ *   Abs (:63-81): unsigned T through its signed type and narrowed back; float / double: the sign bit cleared; complex: hypot.  12 types.
+ *   Real, Imag, Arg (:85-126), ToRealImag (:164-178), ToMagPhase (:199-213): complex<float>, complex<double>.  Arg is atan2(im, re) with signed zeros.
+ *   RadiansToDegree, DegreeToRadians (:130-160): (x / pi) * 180 and (x / 180) * pi, two IEEE operations in this order.  float, double.
+ *   RealImagToComplex (:182-195), MagPhaseToComplex (:217-231: {r cos t, r sin t}): float, double.
+ *   ComplexToInterleaved (:235-254), InterleavedToComplex (:258-277): {complex<float>, complex<double>} x {float, double, int8, int16} (the templates' constraint,
+ *     wider than their registration), a static_cast per component.
+ * DEVIATIONS (undefined in the reference, defined here): float -> integer saturates and NaN -> 0; signed overflow of input * scale and of abs wraps modulo 2^w.
+ * complex<float> / float transcendentals (Abs, Arg, ToMagPhase, MagPhaseToComplex) are evaluated in float64 on the float arguments and rounded once.
+ * check (host only; also the first step of create): GR4HIP_INVALID_ARGUMENT for an unknown kind or dtype and for every kind / dtype pair the requires clauses
+ *   exclude; out_dtype must be the block's R.
+ * process: d_in / d_out are arrays of n_in-port / n_out-port device pointers (gr4hip_convert_ports), each with the alignment of its ELEMENT type only.  A NULL
+ *   entry of d_out is an unconnected port and is skipped.  n_in counts elements of input 0 (an odd count is GR4HIP_INVALID_ARGUMENT for InterleavedToComplex);
+ *   *n_out receives the elements written to output 0.  One launch, no wait.
+ * set_prologue / set_epilogue copy the program (as gr4hip_fir_set_prologue); NULL takes it off.  The prologue's dtype must be in_dtype and the kind must have one
+ *   input, the epilogue's out_dtype and one output (else GR4HIP_UNSUPPORTED).  A rotator op sees the absolute index of the (complex) sample since create / reset.
+ * set_scale / set_* / reset are host-side notes: the next process call carries them on its stream. */
+typedef struct gr4hip_convert gr4hip_convert_t;
+typedef enum {
+    GR4HIP_CONVERT = 0, GR4HIP_SCALING_CONVERT, GR4HIP_CONVERT_ABS, GR4HIP_CONVERT_REAL, GR4HIP_CONVERT_IMAG, GR4HIP_CONVERT_ARG, GR4HIP_RADIANS_TO_DEGREE,
+    GR4HIP_DEGREE_TO_RADIANS, GR4HIP_TO_REAL_IMAG, GR4HIP_REAL_IMAG_TO_COMPLEX, GR4HIP_TO_MAG_PHASE, GR4HIP_MAG_PHASE_TO_COMPLEX, GR4HIP_COMPLEX_TO_INTERLEAVED,
+    GR4HIP_INTERLEAVED_TO_COMPLEX
+} gr4hip_convert_kind;
+typedef struct {
+    int    kind;      /* gr4hip_convert_kind */
+    int    in_dtype;  /* T of the input port(s) */
+    int    out_dtype; /* R of the output port(s) */
+    double scale;     /* ScalingConvert::scale (:46), converted to in_dtype; ignored by the other kinds */
+} gr4hip_convert_params;
+int    gr4hip_convert_params_default(gr4hip_convert_params* p, int kind, int in_dtype); /* out_dtype = the block's R (in_dtype for the two-type kinds), scale = 1 (:46) */
+int    gr4hip_convert_params_check(const gr4hip_convert_params* p);                      /* host only: the requires clauses (:16, :38, :64, :130, :236, :259) */
+int    gr4hip_convert_create(gr4hip_convert_t** h, const gr4hip_convert_params* p);
+int    gr4hip_convert_destroy(gr4hip_convert_t* h);
+int    gr4hip_convert_set_scale(gr4hip_convert_t* h, double scale);                      /* settingsChanged of ScalingConvert::scale (:46) */
+int    gr4hip_convert_reset(gr4hip_convert_t* h);                                        /* stream position back to 0 (only rotator ops of the hooks read it) */
+int    gr4hip_convert_ports(const gr4hip_convert_t* h, size_t* n_in, size_t* n_out, size_t* in_chunk, size_t* out_chunk); /* GR_MAKE_REFLECTABLE port lists; Resampling<> chunks */
+int    gr4hip_convert_process(gr4hip_convert_t* h, const void* const* d_in, void* const* d_out, size_t n_in, size_t* n_out, gr4hip_stream_t stream); /* processOne / processBulk (:25, :51, :73, :95, :110, :125, :140, :157, :175, :192, :210, :228, :247, :271) */
+int    gr4hip_convert_set_prologue(gr4hip_convert_t* h, const gr4hip_ewise_t* prog);     /* Merge<A, "out", Convert, "in"> (BlockMerging.hpp:126-240) */
+int    gr4hip_convert_set_epilogue(gr4hip_convert_t* h, const gr4hip_ewise_t* prog);     /* Merge<Convert, "out", B, "in"> */
+size_t gr4hip_convert_tile(const gr4hip_convert_params* p);                              /* items one workgroup of the aligned body converts (0: invalid params) */
+
 #ifdef __cplusplus
 }
 #endif
