@@ -7,6 +7,7 @@ Names, settings and error behaviour follow the reference blocks (citations relat
   Rotator                                                                     blocks/math/.../Rotator.hpp
   FrequencyEstimatorTimeDomain / FrequencyEstimatorFrequencyDomain            blocks/filter/.../FrequencyEstimator.hpp
   IQDemodulator                                                               blocks/filter/.../FrequencyEstimator.hpp
+  PowerMetrics / PowerFactor / SystemUnbalance                                blocks/electrical/.../PowerEstimators.hpp
   Chain                                                                       the runtime fusion of fir_filter -> FFT -> mag2
                                                                               (Merge<> analogue, core/.../BlockMerging.hpp:136-320)
 Blocks consume and produce torch tensors that live on the GPU (`process_bulk(x) -> y`); torch only provides the
@@ -885,6 +886,82 @@ class PowerMetrics(_Handle):
         check(lib().gr4hip_powermetrics_process(self._h, u.data_ptr(), i.data_ptr(), stride, n, ptr[0], ptr[1], ptr[2], ptr[3], ptr[4], max(n_out, 1), None,
                                                 _stream()), "PowerMetrics.process")
         return tuple(outs)
+
+
+class _ElectricalRows:
+    """the row handling PowerFactor and SystemUnbalance share: [n_phases, n] device tensors of the block's dtype, rows of unit stride a common row stride apart are
+    read in place (the layout of PowerMetrics' outputs), anything else is made contiguous first"""
+    _what = ""
+    _min_phases = 1
+
+    def __init__(self, n_phases: int = 3, dtype=torch.float32):
+        if dtype not in (torch.float32, torch.float64) or not self._min_phases <= int(n_phases) <= 16:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, self._what, f"dtype float32 or float64, n_phases in [{self._min_phases}, 16]")
+        self.n_phases = int(n_phases)
+        self.dtype = dtype
+
+    @staticmethod
+    def tile() -> int:
+        """items per workgroup of the kernels: where the aligned body hands over to the element-wise tail"""
+        return int(lib().gr4hip_electrical_tile())
+
+    def _rows(self, xs):
+        rows = []
+        for x in xs:
+            if not isinstance(x, torch.Tensor) or not x.is_cuda:
+                raise capi.Gr4HipError(capi.INVALID_ARGUMENT, self._what, "input must be a CUDA/HIP torch tensor (device-only path)")
+            if x.dim() == 1:
+                x = x.unsqueeze(0)
+            if x.dim() != 2 or x.dtype != self.dtype or x.shape[0] != self.n_phases:
+                raise capi.Gr4HipError(capi.INVALID_ARGUMENT, self._what, f"inputs must be {self.dtype} tensors of shape [{self.n_phases}, n]")
+            if rows and (x.shape != rows[0].shape or x.device != rows[0].device):
+                raise capi.Gr4HipError(capi.INVALID_ARGUMENT, self._what, "the inputs must have one shape on one device")
+            if x.shape[1] > 1 and x.stride(1) != 1 or x.shape[0] > 1 and x.stride(0) < x.shape[1]:
+                x = x.contiguous()
+            rows.append(x)
+        n = rows[0].shape[1]
+        stride = rows[0].stride(0) if self.n_phases > 1 else max(n, 1)
+        if self.n_phases > 1 and any(x.stride(0) != stride for x in rows):
+            rows, stride = [x.contiguous() for x in rows], max(n, 1)
+        return rows, n, stride
+
+
+class PowerFactor(_ElectricalRows):
+    """gr::electrical::PowerFactor<T, nPhases> (PowerEstimators.hpp:144-182), T float32 or float64.  process(P, S) takes two [n_phases, n] tensors (a 1-D tensor is
+    one phase; rows may be strided views such as PowerMetrics' outputs, read in place) and returns (power_factor, phase), each [n_phases, n]
+    (include/gr4hip.h "Power factor and system unbalance", POWER_QUALITY.md)."""
+    _what = "PowerFactor"
+    _outputs = ("power_factor", "phase")
+
+    def process(self, P: torch.Tensor, S: torch.Tensor, outputs=_outputs):
+        """`outputs`: the ones to compute; the others come back as None (their pointers are NULL in the call)"""
+        (P, S), n, stride = self._rows((P, S))
+        outs = [torch.empty((self.n_phases, n), dtype=self.dtype, device=P.device) if k in outputs else None for k in self._outputs]
+        ptr = [o.data_ptr() if o is not None else None for o in outs]
+        check(lib().gr4hip_powerfactor_process(_DTYPE_ID[self.dtype], self.n_phases, P.data_ptr(), S.data_ptr(), stride, ptr[0], ptr[1], max(n, 1), n, _stream()),
+              "PowerFactor.process")
+        return tuple(outs)
+
+    process_bulk = process
+
+
+class SystemUnbalance(_ElectricalRows):
+    """gr::electrical::SystemUnbalance<T, nPhases> (PowerEstimators.hpp:193-257), T float32 or float64, nPhases >= 2.  process(U_rms, I_rms, P) takes three
+    [n_phases, n] tensors (rows may be strided views, read in place) and returns (P_total, U_unbalance, I_unbalance), each [n]."""
+    _what = "SystemUnbalance"
+    _min_phases = 2
+    _outputs = ("P_total", "U_unbalance", "I_unbalance")
+
+    def process(self, U_rms: torch.Tensor, I_rms: torch.Tensor, P: torch.Tensor, outputs=_outputs):
+        """`outputs`: the ones to compute; the others come back as None (their pointers are NULL in the call)"""
+        (U, I, P), n, stride = self._rows((U_rms, I_rms, P))
+        outs = [torch.empty(n, dtype=self.dtype, device=U.device) if k in outputs else None for k in self._outputs]
+        ptr = [o.data_ptr() if o is not None else None for o in outs]
+        check(lib().gr4hip_unbalance_process(_DTYPE_ID[self.dtype], self.n_phases, U.data_ptr(), I.data_ptr(), P.data_ptr(), stride, ptr[0], ptr[1], ptr[2], n,
+                                             _stream()), "SystemUnbalance.process")
+        return tuple(outs)
+
+    process_bulk = process
 
 
 class SchmittEdges(NamedTuple):

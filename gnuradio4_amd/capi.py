@@ -183,6 +183,9 @@ SIGNATURES = {
     "gr4hip_powermetrics_reset": (_i, [_vp]),
     "gr4hip_powermetrics_process": (_i, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _psz, _vp]),
     "gr4hip_powermetrics_destroy": (_i, [_vp]),
+    "gr4hip_powerfactor_process": (_i, [_i, _sz, _vp, _vp, _sz, _vp, _vp, _sz, _sz, _vp]),
+    "gr4hip_unbalance_process": (_i, [_i, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
+    "gr4hip_electrical_tile": (_sz, []),
     "gr4hip_schmitt_params_default": (_i, [_vp]),
     "gr4hip_schmitt_check": (_i, [_vp]),
     "gr4hip_schmitt_segment": (_sz, []),

@@ -4,7 +4,7 @@ set -e
 cd "$(dirname "$0")"
 OUT=../../build/host
 mkdir -p $OUT
-HDRS="include/gr4/core.hpp include/gr4/converter_ops.hpp include/gr4/blocks.hpp include/gr4/merge.hpp include/gr4/hip.hpp include/gr4/plugin.hpp include/gr4/grc.hpp ../../include/gr4hip.h"
+HDRS="include/gr4/core.hpp include/gr4/converter_ops.hpp include/gr4/electrical_ops.hpp include/gr4/blocks.hpp include/gr4/merge.hpp include/gr4/hip.hpp include/gr4/plugin.hpp include/gr4/grc.hpp ../../include/gr4hip.h"
 CXX="g++ -std=c++20 -Wall -Wextra -Iinclude"
 LINK="-L.. -lgr4hip -Wl,-rpath,\$ORIGIN/../../gnuradio4_amd -Wl,-rpath,/opt/rocm/lib"
 stale() { # target sources...
@@ -40,6 +40,7 @@ if stale $OUT/test_host_schmitt_trigger tests/test_host_schmitt_trigger.cpp; the
 if stale $OUT/test_host_svd_denoiser tests/test_host_svd_denoiser.cpp; then $CXX -O2 tests/test_host_svd_denoiser.cpp -o $OUT/test_host_svd_denoiser -ldl & pids+=($!); fi
 if stale $OUT/test_host_signal_generator tests/test_host_signal_generator.cpp; then $CXX -O2 tests/test_host_signal_generator.cpp -o $OUT/test_host_signal_generator $LINK & pids+=($!); fi
 if stale $OUT/test_host_converter tests/test_host_converter.cpp; then $CXX -O1 tests/test_host_converter.cpp -o $OUT/test_host_converter $LINK & pids+=($!); fi
+if stale $OUT/test_host_electrical tests/test_host_electrical.cpp; then $CXX -O2 tests/test_host_electrical.cpp -o $OUT/test_host_electrical -ldl & pids+=($!); fi
 for p in "${pids[@]}"; do wait $p; done
 if [ -n "$PLUGIN_OBJS" ]; then $CXX -fPIC -shared -fvisibility=hidden $PLUGIN_OBJS -o ../libgr4hip_blocks.so -L.. -lgr4hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,/opt/rocm/lib; fi
 echo "built $(realpath $OUT)"

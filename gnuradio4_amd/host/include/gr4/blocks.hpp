@@ -9,6 +9,7 @@
 
 #include "../../../../include/gr4hip.h" // host-side design functions only (gr4hip_fir_design / gr4hip_iir_design / gr4hip_window_create: no device needed)
 #include "converter_ops.hpp"
+#include "electrical_ops.hpp"
 #include "core.hpp"
 
 namespace gr::testing {
@@ -557,6 +558,14 @@ struct SvdDenoiser : Block<SvdDenoiser<T>> {
 };
 } // namespace gr::filter
 namespace gr::electrical {
+namespace detail {
+template <typename P>
+std::span<typename P::value_type> electrical_out_span(P& port, std::size_t n, std::vector<typename P::value_type>& scratch) { // an unconnected port computes into scratch
+    if (port.connected()) return port.buffer->write_span(n);
+    scratch.resize(n);
+    return scratch;
+}
+} // namespace detail
 GR_REGISTER_BLOCK("gr::electrical::ThreePhasePowerMetrics", gr::electrical::PowerMetrics, ([T], 3UZ), [ float ])
 GR_REGISTER_BLOCK("gr::electrical::SinglePhasePowerMetrics", gr::electrical::PowerMetrics, ([T], 1UZ), [ float ])
 // PowerMetrics<T, nPhases> (blocks/electrical/.../PowerEstimators.hpp:21-131): per phase a voltage and a current input; active, reactive and apparent power and
@@ -596,6 +605,92 @@ template <typename T>
 using ThreePhasePowerMetrics = PowerMetrics<T, 3U>;
 template <typename T>
 using SinglePhasePowerMetrics = PowerMetrics<T, 1U>;
+
+GR_REGISTER_BLOCK("gr::electrical::SinglePhasePowerFactorCalculator", gr::electrical::PowerFactor, ([T], 1UZ), [ float, double ])
+GR_REGISTER_BLOCK("gr::electrical::ThreePhasePowerFactorCalculator", gr::electrical::PowerFactor, ([T], 3UZ), [ float, double ])
+// PowerFactor<T, nPhases> (blocks/electrical/.../PowerEstimators.hpp:144-182): per phase cos(phi) = P / S clamped to [-1, 1] and phi = acos of it.  Ports and names
+// are the reference's.  The arithmetic is gr4/electrical_ops.hpp, the device kernels' own (csrc/electrical.hip): host and device agree bit for bit on
+// power_factor; phase is std::acos in T here, like the reference (POWER_QUALITY.md).  The gr::UncertainValue<T> instantiations are left out, as for PowerMetrics.
+template <typename T, std::size_t nPhases>
+    requires std::floating_point<T>
+struct PowerFactor : Block<PowerFactor<T, nPhases>> {
+    std::vector<PortIn<T>>  P{nPhases}; // active power
+    std::vector<PortIn<T>>  S{nPhases}; // apparent power
+    std::vector<PortOut<T>> power_factor{nPhases};
+    std::vector<PortOut<T>> phase{nPhases};
+    GR_MAKE_REFLECTABLE(PowerFactor, P, S, power_factor, phase);
+    work::Status processBulk(std::span<const std::span<const T>> pIn, std::span<const std::span<const T>> sIn, std::span<const std::span<T>> powerFactorOut,
+                             std::span<const std::span<T>> phaseAngle) { // (:161-181)
+        namespace ops = gr4::electrical_ops;
+        for (std::size_t phaseIdx = 0; phaseIdx < nPhases; ++phaseIdx) {
+            for (std::size_t n = 0; n < pIn[phaseIdx].size(); ++n) {
+                const T cos_phi             = ops::power_factor<T>(pIn[phaseIdx][n], sIn[phaseIdx][n]);
+                powerFactorOut[phaseIdx][n] = cos_phi;
+                phaseAngle[phaseIdx][n]     = ops::acos_of(cos_phi);
+            }
+        }
+        return work::Status::OK;
+    }
+    work::Status hostWork(std::size_t nIn, std::size_t nOut) {
+        std::vector<std::span<const T>> p, s;
+        std::vector<std::span<T>>       f, a;
+        std::vector<std::vector<T>>     scratch(2 * nPhases);
+        for (std::size_t k = 0; k < nPhases; ++k) {
+            p.push_back(P[k].buffer->read_span(nIn));
+            s.push_back(S[k].buffer->read_span(nIn));
+            f.push_back(detail::electrical_out_span(power_factor[k], nOut, scratch[2 * k]));
+            a.push_back(detail::electrical_out_span(phase[k], nOut, scratch[2 * k + 1]));
+        }
+        return processBulk(p, s, f, a);
+    }
+};
+template <typename T>
+using SinglePhasePowerFactorCalculator = PowerFactor<T, 1>;
+template <typename T>
+using ThreePhasePowerFactorCalculator = PowerFactor<T, 3>;
+
+GR_REGISTER_BLOCK("gr::electrical::TwoPhaseSystemUnbalanceCalculator", gr::electrical::SystemUnbalance, ([T], 2UZ), [ float, double ])
+GR_REGISTER_BLOCK("gr::electrical::ThreePhaseSystemUnbalanceCalculator", gr::electrical::SystemUnbalance, ([T], 3UZ), [ float, double ])
+// SystemUnbalance<T, nPhases> (:193-257): the total active power and the voltage and current unbalance (largest deviation from the phases' average, in percent of
+// it) of a multi-phase system.  Ports and names are the reference's; the arithmetic is gr4/electrical_ops.hpp, which keeps the reference's two different
+// reductions (std::transform_reduce / std::max for the voltage, std::max_element for the current): host and device agree bit for bit on all three outputs.
+template <typename T, std::size_t nPhases>
+    requires(std::floating_point<T> && (nPhases > 1)) // unbalance calculation requires at least two phases
+struct SystemUnbalance : Block<SystemUnbalance<T, nPhases>> {
+    std::vector<PortIn<T>> voltage_rms_inputs{nPhases};  // U_rms_in
+    std::vector<PortIn<T>> current_rms_inputs{nPhases};  // I_rms_in
+    std::vector<PortIn<T>> active_power_inputs{nPhases}; // P_in
+    PortOut<T>             total_active_power_output;    // P_total_out
+    PortOut<T>             voltage_unbalance_output;     // U_unbalance_out
+    PortOut<T>             current_unbalance_output;     // I_unbalance_out
+    GR_MAKE_REFLECTABLE(SystemUnbalance, voltage_rms_inputs, current_rms_inputs, active_power_inputs, total_active_power_output, voltage_unbalance_output, current_unbalance_output);
+    work::Status processBulk(std::span<const std::span<const T>> rmsUIn, std::span<const std::span<const T>> rmsIIn, std::span<const std::span<const T>> PIn,
+                             std::span<T> totalP, std::span<T> unbalancedU, std::span<T> unbalancedI) { // (:217-256)
+        namespace ops = gr4::electrical_ops;
+        constexpr int N = static_cast<int>(nPhases);
+        for (std::size_t n = 0; n < rmsUIn[0].size(); ++n) {
+            totalP[n]      = ops::sum_of<T>([&](int i) { return PIn[static_cast<std::size_t>(i)][n]; }, N);
+            unbalancedU[n] = ops::voltage_unbalance<T>([&](int i) { return rmsUIn[static_cast<std::size_t>(i)][n]; }, N);
+            unbalancedI[n] = ops::current_unbalance<T>([&](int i) { return rmsIIn[static_cast<std::size_t>(i)][n]; }, N);
+        }
+        return work::Status::OK;
+    }
+    work::Status hostWork(std::size_t nIn, std::size_t nOut) {
+        std::vector<std::span<const T>> u, c, p;
+        std::vector<T>                  s0, s1, s2;
+        for (std::size_t k = 0; k < nPhases; ++k) {
+            u.push_back(voltage_rms_inputs[k].buffer->read_span(nIn));
+            c.push_back(current_rms_inputs[k].buffer->read_span(nIn));
+            p.push_back(active_power_inputs[k].buffer->read_span(nIn));
+        }
+        return processBulk(u, c, p, detail::electrical_out_span(total_active_power_output, nOut, s0), detail::electrical_out_span(voltage_unbalance_output, nOut, s1),
+                           detail::electrical_out_span(current_unbalance_output, nOut, s2));
+    }
+};
+template <typename T>
+using TwoPhaseSystemUnbalanceCalculator = SystemUnbalance<T, 2>;
+template <typename T>
+using ThreePhaseSystemUnbalanceCalculator = SystemUnbalance<T, 3>;
 } // namespace gr::electrical
 namespace gr::trigger {
 enum class InterpolationMethod : int { NO_INTERPOLATION = 0, BASIC_LINEAR_INTERPOLATION = 1, LINEAR_INTERPOLATION = 2, POLYNOMIAL_INTERPOLATION = 3 }; // SchmittTrigger.hpp:17-22

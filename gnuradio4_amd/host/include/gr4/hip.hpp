@@ -1076,6 +1076,83 @@ struct Kernel<gr::electrical::PowerMetrics<float, N>> {
     }
 };
 
+// PowerFactor<T, N> and SystemUnbalance<T, N> (PowerEstimators.hpp:144-257), after the pattern of PowerMetrics: the input spans go to HBM as rows of one buffer
+// in one copy, ONE stateless launch (gr4hip_powerfactor_process / gr4hip_unbalance_process), one copy back per output that has a connected port (the others are
+// NULL pointers in the call and are not computed).  Multi-port blocks stay outside hip::plan runs: the edges between PowerMetrics and these two are host spans.
+namespace detail {
+template <typename T, std::size_t R>
+char* electrical_rows_to_device(Offload* st, const std::array<std::vector<gr::PortIn<T>>*, R>& groups, std::size_t N, std::size_t nIn) {
+    const std::size_t b   = nIn * sizeof(T);
+    char*             hin = static_cast<char*>(st->h_in.ensure(R * N * b));
+    for (std::size_t g = 0; g < R; ++g)
+        for (std::size_t k = 0; k < N; ++k) std::memcpy(hin + (g * N + k) * b, (*groups[g])[k].buffer->read_span(nIn).data(), b);
+    char* din = static_cast<char*>(st->d_in.ensure(R * N * b));
+    check(gr4hip_memcpy_h2d(din, hin, R * N * b, nullptr), "h2d");
+    return din;
+}
+} // namespace detail
+template <typename T, std::size_t N>
+struct Kernel<gr::electrical::PowerFactor<T, N>> {
+    using B = gr::electrical::PowerFactor<T, N>;
+    static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
+        try {
+            Offload*          st = offload_state<Offload>(blk);
+            const std::size_t bi = nIn * sizeof(T), bo = nOut * sizeof(T);
+            if (nOut != nIn) throw std::runtime_error("PowerFactor: one output per input");
+            char* din  = detail::electrical_rows_to_device<T, 2>(st, {&blk.P, &blk.S}, N, nIn);
+            char* dout = static_cast<char*>(st->d_out.ensure(2 * N * bo));
+            std::vector<gr::PortOut<T>>* ports[2] = {&blk.power_factor, &blk.phase};
+            void*                        dptr[2];
+            for (std::size_t q = 0; q < 2; ++q) {
+                bool any = false;
+                for (auto& port : *ports[q]) any = any || port.connected();
+                dptr[q] = any ? dout + q * N * bo : nullptr;
+            }
+            check(gr4hip_powerfactor_process(dtype_of<T>(), N, din, din + N * bi, nIn, dptr[0], dptr[1], nOut, nIn, nullptr), "gr4hip_powerfactor_process");
+            char* hout = static_cast<char*>(st->h_out.ensure(2 * N * bo));
+            for (std::size_t q = 0; q < 2; ++q)
+                if (dptr[q]) check(gr4hip_memcpy_d2h(hout + q * N * bo, dout + q * N * bo, N * bo, nullptr), "d2h");
+            check(gr4hip_stream_synchronize(nullptr), "sync");
+            for (std::size_t q = 0; q < 2; ++q) {
+                if (!dptr[q]) continue;
+                for (std::size_t k = 0; k < N; ++k)
+                    if ((*ports[q])[k].connected()) std::memcpy((*ports[q])[k].buffer->write_span(nOut).data(), hout + (q * N + k) * bo, bo);
+            }
+            return work::Status::OK;
+        } catch (const std::exception& e) {
+            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
+            return work::Status::ERROR; // never a silent host fallback
+        }
+    }
+};
+template <typename T, std::size_t N>
+struct Kernel<gr::electrical::SystemUnbalance<T, N>> {
+    using B = gr::electrical::SystemUnbalance<T, N>;
+    static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
+        try {
+            Offload*          st = offload_state<Offload>(blk);
+            const std::size_t bi = nIn * sizeof(T), bo = nOut * sizeof(T);
+            if (nOut != nIn) throw std::runtime_error("SystemUnbalance: one output per input");
+            char* din  = detail::electrical_rows_to_device<T, 3>(st, {&blk.voltage_rms_inputs, &blk.current_rms_inputs, &blk.active_power_inputs}, N, nIn);
+            char* dout = static_cast<char*>(st->d_out.ensure(3 * bo));
+            gr::PortOut<T>* ports[3] = {&blk.total_active_power_output, &blk.voltage_unbalance_output, &blk.current_unbalance_output};
+            void*           dptr[3];
+            for (std::size_t q = 0; q < 3; ++q) dptr[q] = ports[q]->connected() ? dout + q * bo : nullptr;
+            check(gr4hip_unbalance_process(dtype_of<T>(), N, din, din + N * bi, din + 2 * N * bi, nIn, dptr[0], dptr[1], dptr[2], nIn, nullptr), "gr4hip_unbalance_process");
+            char* hout = static_cast<char*>(st->h_out.ensure(3 * bo));
+            for (std::size_t q = 0; q < 3; ++q)
+                if (dptr[q]) check(gr4hip_memcpy_d2h(hout + q * bo, dout + q * bo, bo, nullptr), "d2h");
+            check(gr4hip_stream_synchronize(nullptr), "sync");
+            for (std::size_t q = 0; q < 3; ++q)
+                if (dptr[q]) std::memcpy(ports[q]->buffer->write_span(nOut).data(), hout + q * bo, bo);
+            return work::Status::OK;
+        } catch (const std::exception& e) {
+            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
+            return work::Status::ERROR; // never a silent host fallback
+        }
+    }
+};
+
 // SchmittTrigger<T, Method>: the chunk goes to HBM, one gr4hip_schmitt_process (room for an edge per sample), the count comes back, then that many edges.  The
 // samples pass through on the host, bit for bit.  Every edge with a non-empty name becomes a tag at sample + edge_idx (gr4/blocks.hpp states the deviations
 // from the reference's processBulk).  offset / threshold by settings reset the handle's detector; any other update leaves it alone.

@@ -55,6 +55,15 @@ void register_schmitt(BlockRegistry& r) { // basic/Trigger.hpp:11-13; SchmittTri
 }
 
 template <typename T>
+void register_power_quality(BlockRegistry& r) { // PowerEstimators.hpp:141-142, 190-191; the gr::UncertainValue<T> instantiations are left out, as for PowerMetrics
+    using namespace gr::electrical;
+    r.insert<SinglePhasePowerFactorCalculator<T>>(named<T>("gr::electrical::SinglePhasePowerFactorCalculator"));
+    r.insert<ThreePhasePowerFactorCalculator<T>>(named<T>("gr::electrical::ThreePhasePowerFactorCalculator"));
+    r.insert<TwoPhaseSystemUnbalanceCalculator<T>>(named<T>("gr::electrical::TwoPhaseSystemUnbalanceCalculator"));
+    r.insert<ThreePhaseSystemUnbalanceCalculator<T>>(named<T>("gr::electrical::ThreePhaseSystemUnbalanceCalculator"));
+}
+
+template <typename T>
 void register_signal_generator(BlockRegistry& r) { // basic/SignalGenerator.hpp:25 registers every fundamental type; the four with a device implementation are offered
     r.insert<gr::basic::SignalGenerator<T>>(named<T>("gr::basic::SignalGenerator"));
     r.insert<gr::hip::SignalSource<T>>(named<T>("gr::hip::SignalSource"));
@@ -98,6 +107,7 @@ const bool registered = [] {
     r.insert<IQDemodulatorDecimating<double>>(named<double>("gr::filter::IQDemodulator", ", gr::Resampling<1024U, 1U, false>"));
     r.insert<gr::electrical::SinglePhasePowerMetrics<float>>(named<float>("gr::electrical::SinglePhasePowerMetrics")); // PowerEstimators.hpp:18-19
     r.insert<gr::electrical::ThreePhasePowerMetrics<float>>(named<float>("gr::electrical::ThreePhasePowerMetrics"));
+    register_power_quality<float>(r); register_power_quality<double>(r);
     register_schmitt<std::int16_t>(r); register_schmitt<std::int32_t>(r); register_schmitt<float>(r); register_schmitt<double>(r);
     r.insert<SvdDenoiser<float>>(named<float>("gr::filter::SvdDenoiser")); // SvdDenoiser.hpp:12
     r.insert<SvdDenoiser<double>>(named<double>("gr::filter::SvdDenoiser"));

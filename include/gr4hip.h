@@ -667,6 +667,31 @@ int    gr4hip_powermetrics_process(gr4hip_powermetrics_t* h, const float* d_u, c
                                    float* d_Urms, float* d_Irms, size_t out_stride, size_t* n_out, gr4hip_stream_t stream);
 int    gr4hip_powermetrics_destroy(gr4hip_powermetrics_t* h);
 
+/* ------------------------------------------------------------------------------------------------ Power factor and system unbalance (PowerEstimators.hpp:144-257)
+ * The two blocks PowerMetrics feeds, stateless and per sample like gr4hip_math_nary; the rows have the stride layout of gr4hip_powermetrics_process, so its
+ * outputs chain straight in without a copy.  dtype is GR4HIP_F32 or GR4HIP_F64 (the UncertainValue instantiations are left out, as for PowerMetrics).  The
+ * arithmetic is gr4/electrical_ops.hpp, shared with the host mirror blocks; design notes: POWER_QUALITY.md.
+ *
+ * gr4hip_powerfactor_process replaces gr::electrical::PowerFactor<T, nPhases>::processBulk (:161-181): per phase and sample c = (S != 0) ? P / S : 0, clamped to
+ * [-1, 1] as std::clamp does (a NaN stays NaN, -0.0 stays -0.0); power_factor = c, phase = acos(c) (float samples: acos in float64 on the float argument, rounded
+ * once).  d_P / d_S: n_phases (1 ... 16) rows of n elements, in_stride elements apart; d_power_factor / d_phase: the same shape, out_stride apart.
+ *
+ * gr4hip_unbalance_process replaces gr::electrical::SystemUnbalance<T, nPhases>::processBulk (:217-256): per sample over the n_phases (2 ... 16) rows of d_Urms,
+ * d_Irms and d_P, in_stride apart: P_total = ((0 + P_0) + P_1) + ...; for U and I avg = (((0 + x_0) + x_1) + ...) / n_phases; the voltage's largest deviation is
+ * the left fold m = (m < |x_i - avg|) ? |x_i - avg| : m from 0 (std::transform_reduce with std::max, :234-237), the current's is |best - avg| of the
+ * std::max_element under |a - avg| < |b - avg| (:243-245); unbalance = (avg > 0) ? (dmax / avg) * 100 : 0.  The two forms differ on one input: every phase +inf
+ * gives 0 for the voltage and NaN for the current.  Each output is ONE row of n elements.
+ *
+ * Both: any output pointer may be NULL (an unconnected port; what only it needs is neither read nor computed).  n == 0 is OK and writes nothing.  Pointers need
+ * their element's alignment only; rows that share a misalignment from 16 bytes move 16 bytes per lane, a row that disagrees is moved element by element.
+ * GR4HIP_INVALID_ARGUMENT, checked on the host before any device work: a dtype other than F32 / F64, a phase count outside the range, a NULL input, a pointer not
+ * aligned to its element, a stride smaller than n, an input overlapping an output.  The call queues one kernel on `stream` and returns. */
+int    gr4hip_powerfactor_process(int dtype, size_t n_phases, const void* d_P, const void* d_S, size_t in_stride, void* d_power_factor, void* d_phase, size_t out_stride,
+                                  size_t n, gr4hip_stream_t stream);
+int    gr4hip_unbalance_process(int dtype, size_t n_phases, const void* d_Urms, const void* d_Irms, const void* d_P, size_t in_stride, void* d_P_total,
+                                void* d_U_unbalance, void* d_I_unbalance, size_t n, gr4hip_stream_t stream);
+size_t gr4hip_electrical_tile(void); /* items per workgroup of both kernels: tests place their edges by it */
+
 /* ------------------------------------------------------------------------------------------------ Schmitt trigger (algorithm/.../SchmittTrigger.hpp:39-357)
  * gr::trigger::SchmittTrigger<T, Method, 32>, the detector of gr::blocks::basic::SchmittTrigger (blocks/basic/.../Trigger.hpp:45: N_HISTORY = 32), for T in
  * {int16, int32, float, double}: processOne (:103-222) applied to every sample of the stream exactly once, in order, whatever the chunking into calls; the
