@@ -1109,6 +1109,149 @@ class SvdDenoiser(_Handle):
         return int(s.value)
 
 
+_SAVGOL_DTYPES = {torch.float32: capi.F32, torch.float64: capi.F64}
+
+
+def _savgol_dtype(dtype, who: str) -> int:
+    if dtype not in _SAVGOL_DTYPES:
+        raise capi.Gr4HipError(capi.INVALID_ARGUMENT, who, f"dtype {dtype} (float32, float64)")
+    return _SAVGOL_DTYPES[dtype]
+
+
+def design_savitzky_golay(dtype=torch.float32, window_size: int = 11, poly_order: int = 4, deriv_order: int = 0, delta: float = 1.0, alignment: str = "Centred"):
+    """computeCoefficients<T> (algorithm/filter/SavitzkyGolay.hpp:93-151) through gr4hip_savgol_design (host code, no device): (coefficients as a numpy array of
+    T, capi.SavgolInfo).  coeffs[k] belongs to the offset k - D; "Causal", or anything else = Centred."""
+    did = _savgol_dtype(dtype, "design_savitzky_golay")
+    c = np.empty(max(int(window_size), 1), _NP_DTYPE[did])
+    info = capi.SavgolInfo()
+    check(lib().gr4hip_savgol_design(did, int(window_size), int(poly_order), int(deriv_order), float(delta),
+                                     capi.SAVGOL_CAUSAL if alignment == "Causal" else capi.SAVGOL_CENTRED, c.ctypes.data, C.byref(info)), "design_savitzky_golay")
+    return c, info
+
+
+class SavitzkyGolayFilter:
+    """gr::filter::SavitzkyGolayFilter<T> (blocks/filter/.../SavitzkyGolayFilter.hpp:17-81) for T in {float32, float64}: the streaming filter
+    y[n] = sum_k c[k] x[n - (W - 1) + k] over a history of zeros (SavitzkyGolay.hpp:226-233, BoundaryPolicy::Default), which is fir_filter with b[k] = c[W - 1 - k]:
+    the library's design on its FIR handles (IEEE float32 kernels for float, the FP64 kernel for double).  set_params designs again and clears the history, as
+    setParameters does (:253-260); delta = 1 / T(sample_rate) when sample_rate > 0, else 1 (:49-52)."""
+    _names = ("window_size", "poly_order", "deriv_order", "sample_rate", "alignment")
+
+    def __init__(self, dtype=torch.float32, window_size: int = 11, poly_order: int = 4, deriv_order: int = 0, sample_rate: float = 1.0, alignment: str = "Centred"):
+        self._np = _NP_DTYPE[_savgol_dtype(dtype, "SavitzkyGolayFilter")]
+        self.dtype = dtype
+        self._s = dict(window_size=int(window_size), poly_order=int(poly_order), deriv_order=int(deriv_order), sample_rate=float(sample_rate), alignment=str(alignment))
+        self._fir = None
+        self._design()
+
+    def _design(self):
+        s = self._s
+        rate = self._np(np.float32(s["sample_rate"]))  # the setting is a float (:40), cast to T (:49)
+        delta = self._np(1) / rate if rate > 0 else self._np(1)
+        self.coeffs, self.info = design_savitzky_golay(self.dtype, s["window_size"], s["poly_order"], s["deriv_order"], float(delta), s["alignment"])
+        b = self.coeffs[::-1].copy()
+        if self._fir is None:
+            self._fir = fir_filter(b, self.dtype)
+            if self.dtype == torch.float32:
+                self._fir.set_algo(capi.FIR_EXACT_F32)
+        else:
+            self._fir.settings_changed(b)
+            self._fir.reset()  # set_taps keeps the FIR history; the reference's setParameters clears it
+
+    def __getattr__(self, name):
+        if name in type(self)._names:
+            return self.__dict__["_s"][name]
+        raise AttributeError(name)
+
+    def set_params(self, **settings):
+        for k in settings:
+            if k not in self._names:
+                raise TypeError(f"SavitzkyGolayFilter: unknown setting '{k}'")
+        old = dict(self._s)
+        self._s.update({k: (str(v) if k == "alignment" else float(v) if k == "sample_rate" else int(v)) for k, v in settings.items()})
+        try:
+            self._design()
+        except Exception:
+            self._s = old
+            raise
+
+    def reset(self):
+        self._fir.reset()
+
+    def close(self):
+        self._fir.close()
+
+    def process_bulk(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return self._fir.process_bulk(x, out)
+
+
+class SavitzkyGolayDataSetFilter(_Handle):
+    """gr::filter::SavitzkyGolayDataSetFilter<T> (blocks/filter/.../SavitzkyGolayFilter.hpp:87-164) for T in {float32, float64}: zero-phase (forward-backward)
+    Savitzky-Golay filtering, both passes in one launch (include/gr4hip.h "Savitzky-Golay", SAVITZKY_GOLAY.md).  process(x[batch, n]) filters every row on its own;
+    the block itself filters the whole flat signal_values as one row.  boundary_policy: "Replicate", or anything else = Reflect (:126-128)."""
+    _destroy = "gr4hip_savgol_zp_destroy"
+    _names = ("window_size", "poly_order", "deriv_order", "boundary_policy")
+
+    def __init__(self, dtype=torch.float32, window_size: int = 11, poly_order: int = 4, deriv_order: int = 0, boundary_policy: str = "Reflect"):
+        super().__init__()
+        self._did = _savgol_dtype(dtype, "SavitzkyGolayDataSetFilter")
+        self.dtype = dtype
+        self._s = dict(window_size=int(window_size), poly_order=int(poly_order), deriv_order=int(deriv_order), boundary_policy=str(boundary_policy))
+        p = self._params(self._s)
+        check(lib().gr4hip_savgol_zp_create(C.byref(self._h), C.byref(p)), "SavitzkyGolayDataSetFilter")
+
+    @staticmethod
+    def tile() -> int:
+        """outputs per workgroup of the kernel: a row of at most this many samples is one workgroup's"""
+        return int(lib().gr4hip_savgol_zp_tile())
+
+    def _params(self, s):
+        return capi.SavgolZpParams(self._did, s["window_size"], s["poly_order"], s["deriv_order"],
+                                   capi.SAVGOL_REPLICATE if s["boundary_policy"] == "Replicate" else capi.SAVGOL_REFLECT)
+
+    def __getattr__(self, name):
+        if name in type(self)._names:
+            return self.__dict__["_s"][name]
+        raise AttributeError(name)
+
+    def set_params(self, **settings):
+        for k in settings:
+            if k not in self._names:
+                raise TypeError(f"SavitzkyGolayDataSetFilter: unknown setting '{k}'")
+        s = dict(self._s)
+        s.update({k: (str(v) if k == "boundary_policy" else int(v)) for k, v in settings.items()})
+        p = self._params(s)
+        check(lib().gr4hip_savgol_zp_set_params(self._h, C.byref(p)), "SavitzkyGolayDataSetFilter.set_params")
+        self._s = s
+
+    def coefficients(self):
+        """(the W coefficients in T the kernel filters with, capi.SavgolInfo)"""
+        info = capi.SavgolInfo()
+        c = np.empty(max(self._s["window_size"], 1), _NP_DTYPE[self._did])
+        check(lib().gr4hip_savgol_zp_coeffs(self._h, c.ctypes.data, C.byref(info)), "SavitzkyGolayDataSetFilter.coefficients")
+        return c, info
+
+    def process(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x: [n] or [batch, n], rows a stride apart (a column slice of a wider tensor is taken as it is, without a copy)"""
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "SavitzkyGolayDataSetFilter", "input must be a CUDA/HIP torch tensor (device-only path)")
+        if x.dtype != self.dtype or x.dim() not in (1, 2):
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "SavitzkyGolayDataSetFilter", f"input must be a 1-D or 2-D {self.dtype} tensor")
+        x2 = x if x.dim() == 2 else x.unsqueeze(0)
+        if x2.numel() and (x2.stride(1) != 1 or (x2.shape[0] > 1 and x2.stride(0) < x2.shape[1])):
+            x2 = x2.contiguous()
+        batch, n = x2.shape
+        if out is None:
+            y = torch.empty_like(x2) if x2.is_contiguous() else torch.empty_strided(x2.shape, x2.stride(), dtype=x2.dtype, device=x2.device)
+        else:
+            y = out if out.dim() == 2 else out.unsqueeze(0)
+            if (not y.is_cuda or y.device != x2.device or y.dtype != self.dtype or y.shape != x2.shape or (n and y.stride(1) != 1)
+                    or (batch > 1 and y.stride(0) != x2.stride(0))):
+                raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "SavitzkyGolayDataSetFilter.process", "out must be a device tensor of the input's dtype, shape and row stride")
+        stride = x2.stride(0) if batch > 1 else max(n, 1)
+        check(lib().gr4hip_savgol_zp_process(self._h, x2.data_ptr(), y.data_ptr(), n, batch, stride, _stream()), "SavitzkyGolayDataSetFilter.process")
+        return y if x.dim() == 2 else y[0]
+
+
 class SignalGenerator(_Handle):
     """gr::basic::SignalGenerator<T> (blocks/basic/.../SignalGenerator.hpp:25-87) as a device source for T in {float32, float64, complex64, int16}: sample n is what
     the n-th generateSample() of the reference's core returns, whatever the cutting into calls (include/gr4hip.h "Signal generator", SIGNAL_GENERATOR.md).

@@ -226,6 +226,14 @@ SIGNATURES = {
     "gr4hip_convert_set_prologue": (_i, [_vp, _vp]),
     "gr4hip_convert_set_epilogue": (_i, [_vp, _vp]),
     "gr4hip_convert_tile": (_sz, [_vp]),
+    "gr4hip_savgol_design": (_i, [_i, _sz, _sz, _sz, _d, _i, _vp, _vp]),
+    "gr4hip_savgol_pinv_row": (_i, [_i, _sz, _sz, _sz, _i, _vp, _vp]),
+    "gr4hip_savgol_zp_tile": (_sz, []),
+    "gr4hip_savgol_zp_create": (_i, [_pvp, _vp]),
+    "gr4hip_savgol_zp_set_params": (_i, [_vp, _vp]),
+    "gr4hip_savgol_zp_coeffs": (_i, [_vp, _vp, _vp]),
+    "gr4hip_savgol_zp_process": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp]),
+    "gr4hip_savgol_zp_destroy": (_i, [_vp]),
 }
 
 class FilterParams(C.Structure):
@@ -288,6 +296,22 @@ CONVERT_KINDS = ["Convert", "ScalingConvert", "Abs", "Real", "Imag", "Arg", "Rad
 class ConvertParams(C.Structure):
     """gr4hip_convert_params: which of the fourteen converter blocks (ConverterBlocks.hpp), its port types and ScalingConvert's scale"""
     _fields_ = [("kind", _i), ("in_dtype", _i), ("out_dtype", _i), ("scale", _d)]
+
+
+SAVGOL_CENTRED, SAVGOL_CAUSAL = range(2)
+SAVGOL_REFLECT, SAVGOL_REPLICATE = range(2)
+SAVGOL_ZP_MAX_WINDOW = 255
+
+
+class SavgolInfo(C.Structure):
+    """gr4hip_savgol_info: the clamped settings of a Savitzky-Golay design, the kept rank of its truncated pseudo-inverse and the singular values that decided it"""
+    _fields_ = [("window_size", C.c_size_t), ("poly_order", C.c_size_t), ("deriv_order", C.c_size_t), ("rank", C.c_size_t), ("sigma_max", _d),
+                ("sigma_min_kept", _d), ("threshold", _d), ("ambiguous", _i)]
+
+
+class SavgolZpParams(C.Structure):
+    """gr4hip_savgol_zp_params: the sample type and the settings of gr::filter::SavitzkyGolayDataSetFilter<T> (SavitzkyGolayFilter.hpp:111-114)"""
+    _fields_ = [("dtype", _i), ("window_size", C.c_size_t), ("poly_order", C.c_size_t), ("deriv_order", C.c_size_t), ("boundary_policy", _i)]
 
 
 LOWPASS, HIGHPASS, BANDPASS, BANDSTOP = range(4)

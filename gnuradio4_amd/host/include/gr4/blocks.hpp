@@ -556,6 +556,146 @@ struct SvdDenoiser : Block<SvdDenoiser<T>> {
         return work::Status::ERROR;
     }
 };
+
+// ---- Savitzky-Golay (blocks/filter/.../SavitzkyGolayFilter.hpp:17-164 over algorithm/filter/SavitzkyGolay.hpp).  Members, names, defaults and the reflected sets are
+// the reference's.  The coefficients come from gr4hip_savgol_design (host code of libgr4hip.so, like the filter design behind BasicFilter: the float design keeps
+// the reference's truncated pseudo-inverse, SAVITZKY_GOLAY.md); the host bodies are the reference's plain loops in T, the device paths are in gr4/hip.hpp.
+namespace savitzky_golay {
+template <typename T>
+[[nodiscard]] inline std::vector<T> design(std::size_t window_size, std::size_t poly_order, std::size_t deriv_order, T delta, bool causal) { // computeCoefficients<T> (:93-151)
+    std::vector<T> c(std::max<std::size_t>(window_size, 1));
+    const int      rc = gr4hip_savgol_design(std::is_same_v<T, float> ? GR4HIP_F32 : GR4HIP_F64, window_size, poly_order, deriv_order, static_cast<double>(delta),
+                                             causal ? GR4HIP_SAVGOL_CAUSAL : GR4HIP_SAVGOL_CENTRED, c.data(), nullptr);
+    if (rc != GR4HIP_OK) throw std::invalid_argument(std::string("Savitzky-Golay design: ") + gr4hip_last_error());
+    return c;
+}
+[[nodiscard]] constexpr std::size_t reflectIndex(std::ptrdiff_t i, std::size_t N) noexcept { // (:51-64)
+    if (N == 0) return 0;
+    if (i < 0) i = -i - 1;
+    const auto period = static_cast<std::ptrdiff_t>(2 * N);
+    i %= period;
+    if (i >= static_cast<std::ptrdiff_t>(N)) i = period - i - 1;
+    return static_cast<std::size_t>(i);
+}
+[[nodiscard]] constexpr std::size_t replicateIndex(std::ptrdiff_t i, std::size_t N) noexcept { // (:66-77)
+    if (N == 0 || i < 0) return 0;
+    return i >= static_cast<std::ptrdiff_t>(N) ? N - 1 : static_cast<std::size_t>(i);
+}
+template <typename T>
+inline void apply(std::span<const T> in, std::span<T> out, std::span<const T> coeffs, bool replicate) { // apply (:156-172), Centred
+    const std::size_t N = in.size(), W = coeffs.size();
+    if (N == 0 || W == 0 || out.size() < N) return;
+    const auto D = static_cast<std::ptrdiff_t>((W - 1) / 2);
+    for (std::size_t n = 0; n < N; ++n) {
+        T acc{0};
+        for (std::size_t k = 0; k < W; ++k) {
+            const auto idx = static_cast<std::ptrdiff_t>(n) + static_cast<std::ptrdiff_t>(k) - D;
+            acc += coeffs[k] * in[replicate ? replicateIndex(idx, N) : reflectIndex(idx, N)];
+        }
+        out[n] = acc;
+    }
+}
+template <typename T>
+inline void applyZeroPhase(std::span<const T> in, std::span<T> out, std::span<const T> coeffs, bool replicate) { // (:177-193)
+    const std::size_t N = in.size();
+    if (N == 0 || coeffs.empty() || out.size() < N) return;
+    std::vector<T> temp(N), temp2(N);
+    apply<T>(in, temp, coeffs, replicate);
+    std::reverse(temp.begin(), temp.end());
+    apply<T>(std::span<const T>(temp), temp2, coeffs, replicate);
+    std::reverse(temp2.begin(), temp2.end());
+    std::copy(temp2.begin(), temp2.end(), out.begin());
+}
+} // namespace savitzky_golay
+
+GR_REGISTER_BLOCK(gr::filter::SavitzkyGolayFilter, [T], [ float, double ])
+// SavitzkyGolayFilter<T> (:17-81): y[n] = sum_k c[k] x[n - (W - 1) + k] over a history of zeros (SavitzkyGolay.hpp:226-233, BoundaryPolicy::Default with value 0).
+// Any update that names one of the five settings is setParameters (:67-76, SavitzkyGolay.hpp:253-260): new coefficients AND an empty history.
+template <typename T>
+    requires std::floating_point<T>
+struct SavitzkyGolayFilter : Block<SavitzkyGolayFilter<T>> {
+    PortIn<T>  in;
+    PortOut<T> out;
+
+    Annotated<gr::Size_t, "window size", Doc<"filter window size (samples, must be >= poly_order+1)">> window_size = 11U;
+    Annotated<gr::Size_t, "polynomial order", Doc<"order of fitting polynomial">>                      poly_order  = 4U;
+    Annotated<gr::Size_t, "derivative order", Doc<"derivative order (0=smooth, 1=1st deriv, ...)">>    deriv_order = 0U;
+    Annotated<float, "sample rate", Doc<"input sample rate for derivative scaling">, Unit<"Hz">>       sample_rate = 1.0f;
+    Annotated<std::string, "alignment", Doc<"Centred or Causal">>                                      alignment   = std::string("Centred");
+
+    GR_MAKE_REFLECTABLE(SavitzkyGolayFilter, in, out, window_size, poly_order, deriv_order, sample_rate, alignment);
+
+    std::vector<T> _coeffs, _history;           // the history oldest first, as HistoryBuffer::push_back leaves it
+    bool           _parameters_changed = false; // an update named a setting since the device stage was made: setParameters, i.e. a reset
+
+    [[nodiscard]] bool causal() const { return alignment.value == "Causal"; } // anything else is Centred (:53-55)
+    [[nodiscard]] T    delta() const {                                        // (:49-52)
+        const T sampleRateT = static_cast<T>(sample_rate.value);
+        return sampleRateT > T{0} ? T{1} / sampleRateT : T{1};
+    }
+    [[nodiscard]] std::vector<T> designCoefficients() const { return savitzky_golay::design<T>(window_size.value, poly_order.value, deriv_order.value, delta(), causal()); }
+    void start() { // (:60-65)
+        _coeffs = designCoefficients();
+        _history.assign(_coeffs.size(), T{0});
+    }
+    void settingsChanged(const property_map&, const property_map& newSettings) {
+        if (newSettings.contains("window_size") || newSettings.contains("poly_order") || newSettings.contains("deriv_order") || newSettings.contains("sample_rate") ||
+            newSettings.contains("alignment")) {
+            _parameters_changed = true;
+            _coeffs.clear(); // designed at the next sample (the host body) or stage (the device path): a program that only holds the block needs no library
+        }
+    }
+    void reset() { _history.assign(_history.size(), T{0}); } // (:78)
+    [[nodiscard]] T processOne(T input) {
+        if (_coeffs.empty()) start();
+        std::move(_history.begin() + 1, _history.end(), _history.begin());
+        _history.back() = input;
+        T acc{0};
+        for (std::size_t k = 0; k < _coeffs.size(); ++k) acc += _history[k] * _coeffs[k];
+        return acc;
+    }
+};
+
+GR_REGISTER_BLOCK(gr::filter::SavitzkyGolayDataSetFilter, [T], [ float, double ])
+// SavitzkyGolayDataSetFilter<T> (:87-164): zero-phase filtering of the whole flat signal_values as ONE sequence (:154-161), everything else of the DataSet passed
+// through; an empty signal_values comes back unchanged (:150-152).  Always Centred with delta 1 (:121-130).
+template <typename T>
+    requires std::floating_point<T>
+struct SavitzkyGolayDataSetFilter : Block<SavitzkyGolayDataSetFilter<T>> {
+    PortIn<DataSet<T>>  in;
+    PortOut<DataSet<T>> out;
+
+    Annotated<gr::Size_t, "window size", Doc<"filter window size (samples, must be >= poly_order+1)">> window_size     = 11U;
+    Annotated<gr::Size_t, "polynomial order", Doc<"order of fitting polynomial">>                      poly_order      = 4U;
+    Annotated<gr::Size_t, "derivative order", Doc<"derivative order (0=smooth, 1=1st deriv, ...)>">>   deriv_order     = 0U;
+    Annotated<std::string, "boundary policy", Doc<"Reflect or Replicate">>                             boundary_policy = std::string("Reflect");
+
+    GR_MAKE_REFLECTABLE(SavitzkyGolayDataSetFilter, in, out, window_size, poly_order, deriv_order, boundary_policy);
+
+    std::vector<T> _coeffs;
+    bool           _parameters_changed = false;
+
+    [[nodiscard]] bool replicate() const { return boundary_policy.value == "Replicate"; } // anything else is Reflect (:126-128)
+    void               start() { _coeffs = savitzky_golay::design<T>(window_size.value, poly_order.value, deriv_order.value, T{1}, false); } // (:132-140)
+    void               settingsChanged(const property_map&, const property_map& newSettings) {
+        if (newSettings.contains("window_size") || newSettings.contains("poly_order") || newSettings.contains("deriv_order") || newSettings.contains("boundary_policy")) {
+            _parameters_changed = true;
+            _coeffs.clear();
+        }
+    }
+    [[nodiscard]] gr4hip_savgol_zp_params params() const {
+        return {std::is_same_v<T, float> ? GR4HIP_F32 : GR4HIP_F64, static_cast<std::size_t>(window_size.value), static_cast<std::size_t>(poly_order.value),
+                static_cast<std::size_t>(deriv_order.value), replicate() ? GR4HIP_SAVGOL_REPLICATE : GR4HIP_SAVGOL_REFLECT};
+    }
+    [[nodiscard]] DataSet<T> processOne(DataSet<T> input) {
+        if (input.signal_values.empty()) return input;
+        if (_coeffs.empty()) start();
+        std::vector<T> filtered(input.signal_values.size());
+        savitzky_golay::applyZeroPhase<T>(std::span<const T>(input.signal_values), std::span<T>(filtered), std::span<const T>(_coeffs), replicate());
+        input.signal_values = std::move(filtered);
+        return input;
+    }
+};
 } // namespace gr::filter
 namespace gr::electrical {
 namespace detail {

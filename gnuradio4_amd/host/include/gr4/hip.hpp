@@ -1272,6 +1272,91 @@ struct Kernel<gr::filter::SvdDenoiser<T>> {
     }
 };
 
+// SavitzkyGolayFilter<T>: the streaming block is the library's coefficient design on its FIR handles, b[k] = c[W - 1 - k] (include/gr4hip.h "Savitzky-Golay"): the
+// IEEE float32 kernels for float (derivative coefficients reject nearly all input power, so the dynamic-range guard of the faster ones would mark every segment
+// anyway), the FP64 kernel for double.  A stage is made from the block's current settings with an empty history; an update that names one of the block's settings
+// is setParameters (SavitzkyGolay.hpp:253-260), which clears the history, so the stage is made anew (gr4hip_fir_set_taps alone would keep it).
+template <typename T>
+struct SavgolStage final : Stage {
+    gr4hip_fir_t*   h32 = nullptr;
+    gr4hip_fir64_t* h64 = nullptr;
+    explicit SavgolStage(const std::vector<T>& coeffs) {
+        in_bytes = out_bytes = sizeof(T);
+        const std::vector<T> b(coeffs.rbegin(), coeffs.rend());
+        if constexpr (std::is_same_v<T, float>) {
+            check(gr4hip_fir_create(&h32, GR4HIP_F32, b.data(), b.size(), 1), "gr4hip_fir_create");
+            check(gr4hip_fir_set_algo(h32, GR4HIP_FIR_EXACT_F32), "gr4hip_fir_set_algo");
+        } else {
+            check(gr4hip_fir64_create(&h64, b.data(), b.size(), 1), "gr4hip_fir64_create");
+        }
+    }
+    ~SavgolStage() override {
+        if (h32) gr4hip_fir_destroy(h32);
+        if (h64) gr4hip_fir64_destroy(h64);
+    }
+    std::string_view kind() const override { return std::is_same_v<T, float> ? "savgol_f32" : "savgol_f64"; }
+    int enqueue(const void* in, std::size_t n, void* out, std::size_t* n_out, gr4hip_stream_t s) override {
+        if constexpr (std::is_same_v<T, float>) return gr4hip_fir_process(h32, in, n, out, n_out, s);
+        else return gr4hip_fir64_process(h64, static_cast<const double*>(in), n, static_cast<double*>(out), n_out, s);
+    }
+};
+template <typename T>
+struct Kernel<gr::filter::SavitzkyGolayFilter<T>> {
+    using B = gr::filter::SavitzkyGolayFilter<T>;
+    static std::unique_ptr<Stage> make_stage(B& b) {
+        b._parameters_changed = false;
+        return std::make_unique<SavgolStage<T>>(b.designCoefficients());
+    }
+    static work::Status work(B& b, std::size_t nIn, std::size_t nOut) {
+        return offload_work(b, nIn, nOut, make_stage, [](Stage&, B& blk) { return !blk._parameters_changed; }); // (an update of another setting keeps the stage)
+    }
+};
+
+// SavitzkyGolayDataSetFilter<T>: each DataSet's flat signal_values goes to HBM as one row, gr4hip_savgol_zp_process filters it forward and backward in one launch,
+// and the values come back into a copy of the DataSet whose other members are untouched.  An empty signal_values is passed through (SavitzkyGolayFilter.hpp:150-152).
+template <typename T>
+struct Kernel<gr::filter::SavitzkyGolayDataSetFilter<T>> {
+    using B = gr::filter::SavitzkyGolayDataSetFilter<T>;
+    struct State final : Offload {
+        gr4hip_savgol_zp_t* h = nullptr;
+        ~State() override { if (h) gr4hip_savgol_zp_destroy(h); }
+    };
+    static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
+        try {
+            State*     st = offload_state<State>(blk);
+            const auto p  = blk.params();
+            if (!st->h) check(gr4hip_savgol_zp_create(&st->h, &p), "gr4hip_savgol_zp_create");
+            else if (blk._parameters_changed) check(gr4hip_savgol_zp_set_params(st->h, &p), "gr4hip_savgol_zp_set_params");
+            blk._parameters_changed = false;
+            if (nOut != nIn) throw std::runtime_error("SavitzkyGolayDataSetFilter: one DataSet out per DataSet in");
+            const auto is = blk.in.buffer->read_span(nIn);
+            auto       os = blk.out.connected() ? blk.out.buffer->write_span(nOut) : std::span<DataSet<T>>{};
+            for (std::size_t f = 0; f < nIn; ++f) {
+                DataSet<T>        ds    = is[f];
+                const std::size_t n     = ds.signal_values.size();
+                const std::size_t bytes = n * sizeof(T);
+                if (n) {
+                    char* hin = static_cast<char*>(st->h_in.ensure(bytes));
+                    std::memcpy(hin, ds.signal_values.data(), bytes);
+                    char* din  = static_cast<char*>(st->d_in.ensure(bytes));
+                    char* dout = static_cast<char*>(st->d_out.ensure(bytes));
+                    check(gr4hip_memcpy_h2d(din, hin, bytes, nullptr), "h2d");
+                    check(gr4hip_savgol_zp_process(st->h, din, dout, n, 1, n, nullptr), "gr4hip_savgol_zp_process");
+                    char* hout = static_cast<char*>(st->h_out.ensure(bytes));
+                    check(gr4hip_memcpy_d2h(hout, dout, bytes, nullptr), "d2h");
+                    check(gr4hip_stream_synchronize(nullptr), "sync");
+                    std::memcpy(ds.signal_values.data(), hout, bytes);
+                }
+                if (!os.empty()) os[f] = std::move(ds);
+            }
+            return work::Status::OK;
+        } catch (const std::exception& e) {
+            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
+            return work::Status::ERROR; // never a silent host fallback
+        }
+    }
+};
+
 // SignalGenerator<T> (a source: its customWork comes here with the span of its CPU-domain edge): the chunk is generated in HBM by gr4hip_siggen_process and copied
 // to the edge.  The handle is made at the first chunk -- start(): configure + reset (SignalGenerator.hpp:57-61) -- and told of every later settingsChanged / reset
 // in front of the chunk that follows it.  The values are those of the host body (FastSin / FastCos: the closed-form phasor, include/gr4hip.h).

@@ -113,6 +113,10 @@ const bool registered = [] {
     r.insert<SvdDenoiser<double>>(named<double>("gr::filter::SvdDenoiser"));
     r.insert<SvdDenoiser<std::complex<float>>>(named<std::complex<float>>("gr::filter::SvdDenoiser"));
     r.insert<SvdDenoiser<std::complex<double>>>(named<std::complex<double>>("gr::filter::SvdDenoiser"));
+    r.insert<SavitzkyGolayFilter<float>>(named<float>("gr::filter::SavitzkyGolayFilter")); // SavitzkyGolayFilter.hpp:17, 87
+    r.insert<SavitzkyGolayFilter<double>>(named<double>("gr::filter::SavitzkyGolayFilter"));
+    r.insert<SavitzkyGolayDataSetFilter<float>>(named<float>("gr::filter::SavitzkyGolayDataSetFilter"));
+    r.insert<SavitzkyGolayDataSetFilter<double>>(named<double>("gr::filter::SavitzkyGolayDataSetFilter"));
     register_signal_generator<float>(r); register_signal_generator<double>(r); register_signal_generator<std::complex<float>>(r); register_signal_generator<std::int16_t>(r);
     r.insert<gr::blocks::fft::FFT<double, gr::DataSet<double>>>(named<double>("gr::blocks::fft::FFT"));
     r.insert<gr::blocks::fft::FFT<float>>(named<float>("gr::blocks::fft::FFT"));

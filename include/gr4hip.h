@@ -714,8 +714,8 @@ size_t gr4hip_electrical_tile(void); /* items per workgroup of both kernels: tes
  *   a NaN sample compares false everywhere and holds the state.
  * d_in: n_in samples of params.dtype.  d_edges: room for `capacity` edges, written in order of `sample`; *d_n_edges (device memory) receives the number of edges
  * DETECTED: only the first `capacity` are written, and the state advances over the whole call either way.  n_in == 0 is OK (*d_n_edges = 0).
- * GR4HIP_UNSUPPORTED for POLYNOMIAL_INTERPOLATION (:224-289: it needs the Savitzky-Golay coefficient design, which this library does not have; no other method
- * is taken in its place).  GR4HIP_INVALID_ARGUMENT, checked on the host before any device work: a non-finite offset, a non-finite or negative threshold, an
+ * GR4HIP_UNSUPPORTED for POLYNOMIAL_INTERPOLATION (:224-289: it needs the Savitzky-Golay coefficient design, which the detector is not wired to -- gr4hip_savgol_design
+ * below came later, and the error text still says the library does not have it; no other method is taken in its place).  GR4HIP_INVALID_ARGUMENT, checked on the host before any device work: a non-finite offset, a non-finite or negative threshold, an
  * unknown method or dtype, for the integer types a fractional offset / threshold or ones whose sum or difference leaves the type's range, for float ones that
  * are not finite as float.  set_params resets the detector as settingsChanged does (Trigger.hpp:76-80; the dtype is fixed at create); reset is reset() (:90-101).
  * Both are host-side notes applied by the next process call on its stream.  process queues its three launches and returns without waiting for them, with one
@@ -900,6 +900,58 @@ int    gr4hip_convert_process(gr4hip_convert_t* h, const void* const* d_in, void
 int    gr4hip_convert_set_prologue(gr4hip_convert_t* h, const gr4hip_ewise_t* prog);     /* Merge<A, "out", Convert, "in"> (BlockMerging.hpp:126-240) */
 int    gr4hip_convert_set_epilogue(gr4hip_convert_t* h, const gr4hip_ewise_t* prog);     /* Merge<Convert, "out", B, "in"> */
 size_t gr4hip_convert_tile(const gr4hip_convert_params* p);                              /* items one workgroup of the aligned body converts (0: invalid params) */
+
+/* ------------------------------------------------------------------------------------------------ Savitzky-Golay (blocks/filter/.../SavitzkyGolayFilter.hpp:17-164)
+ * gr::filter::SavitzkyGolayFilter<T> and SavitzkyGolayDataSetFilter<T> over algorithm/filter/SavitzkyGolay.hpp, T in {float, double}.  Design notes, the evidence
+ * for the truncation rule and the measured bounds: SAVITZKY_GOLAY.md.
+ * gr4hip_savgol_design (host only, no device) restates computeCoefficients<T> (SavitzkyGolay.hpp:93-151):
+ *   W = max(window_size, 1), p = min(poly_order, W - 1), d = min(deriv_order, p), delta = max(T(delta), eps_T) (:95-98: delta <= 0 is clamped, not refused);
+ *   D = (W - 1) / 2 for Centred, W - 1 for Causal (:105); A[i][j] = (i - D)^j by the running product (:108-115), in float64;
+ *   the singular values of A come from a one-sided Jacobi in float64, and sigma_k is dropped when sigma_k < eps_T max(W, p + 1) sigma_0 (:128-133) with T's
+ *   epsilon: the reference's float design truncates at ordinary settings (W 51, p 4 keeps 4 of 5), and the truncated filter is the one it computes with;
+ *   row d of the truncated pseudo-inverse is rounded to T, then multiplied in T by T(d!) / std::pow(delta, T(d)) (:147-148; d! in size_t arithmetic, :43-49);
+ *   h_coeffs_out receives W values of T, coeffs[k] belonging to the offset k - D.
+ *   info_out (may be NULL): the clamped settings, the kept rank, sigma_0, the smallest kept sigma, the threshold, and `ambiguous`: some sigma_k lies within
+ *   16 eps_T sigma_0 of the threshold, where the reference's own T-precision SVD could decide either way.  16 is a chosen safety factor over the ~ eps sigma_0
+ *   error of a backward-stable SVD, not a measured one.  The flag is information: nothing is refused because of it.
+ *   GR4HIP_INVALID_ARGUMENT: a dtype other than F32 / F64, an unknown alignment, a NULL output.  GR4HIP_UNSUPPORTED: W (p + 1) > 2^22, or a power that is not finite.
+ * gr4hip_savgol_pinv_row: the same row of the same truncated pseudo-inverse in float64, before the rounding to T and the scale (what the tests bound).
+ * gr4hip_savgol_zp_*: applyZeroPhase (:177-193) as the DataSet block calls it (SavitzkyGolayFilter.hpp:121-137, 154-159: Centred, delta 1), on each of `batch` rows
+ *   of n samples, row r at d_in / d_out + r * row_stride samples:
+ *     t[j] = sum_k c[k] x[b(j + k - D)], rounded to T (the reference's std::vector<T> temp); out[n] = sum_k c[k] t[b(n - k + D)]
+ *   with b = reflectIndex / replicateIndex (:51-77) -- the literal apply, reverse, apply, reverse.  Both passes are one launch, sums in float64 for both types, and
+ *   t stays in LDS.  Rows need the alignment of T only; nothing outside the n samples of a row is read or written.  process queues the launch and returns without
+ *   waiting.  n == 0 (or batch == 0) is a no-op returning OK (:180).  The coefficients travel in the kernel's arguments, so set_params (settingsChanged, :142-147)
+ *   is a host-side note and the handle owns no device memory; the dtype is fixed at create.
+ *   GR4HIP_UNSUPPORTED from create / set_params: max(window_size, 1) > GR4HIP_SAVGOL_ZP_MAX_WINDOW (the caller keeps its CPU path).  GR4HIP_INVALID_ARGUMENT: an unknown
+ *   dtype or boundary policy, a buffer not aligned to its samples, row_stride < n with more than one row, d_in and d_out overlapping, more than 2^31 - 1 tiles.
+ * The streaming block has no entry point of its own: processOne (SavitzkyGolay.hpp:226-233) with the Default boundary policy the block always uses
+ *   (SavitzkyGolayFilter.hpp:48-57) is y[n] = sum_k c[k] x[n - (W - 1) + k] over a history of zeros, i.e. fir_filter with b[k] = c[W - 1 - k]: gr4hip_fir_* with
+ *   GR4HIP_FIR_EXACT_F32 for float, gr4hip_fir64_* for double.  A settings change calls set_taps AND reset, because setParameters clears the history (:253-260). */
+#define GR4HIP_SAVGOL_ZP_MAX_WINDOW 255
+typedef enum { GR4HIP_SAVGOL_CENTRED = 0, GR4HIP_SAVGOL_CAUSAL = 1 } gr4hip_savgol_alignment;   /* algorithm::savitzky_golay::Alignment (:19-22) */
+typedef enum { GR4HIP_SAVGOL_REFLECT = 0, GR4HIP_SAVGOL_REPLICATE = 1 } gr4hip_savgol_boundary; /* the two BoundaryPolicy values the DataSet block sets (:126-128) */
+typedef struct {
+    size_t window_size, poly_order, deriv_order; /* after the clamps */
+    size_t rank;                                 /* singular values kept */
+    double sigma_max, sigma_min_kept, threshold; /* sigma_0, the smallest kept one, eps_T max(W, p + 1) sigma_0 */
+    int    ambiguous;
+} gr4hip_savgol_info;
+typedef struct {
+    int    dtype;                                /* GR4HIP_F32 or GR4HIP_F64 (SavitzkyGolayFilter.hpp:87) */
+    size_t window_size, poly_order, deriv_order; /* (:111-113) */
+    int    boundary_policy;                      /* gr4hip_savgol_boundary (:114: "Replicate", anything else is Reflect) */
+} gr4hip_savgol_zp_params;
+typedef struct gr4hip_savgol_zp gr4hip_savgol_zp_t;
+int    gr4hip_savgol_design(int dtype, size_t window_size, size_t poly_order, size_t deriv_order, double delta, int alignment, void* h_coeffs_out,
+                            gr4hip_savgol_info* info_out);
+int    gr4hip_savgol_pinv_row(int dtype, size_t window_size, size_t poly_order, size_t deriv_order, int alignment, double* h_row_out, gr4hip_savgol_info* info_out);
+size_t gr4hip_savgol_zp_tile(void); /* outputs per workgroup: a row of at most this many samples is one workgroup's (tests place their edges by it) */
+int    gr4hip_savgol_zp_create(gr4hip_savgol_zp_t** h, const gr4hip_savgol_zp_params* p);     /* start() -> updateCoefficients (:132-140) */
+int    gr4hip_savgol_zp_set_params(gr4hip_savgol_zp_t* h, const gr4hip_savgol_zp_params* p); /* settingsChanged (:142-147) */
+int    gr4hip_savgol_zp_coeffs(const gr4hip_savgol_zp_t* h, void* h_coeffs_out, gr4hip_savgol_info* info_out); /* the W coefficients in T the handle filters with */
+int    gr4hip_savgol_zp_process(gr4hip_savgol_zp_t* h, const void* d_in, void* d_out, size_t n, size_t batch, size_t row_stride, gr4hip_stream_t stream); /* processOne (:149-163) */
+int    gr4hip_savgol_zp_destroy(gr4hip_savgol_zp_t* h);
 
 #ifdef __cplusplus
 }
