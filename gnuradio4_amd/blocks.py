@@ -171,6 +171,48 @@ class fir_interpolator(_Handle):
         return out
 
 
+class complex_fir_filter(_Handle):
+    """Complex taps x complex data FIR, direct and decimating (SURVEY.md Appendix A's "complex-tap variant"; the reference's fir_filter takes floating-point
+    T only, so the definition is the project's: COMPLEX_FIR.md).  settings `b` (complex), `decimate`; complex64 in, complex64 out, n_out = n_in / decimate."""
+    _destroy = "gr4hip_cfir_destroy"
+
+    def __init__(self, b: Sequence[complex], decimate: int = 1):
+        super().__init__()
+        self.dtype = torch.complex64
+        self.decimate = int(decimate)
+        self.b = np.ascontiguousarray(b, np.complex64)
+        check(lib().gr4hip_cfir_create(C.byref(self._h), self.b.ctypes.data, len(self.b), self.decimate), "complex_fir_filter")
+
+    def settings_changed(self, b: Sequence[complex]):
+        self.b = np.ascontiguousarray(b, np.complex64)
+        check(lib().gr4hip_cfir_set_taps(self._h, self.b.ctypes.data, len(self.b)), "complex_fir_filter.set_taps")
+
+    def reset(self):
+        check(lib().gr4hip_cfir_reset(self._h), "complex_fir_filter.reset")
+
+    def set_guard_mode(self, mode: int):
+        """capi.GUARD_STRICT (default) or capi.GUARD_OFF (no marking, no second evaluation) -- gr4hip_cfir_set_guard_mode"""
+        check(lib().gr4hip_cfir_set_guard_mode(self._h, int(mode)), "complex_fir_filter.set_guard_mode")
+
+    @staticmethod
+    def segment() -> int:
+        """complex outputs per guard segment"""
+        return int(lib().gr4hip_cfir_segment())
+
+    @staticmethod
+    def tile() -> int:
+        """complex outputs per tile group of the matrix-pipe kernel"""
+        return int(lib().gr4hip_cfir_tile())
+
+    def process_bulk(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        x = _dev(x, "complex_fir_filter")
+        if x.dtype != self.dtype:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "complex_fir_filter", f"expected {self.dtype}, got {x.dtype}")
+        out = _out(out, x.numel() // self.decimate, self.dtype, x, "complex_fir_filter.process")
+        check(lib().gr4hip_cfir_process(self._h, x.data_ptr(), x.numel(), out.data_ptr(), None, _stream()), "complex_fir_filter.process")
+        return out
+
+
 class iir_filter(_Handle):
     """gr::filter::iir_filter<float, form> (time_domain_filter.hpp:62-122) or a cascade of sections
     (gr::filter::Filter<float>, FilterTool.hpp:223-247).  b, a: [nsections][n] or 1-D for a single section."""

@@ -95,6 +95,15 @@ SIGNATURES = {
     "gr4hip_fir_interp_reset": (_i, [_vp]),
     "gr4hip_fir_interp_process": (_i, [_vp, _vp, _sz, _vp, _psz, _vp]),
     "gr4hip_fir_interp_destroy": (_i, [_vp]),
+    "gr4hip_cfir_create": (_i, [_pvp, _vp, _sz, _sz]),
+    "gr4hip_cfir_set_taps": (_i, [_vp, _vp, _sz]),
+    "gr4hip_cfir_reset": (_i, [_vp]),
+    "gr4hip_cfir_set_guard_mode": (_i, [_vp, _i]),
+    "gr4hip_cfir_process": (_i, [_vp, _vp, _sz, _vp, _psz, _vp]),
+    "gr4hip_cfir_destroy": (_i, [_vp]),
+    "gr4hip_cfir_tile": (_sz, []),
+    "gr4hip_cfir_segment": (_sz, []),
+    "gr4hip_cfir_band_table": (_i, [_vp, _sz, _sz, _vp, _sz, _psz, C.POINTER(C.c_long)]),
     "gr4hip_decimate": (_i, [_i, _vp, _sz, _sz, _vp, _psz, _vp]),
     "gr4hip_iir_create": (_i, [_pvp, _i, _sz, _vp, _sz, _vp, _sz]),
     "gr4hip_iir_reset": (_i, [_vp]),

@@ -1073,6 +1073,54 @@ struct fir_interpolator : Block<fir_interpolator<T>, Resampling<1, 1, false>> {
         return work::Status::OK;
     }
 };
+
+// ---- complex-tap FIR for complex streams, direct and decimating (SURVEY.md Appendix A's "complex-tap variant"; COMPLEX_FIR.md).  The reference's fir_filter is
+// `requires std::floating_point<T>`, so like fir_interpolator this is the project's block: y[n] = sum_k b[k] x[n - k] with complex b, output m = y[m decimate].
+// Settings: the taps as two float vectors of equal length (pmt has no complex vector), and `decimate`; input_chunk_size = decimate, so gr:sample_rate is
+// forwarded divided by it (Block.hpp:1088-1099).  Host body: the sum in fir_filter's order, every complex product as four real products.
+template <typename T>
+    requires std::is_same_v<T, std::complex<float>>
+struct complex_fir_filter : Block<complex_fir_filter<T>, Resampling<1, 1, false>> {
+    PortIn<T>          in;
+    PortOut<T>         out;
+    std::vector<float> b_real{1.f};
+    std::vector<float> b_imag{0.f};
+    Size_t             decimate = 1;
+    GR_MAKE_REFLECTABLE(complex_fir_filter, in, out, b_real, b_imag, decimate);
+    std::vector<T> _hist; // newest first, K samples
+
+    void settingsChanged(const property_map&, const property_map&) {
+        if (b_real.size() != b_imag.size()) throw std::invalid_argument("complex_fir_filter: b_real and b_imag must have the same length");
+        if (b_real.empty()) throw std::invalid_argument("complex_fir_filter: need at least one tap");
+        if (decimate == 0) throw std::invalid_argument("complex_fir_filter: decimate must be >= 1");
+        this->input_chunk_size = decimate;
+        if (b_real.size() > _hist.size()) _hist.assign(b_real.size(), T{}); // like fir_filter: the history is replaced only when it must grow
+    }
+    void reset() { std::fill(_hist.begin(), _hist.end(), T{}); }
+    [[nodiscard]] std::vector<float> interleavedTaps() const {
+        std::vector<float> t(2 * b_real.size());
+        for (std::size_t k = 0; k < b_real.size(); ++k) { t[2 * k] = b_real[k]; t[2 * k + 1] = k < b_imag.size() ? b_imag[k] : 0.f; }
+        return t;
+    }
+    [[nodiscard]] work::Status processBulk(std::span<const T> input, std::span<T> output) noexcept {
+        const std::size_t K = std::min(b_real.size(), b_imag.size()), D = std::max<std::size_t>(1, decimate);
+        if (_hist.size() < K) _hist.assign(K, T{});
+        std::size_t o = 0;
+        for (std::size_t i = 0; i < input.size(); ++i) {
+            std::move_backward(_hist.begin(), _hist.end() - 1, _hist.end());
+            _hist[0] = input[i];
+            if (i % D != 0) continue;
+            float re = 0.f, im = 0.f;
+            for (std::size_t k = 0; k < K; ++k) {
+                const float xr = _hist[k].real(), xi = _hist[k].imag();
+                re += b_real[k] * xr - b_imag[k] * xi;
+                im += b_real[k] * xi + b_imag[k] * xr;
+            }
+            output[o++] = T(re, im);
+        }
+        return work::Status::OK;
+    }
+};
 } // namespace gr::filter
 
 namespace gr::blocks::math {

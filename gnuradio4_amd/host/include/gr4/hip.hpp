@@ -588,6 +588,24 @@ struct InterpStage final : Stage {
     int enqueue(const void* in, std::size_t n, void* out, std::size_t* n_out, gr4hip_stream_t s) override { return gr4hip_fir_interp_process(h, in, n, out, n_out, s); }
 };
 
+// complex-tap FIR (complex data, direct and decimating): gr4hip_cfir_*, n_out = n / decim
+struct CfirStage final : Stage {
+    gr4hip_cfir_t*     h = nullptr;
+    std::size_t        decim;
+    std::vector<float> taps; // interleaved {re, im}
+    CfirStage(const std::vector<float>& interleaved, std::size_t decimate) : decim(std::max<std::size_t>(1, decimate)), taps(interleaved) {
+        in_bytes = out_bytes = 8; in_chunk = decim; out_chunk = 1;
+        check(gr4hip_cfir_create(&h, taps.data(), taps.size() / 2, decim), "gr4hip_cfir_create");
+    }
+    ~CfirStage() override { gr4hip_cfir_destroy(h); }
+    void set_taps(const std::vector<float>& interleaved) {
+        taps = interleaved;
+        check(gr4hip_cfir_set_taps(h, taps.data(), taps.size() / 2), "gr4hip_cfir_set_taps"); // (the history is kept)
+    }
+    std::string_view kind() const override { return "cfir_c32"; }
+    int enqueue(const void* in, std::size_t n, void* out, std::size_t* n_out, gr4hip_stream_t s) override { return gr4hip_cfir_process(h, in, n, out, n_out, s); }
+};
+
 struct RotatorStage final : Stage {
     gr4hip_rotator_t* h = nullptr;
     EwiseProgram      prog; // the closed-form rotator as a per-sample op (empty with the reference's recurrence: that one is sequential and stays a stage of its own)
@@ -865,6 +883,19 @@ struct Kernel<gr::filter::fir_interpolator<T>> {
     using B = gr::filter::fir_interpolator<T>;
     static std::unique_ptr<Stage> make_stage(B& b) { return std::make_unique<InterpStage<T>>(b.b, b.interpolate); }
     static work::Status           work(B& b, std::size_t nIn, std::size_t nOut) { return offload_work(b, nIn, nOut, make_stage); }
+};
+template <>
+struct Kernel<gr::filter::complex_fir_filter<std::complex<float>>> {
+    using B = gr::filter::complex_fir_filter<std::complex<float>>;
+    static std::unique_ptr<Stage> make_stage(B& b) { return std::make_unique<CfirStage>(b.interleavedTaps(), b.decimate); }
+    static work::Status           work(B& b, std::size_t nIn, std::size_t nOut) {
+        return offload_work(b, nIn, nOut, make_stage, [](Stage& st, B& blk) {
+            auto& c = static_cast<CfirStage&>(st);
+            if (c.decim != std::max<std::size_t>(1, blk.decimate)) return false; // another rate: a new stage
+            c.set_taps(blk.interleavedTaps());
+            return true;
+        });
+    }
 };
 template <typename T, typename... Args>
 requires(std::is_same_v<T, float> || std::is_same_v<T, std::complex<float>>)

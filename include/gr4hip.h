@@ -169,7 +169,7 @@ int gr4hip_ring_size(const gr4hip_ring_t* ring, size_t* bytes);
 /* ------------------------------------------------------------------------------------------------ a1/a2/a5/a6
  * gr::filter::fir_filter<T>::processOne (blocks/filter/.../time_domain_filter.hpp:44-47):
  *   y[n] = sum_k b[k] x[n-k], zero initial history, history carried across calls (HistoryBuffer.hpp:130-139).
- * dtype F32 (registered) or C32 (complex data x real taps).  decim > 1 gives the
+ * dtype F32 (registered) or C32 (complex data x real taps; SURVEY.md Appendix A -- complex taps: gr4hip_cfir_* below).  decim > 1 gives the
  * BasicFilterProto decimating processBulk (:190-204): output m == y[m*decim]; n_in must be a multiple of decim
  * (the reference guarantees it through input_chunk_size = decimate, :166-168). */
 /* Decimate by 8 with 97 .. 1025 taps (float, long 16-byte-aligned spans: BASELINE configs[2]'s filter), by 16 with 33 .. 897 and by 32 with 33 .. 641 taps (complex data: by 8 with 64 .. 513, by 16 with 33 .. 449, by 32 with 33 .. 321 taps) run since late round 4 on the f16 matrix pipe with the arithmetic and
@@ -238,6 +238,29 @@ int gr4hip_fir_interp_set_taps(gr4hip_fir_interp_t* fir, const float* h_taps, si
 int gr4hip_fir_interp_reset(gr4hip_fir_interp_t* fir);
 int gr4hip_fir_interp_process(gr4hip_fir_interp_t* fir, const void* d_in, size_t n_in, void* d_out, size_t* n_out, gr4hip_stream_t stream);
 int gr4hip_fir_interp_destroy(gr4hip_fir_interp_t* fir);
+
+/* Complex-tap FIR for complex streams, direct and decimating (SURVEY.md Appendix A lists the "complex-tap variant as an option"; COMPLEX_FIR.md).  The reference has
+ * no such block -- its fir_filter is `requires std::floating_point<T>` -- so it does not pin parity here: the definition below is the project's, and the project's own
+ * float64 oracle (tests/complex_fir_oracle.py) pins it:
+ *   y[n] = sum_{k < ntaps} b[k] x[n - k],   b and x complex<float> (h_taps: ntaps interleaved {re, im}), every complex product as four real products;
+ *   decim D: output m = y[m D], n_in a multiple of D, n_out = n_in / D.  Zero initial history, the last ntaps - 1 inputs carried across calls.
+ * 1 <= ntaps <= 2048, 1 <= decim <= 64 (beyond: GR4HIP_UNSUPPORTED).  NULL taps, ntaps == 0, decim == 0, a non-finite tap, n_in % decim != 0, overlapping or not
+ * 8-byte-aligned buffers: GR4HIP_INVALID_ARGUMENT before any device work.  17 .. 1024 taps at decim <= 16 run on the f32 matrix pipe in tile groups of
+ * gr4hip_cfir_tile() outputs (exact float32 products; the tap operand of that form is what gr4hip_cfir_band_table returns: [n_steps][16][16] floats, step r_min first;
+ * h_out == NULL: sizes only; host code, no device), everything else and the ragged tail as IEEE float32 multiply-adds.  The guard is the FIR family's one rule
+ * (above): per segment of gr4hip_cfir_segment() outputs, D P_y < (sum |b|^2 / 128) P_x or a non-finite sample in the segment's window marks it, and marked segments are
+ * evaluated again as float64 sums in ascending k, rounded once, behind the launch on the same stream.  Guard modes: GR4HIP_GUARD_STRICT (default) or GR4HIP_GUARD_OFF
+ * (no marking, no second evaluation); GR4HIP_GUARD_DEFERRED: GR4HIP_UNSUPPORTED. */
+typedef struct gr4hip_cfir gr4hip_cfir_t;
+int    gr4hip_cfir_create(gr4hip_cfir_t** fir, const float* h_taps, size_t ntaps, size_t decim);
+int    gr4hip_cfir_set_taps(gr4hip_cfir_t* fir, const float* h_taps, size_t ntaps); /* history kept unless it must grow (like fir_filter) */
+int    gr4hip_cfir_reset(gr4hip_cfir_t* fir);
+int    gr4hip_cfir_set_guard_mode(gr4hip_cfir_t* fir, int mode);
+int    gr4hip_cfir_process(gr4hip_cfir_t* fir, const void* d_in, size_t n_in, void* d_out, size_t* n_out /* may be NULL */, gr4hip_stream_t stream);
+int    gr4hip_cfir_destroy(gr4hip_cfir_t* fir);
+size_t gr4hip_cfir_tile(void);    /* complex outputs per MFMA tile group of one workgroup */
+size_t gr4hip_cfir_segment(void); /* complex outputs per guard segment */
+int    gr4hip_cfir_band_table(const float* h_taps, size_t ntaps, size_t decim, float* h_out, size_t cap, size_t* n_steps, long* r_min);
 
 /* gr::filter::Decimator<T>::processBulk (time_domain_filter.hpp:234-244): keep samples with i % decim == 0. */
 int gr4hip_decimate(int dtype, const void* d_in, size_t n_in, size_t decim, void* d_out, size_t* n_out, gr4hip_stream_t stream);
