@@ -419,6 +419,61 @@ class FFT(_Handle):
         return out
 
 
+def design_pfb(n_channels: int, taps_per_channel: int, window="Hamming", beta: float = 1.6) -> np.ndarray:
+    """the bank's windowed-sinc prototype h[j] = w[j] sinc((j - (P N - 1) / 2) / N), float32 [P N] (gr4hip_pfb_design: host code, no device)"""
+    h = np.empty(int(n_channels) * int(taps_per_channel), np.float32)
+    check(lib().gr4hip_pfb_design(h.ctypes.data, int(n_channels), int(taps_per_channel), _window_id(window), float(beta)), "design_pfb")
+    return h
+
+
+class PolyphaseFilterBank(_Handle):
+    """Critically sampled polyphase analysis bank in front of the FFT block's transform (PFB spectrometer / channelizer; the project's own definition, PFB.md):
+    frame m = FFT_N(sum_k h[k N + i] x[(m - P + 1 + k) N + i]).  complex64 in, N samples per frame in and out, the last (P - 1) N samples carried across calls.
+    `taps` = P N float values (None: design_pfb with `window`)."""
+    _destroy = "gr4hip_pfb_destroy"
+
+    def __init__(self, n_channels: int, taps_per_channel: int, taps=None, window="Hamming"):
+        super().__init__()
+        self.n_channels, self.taps_per_channel, self.dtype = int(n_channels), int(taps_per_channel), torch.complex64
+        self.taps = None
+        if taps is not None:
+            self.taps = np.ascontiguousarray(taps, np.float32)
+            if self.taps.size != self.n_channels * self.taps_per_channel:
+                raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "PolyphaseFilterBank", f"{self.taps.size} taps, the bank has {self.taps_per_channel} x {self.n_channels}")
+        elif _window_id(window) != _window_id("Hamming"):  # (Hamming is the library's own default design)
+            self.taps = design_pfb(self.n_channels, self.taps_per_channel, window)
+        check(lib().gr4hip_pfb_create(C.byref(self._h), capi.C32, self.n_channels, self.taps_per_channel, self.taps.ctypes.data if self.taps is not None else None, 0),
+              "PolyphaseFilterBank")
+
+    def set_taps(self, taps):
+        """new prototype from the next call on; the history is kept"""
+        self.taps = np.ascontiguousarray(taps, np.float32)
+        check(lib().gr4hip_pfb_set_taps(self._h, self.taps.ctypes.data, self.taps.size), "PolyphaseFilterBank.set_taps")
+
+    def reset(self):
+        check(lib().gr4hip_pfb_reset(self._h), "PolyphaseFilterBank.reset")
+
+    def _run(self, x, out, dtype, power: bool):
+        x = _dev(x, "PolyphaseFilterBank")
+        if x.dtype != self.dtype:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "PolyphaseFilterBank", f"expected {self.dtype}, got {x.dtype}")
+        if x.numel() % self.n_channels:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "PolyphaseFilterBank", f"{x.numel()} samples are not whole frames of {self.n_channels}")
+        frames = x.numel() // self.n_channels
+        out = _out(out, frames * self.n_channels, dtype, x, "PolyphaseFilterBank", (frames, self.n_channels))
+        check(lib().gr4hip_pfb_process(self._h, x.data_ptr(), frames, None if power else out.data_ptr(), out.data_ptr() if power else None, _stream()),
+              "PolyphaseFilterBank.process")
+        return out
+
+    def process_bulk(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """the channelizer: complex64 [frames, N], bin c of frame m"""
+        return self._run(x, out, torch.complex64, False)
+
+    def power(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """the spectrometer: |X|^2, float32 [frames, N]"""
+        return self._run(x, out, torch.float32, True)
+
+
 class Chain(_Handle):
     """complex<float> fir_filter -> FFT frames -> |X|^2, one fused device pipeline (BASELINE.json configs[1])."""
     _destroy = "gr4hip_chain_destroy"

@@ -104,6 +104,12 @@ SIGNATURES = {
     "gr4hip_cfir_tile": (_sz, []),
     "gr4hip_cfir_segment": (_sz, []),
     "gr4hip_cfir_band_table": (_i, [_vp, _sz, _sz, _vp, _sz, _psz, C.POINTER(C.c_long)]),
+    "gr4hip_pfb_design": (_i, [_vp, _sz, _sz, _i, _f]),
+    "gr4hip_pfb_create": (_i, [_pvp, _i, _sz, _sz, _vp, _i]),
+    "gr4hip_pfb_set_taps": (_i, [_vp, _vp, _sz]),
+    "gr4hip_pfb_reset": (_i, [_vp]),
+    "gr4hip_pfb_process": (_i, [_vp, _vp, _sz, _vp, _vp, _vp]),
+    "gr4hip_pfb_destroy": (_i, [_vp]),
     "gr4hip_decimate": (_i, [_i, _vp, _sz, _sz, _vp, _psz, _vp]),
     "gr4hip_iir_create": (_i, [_pvp, _i, _sz, _vp, _sz, _vp, _sz]),
     "gr4hip_iir_reset": (_i, [_vp]),

@@ -20,63 +20,6 @@
 
 namespace gr4 {
 
-template <int R>
-__device__ __forceinline__ void load_bfly(float2* v, const float2* __restrict__ src, int i, int NB, int p, int step_unit, const float2* __restrict__ tw) {
-    const int k = i & (p - 1);
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        float2 x = src[i + r * NB];
-        if (r > 0 && p > 1) x = cmulf(x, tw[r * k * step_unit]);
-        v[r] = x;
-    }
-}
-
-template <int R>
-__device__ __forceinline__ void store_bfly(const float2* v, float2* dst, int i, int p) {
-    const int k    = i & (p - 1);
-    const int base = (i - k) * R + k;
-#pragma unroll
-    for (int r = 0; r < R; ++r) dst[base + r * p] = v[r];
-}
-
-// the Stockham passes of one frame that sits in LDS (natural order in, natural order out); every lane of the workgroup calls it (it synchronises)
-__device__ __forceinline__ void lds_passes(float2* buf, int t, int tf, const FftPlanDev& plan, const float2* __restrict__ tw) {
-    const int N = plan.N;
-    int p = 1;
-    for (int pass = 0; pass < plan.npass; ++pass) {
-        const int R  = plan.radix[pass];
-        const int NB = N / R;
-        const int nb = NB / tf > 0 ? NB / tf : 1;
-        const int su = N / (p * R); // twiddle index unit: W_{pR}^{rk} = tw[r*k*su]
-        float2    v[8];
-        if (R == 8) {
-            if (t < NB) load_bfly<8>(v, buf, t, NB, p, su, tw);
-        } else if (R == 4) {
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-                if (b < nb && t + b * tf < NB) load_bfly<4>(v + 4 * b, buf, t + b * tf, NB, p, su, tw);
-        } else {
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-                if (b < nb && t + b * tf < NB) load_bfly<2>(v + 2 * b, buf, t + b * tf, NB, p, su, tw);
-        }
-        __syncthreads();
-        if (R == 8) {
-            if (t < NB) { fft8(v); store_bfly<8>(v, buf, t, p); }
-        } else if (R == 4) {
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-                if (b < nb && t + b * tf < NB) { fft4(v[4 * b], v[4 * b + 1], v[4 * b + 2], v[4 * b + 3]); store_bfly<4>(v + 4 * b, buf, t + b * tf, p); }
-        } else {
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-                if (b < nb && t + b * tf < NB) { fft2(v[2 * b], v[2 * b + 1]); store_bfly<2>(v + 2 * b, buf, t + b * tf, p); }
-        }
-        __syncthreads();
-        p *= R;
-    }
-}
-
 // One workgroup = fpb frames; tf = max(1, N/8) lanes per frame, 8 points per lane.
 __global__ void fft_block_kernel(const float* __restrict__ in, const float* __restrict__ window, const float2* __restrict__ tw, FftPlanDev plan, FftOutputs out,
                                  long n_frames) {

@@ -7,7 +7,7 @@
 #ifndef GR4_BUF_LOAD_AUX
 #define GR4_BUF_LOAD_AUX 2
 #endif
-#include "fft_kernels.hpp"
+#include "pfb_kernels.hpp"
 
 namespace gr4 {
 int fft_fast_launch_256(const float* d_in, const float* d_window, const float2* d_tw, const FftOutputs& o, long n_frames, hipStream_t st) {
@@ -15,5 +15,16 @@ int fft_fast_launch_256(const float* d_in, const float* d_window, const float2* 
 }
 int fft_fast_launch_8192(const float* d_in, const float* d_window, const float2* d_tw, const FftOutputs& o, long n_frames, hipStream_t st) {
     return fft_fast_launch<13>(d_in, d_window, d_tw, o, n_frames, st);
+}
+// the polyphase filter bank's kernels of the same two sizes: the same passes, so the same split (PFB.md)
+int pfb_fast_launch_256(const PfbFront& front, const float2* d_tw, const FftOutputs& o, long n_frames, hipStream_t st) { return pfb_fast_launch<8>(front, d_tw, o, n_frames, st); }
+int pfb_fast_launch_8192(const PfbFront& front, const float2* d_tw, const FftOutputs& o, long n_frames, hipStream_t st) { return pfb_fast_launch<13>(front, d_tw, o, n_frames, st); }
+int pfb_run_launch_8192(int P, const float* x, const float* hist, const float* taps, long L, const float2* d_tw, const FftOutputs& o, long n_frames, hipStream_t st, bool* taken) {
+    switch (P) {
+    case 2: return pfb_run_launch<13, 2>(x, hist, taps, L, d_tw, o, n_frames, st, taken);
+    case 3: return pfb_run_launch<13, 3>(x, hist, taps, L, d_tw, o, n_frames, st, taken);
+    case 4: return pfb_run_launch<13, 4>(x, hist, taps, L, d_tw, o, n_frames, st, taken);
+    default: *taken = false; return GR4HIP_OK;
+    }
 }
 } // namespace gr4

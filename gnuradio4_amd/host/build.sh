@@ -43,6 +43,7 @@ if stale $OUT/test_host_converter tests/test_host_converter.cpp; then $CXX -O1 t
 if stale $OUT/test_host_electrical tests/test_host_electrical.cpp; then $CXX -O2 tests/test_host_electrical.cpp -o $OUT/test_host_electrical -ldl & pids+=($!); fi
 if stale $OUT/test_host_savitzky_golay tests/test_host_savitzky_golay.cpp; then $CXX -O2 tests/test_host_savitzky_golay.cpp -o $OUT/test_host_savitzky_golay $LINK -ldl & pids+=($!); fi
 if stale $OUT/test_host_complex_fir tests/test_host_complex_fir.cpp; then $CXX -O2 tests/test_host_complex_fir.cpp -o $OUT/test_host_complex_fir $LINK -ldl & pids+=($!); fi
+if stale $OUT/test_host_pfb tests/test_host_pfb.cpp; then $CXX -O2 tests/test_host_pfb.cpp -o $OUT/test_host_pfb $LINK -ldl & pids+=($!); fi
 for p in "${pids[@]}"; do wait $p; done
 if [ -n "$PLUGIN_OBJS" ]; then $CXX -fPIC -shared -fvisibility=hidden $PLUGIN_OBJS -o ../libgr4hip_blocks.so -L.. -lgr4hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,/opt/rocm/lib; fi
 echo "built $(realpath $OUT)"

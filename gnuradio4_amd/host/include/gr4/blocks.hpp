@@ -1238,6 +1238,124 @@ struct PowerSpectrum : Block<PowerSpectrum<T>, Resampling<1024, 1024, false>> {
     }
 };
 
+// ---- polyphase filter bank in front of the transform (critically sampled analysis bank; PFB.md -- the reference has no polyphase form, the definition is the
+// project's):  frame m = DFT_N( u_m ),  u_m[i] = sum_{k < P} h[k N + i] x[(m - P + 1 + k) N + i],  N = fftSize, P = taps_per_channel, zero initial history.
+// PfbPowerSpectrum emits |X|^2 (float), PfbChannelizer the spectrum itself (complex, frame-major: fftSize bins per frame), both in natural bin order.
+// Settings: fftSize, taps_per_channel, taps (P N values; empty = the windowed-sinc prototype of gr4hip_pfb_design with `window`), window.
+// Host body: the float32 sums of the definition (k ascending from 0, one fma per term and component) and PowerSpectrum's float64 radix-2 transform (plumbing).
+namespace detail {
+struct PfbCore {
+    std::vector<float>               h;    // the prototype in use, P N values
+    std::vector<std::complex<float>> hist; // the last (P - 1) N samples
+    std::size_t                      N = 0, P = 0;
+
+    // throws on every bad setting; a change of N or P clears the history, new taps alone keep it
+    void configure(std::size_t fftSize, std::size_t tapsPerChannel, const std::vector<float>& taps, const std::string& window) {
+        if (fftSize < 2 || (fftSize & (fftSize - 1))) throw std::invalid_argument("fftSize must be a power of two");
+        if (tapsPerChannel < 1 || tapsPerChannel > 32) throw std::invalid_argument("taps_per_channel must be in [1, 32]");
+        if (!taps.empty() && taps.size() != fftSize * tapsPerChannel) throw std::invalid_argument("taps: need taps_per_channel * fftSize values (or none: designed)");
+        std::vector<float> next(taps);
+        if (next.empty()) {
+            gr::algorithm::window::Type type{};
+            if (!gr_enum_parse(type, std::string_view(window))) throw std::invalid_argument("unknown window '" + window + "'");
+            next.resize(fftSize * tapsPerChannel);
+            if (gr4hip_pfb_design(next.data(), fftSize, tapsPerChannel, static_cast<int>(type), 1.6f) != GR4HIP_OK) throw std::invalid_argument(std::string("pfb design: ") + gr4hip_last_error());
+        }
+        h = std::move(next);
+        if (fftSize != N || tapsPerChannel != P) hist.assign((tapsPerChannel - 1) * fftSize, {});
+        N = fftSize;
+        P = tapsPerChannel;
+    }
+    void reset() { std::fill(hist.begin(), hist.end(), std::complex<float>{}); }
+
+    // whole frames of `input` -> emit(frame index, bin, X)
+    template <typename Emit>
+    void process(std::span<const std::complex<float>> input, Emit&& emit) {
+        const std::size_t                 M = input.size() / N, H = (P - 1) * N;
+        std::vector<std::complex<double>> v(N);
+        const auto sample = [&](std::ptrdiff_t n) { return n < 0 ? hist[H - static_cast<std::size_t>(-n)] : input[static_cast<std::size_t>(n)]; }; // n relative to the call
+        for (std::size_t m = 0; m < M; ++m) {
+            for (std::size_t i = 0, j = 0; i < N; ++i) {
+                float re = 0.f, im = 0.f;
+                for (std::size_t k = 0; k < P; ++k) {
+                    const auto s = sample(static_cast<std::ptrdiff_t>((m + k) * N + i) - static_cast<std::ptrdiff_t>(H));
+                    re = std::fma(h[k * N + i], s.real(), re);
+                    im = std::fma(h[k * N + i], s.imag(), im);
+                }
+                v[j] = std::complex<double>(re, im);
+                std::size_t b = N >> 1;
+                while (b >= 1 && (j & b)) { j ^= b; b >>= 1; }
+                j |= b;
+            }
+            for (std::size_t len = 2; len <= N; len <<= 1)
+                for (std::size_t k = 0; k < N; k += len)
+                    for (std::size_t n = 0; n < len / 2; ++n) {
+                        const auto w = std::polar(1.0, -2.0 * std::numbers::pi * static_cast<double>(n) / static_cast<double>(len));
+                        const auto t = v[k + n + len / 2] * w;
+                        v[k + n + len / 2] = v[k + n] - t;
+                        v[k + n] += t;
+                    }
+            for (std::size_t c = 0; c < N; ++c) emit(m, c, v[c]);
+        }
+        // the last (P - 1) N samples of history + input
+        if (H) {
+            std::vector<std::complex<float>> next(H);
+            const std::ptrdiff_t             n0 = static_cast<std::ptrdiff_t>(M * N) - static_cast<std::ptrdiff_t>(H);
+            for (std::size_t j = 0; j < H; ++j) next[j] = sample(n0 + static_cast<std::ptrdiff_t>(j));
+            hist = std::move(next);
+        }
+    }
+};
+} // namespace detail
+
+template <typename T>
+    requires std::is_same_v<T, std::complex<float>>
+struct PfbPowerSpectrum : Block<PfbPowerSpectrum<T>, Resampling<1024, 1024, false>> {
+    PortIn<T>          in;
+    PortOut<float>     out;
+    Size_t             fftSize          = 1024;
+    Size_t             taps_per_channel = 4;
+    std::vector<float> taps;
+    std::string        window = "Hamming";
+    GR_MAKE_REFLECTABLE(PfbPowerSpectrum, in, out, fftSize, taps_per_channel, taps, window);
+    detail::PfbCore _core;
+
+    void settingsChanged(const property_map&, const property_map&) {
+        _core.configure(fftSize, taps_per_channel, taps, window);
+        this->input_chunk_size = this->output_chunk_size = fftSize; // whole frames
+    }
+    void reset() { _core.reset(); }
+    work::Status processBulk(std::span<const T> input, std::span<float> output) {
+        if (_core.N != fftSize) settingsChanged({}, {});
+        _core.process(input, [&](std::size_t m, std::size_t c, const std::complex<double>& X) { output[m * _core.N + c] = static_cast<float>(std::norm(X)); });
+        return work::Status::OK;
+    }
+};
+
+template <typename T>
+    requires std::is_same_v<T, std::complex<float>>
+struct PfbChannelizer : Block<PfbChannelizer<T>, Resampling<1024, 1024, false>> {
+    PortIn<T>          in;
+    PortOut<T>         out;
+    Size_t             fftSize          = 1024;
+    Size_t             taps_per_channel = 4;
+    std::vector<float> taps;
+    std::string        window = "Hamming";
+    GR_MAKE_REFLECTABLE(PfbChannelizer, in, out, fftSize, taps_per_channel, taps, window);
+    detail::PfbCore _core;
+
+    void settingsChanged(const property_map&, const property_map&) {
+        _core.configure(fftSize, taps_per_channel, taps, window);
+        this->input_chunk_size = this->output_chunk_size = fftSize;
+    }
+    void reset() { _core.reset(); }
+    work::Status processBulk(std::span<const T> input, std::span<T> output) {
+        if (_core.N != fftSize) settingsChanged({}, {});
+        _core.process(input, [&](std::size_t m, std::size_t c, const std::complex<double>& X) { output[m * _core.N + c] = static_cast<T>(X); });
+        return work::Status::OK;
+    }
+};
+
 // ---- gr::blocks::fft::FFT<T> (blocks/fourier/.../fft.hpp:31-251): one DataSet per frame of fftSize samples
 // window (default Hann) -> unnormalised forward DFT -> magnitude (hypot 2/N [dB], fft-shifted) + phase (atan2 [unwrap][deg], shifted) + Re + Im,
 // frequency axis, per-signal min/max.  T = std::complex<float> (N bins) or float (N/2 bins: fft.hpp:140-143, 221-227).

@@ -346,6 +346,29 @@ struct PowerSpectrumStage final : Stage {
     }
 };
 
+// polyphase filter bank (gr4hip_pfb_*): PfbPowerSpectrum (|X|^2, float out) and PfbChannelizer (the spectrum, complex out); whole frames of N samples
+struct PfbStage final : Stage {
+    gr4hip_pfb_t*      h = nullptr;
+    std::size_t        N, P;
+    bool               power;
+    std::vector<float> taps;
+    PfbStage(std::size_t fftSize, std::size_t tapsPerChannel, const std::vector<float>& prototype, bool mag2) : N(fftSize), P(tapsPerChannel), power(mag2), taps(prototype) {
+        in_bytes = 8; out_bytes = power ? 4 : 8; in_chunk = out_chunk = fftSize;
+        if (taps.size() != N * P) throw std::invalid_argument("pfb: need taps_per_channel * fftSize taps");
+        check(gr4hip_pfb_create(&h, GR4HIP_C32, N, P, taps.data(), 0), "gr4hip_pfb_create");
+    }
+    ~PfbStage() override { gr4hip_pfb_destroy(h); }
+    void set_taps(const std::vector<float>& prototype) {
+        taps = prototype;
+        check(gr4hip_pfb_set_taps(h, taps.data(), taps.size()), "gr4hip_pfb_set_taps"); // (the history is kept)
+    }
+    std::string_view kind() const override { return power ? "pfb_mag2_c32" : "pfb_c32"; }
+    int enqueue(const void* in, std::size_t n, void* out, std::size_t* n_out, gr4hip_stream_t s) override {
+        *n_out = (n / N) * N;
+        return gr4hip_pfb_process(h, in, n / N, power ? nullptr : static_cast<float*>(out), power ? static_cast<float*>(out) : nullptr, s);
+    }
+};
+
 // fir_filter<complex<float>> -> PowerSpectrum fused into one launch
 struct ChainStage final : Stage {
     gr4hip_chain_t* h = nullptr;
@@ -864,6 +887,25 @@ struct Kernel<gr::blocks::fft::PowerSpectrum<std::complex<float>>> {
     static std::unique_ptr<Stage> make_stage(B& b) { return std::make_unique<PowerSpectrumStage>(b.fftSize, window_id(b.window)); }
     static work::Status           work(B& b, std::size_t nIn, std::size_t nOut) { return offload_work(b, nIn, nOut, make_stage); }
 };
+
+// the two polyphase filter bank blocks: new taps keep the stage (and its history), another fftSize or taps_per_channel makes a new one (history cleared, like the host body)
+template <typename B, bool kPower>
+struct PfbKernel {
+    static std::unique_ptr<Stage> make_stage(B& b) {
+        if (b._core.N != b.fftSize) b.settingsChanged({}, {});
+        return std::make_unique<PfbStage>(b._core.N, b._core.P, b._core.h, kPower);
+    }
+    static work::Status work(B& b, std::size_t nIn, std::size_t nOut) {
+        return offload_work(b, nIn, nOut, make_stage, [](Stage& st, B& blk) {
+            auto& p = static_cast<PfbStage&>(st);
+            if (p.N != blk._core.N || p.P != blk._core.P) return false;
+            p.set_taps(blk._core.h);
+            return true;
+        });
+    }
+};
+template <> struct Kernel<gr::blocks::fft::PfbPowerSpectrum<std::complex<float>>> : PfbKernel<gr::blocks::fft::PfbPowerSpectrum<std::complex<float>>, true> {};
+template <> struct Kernel<gr::blocks::fft::PfbChannelizer<std::complex<float>>> : PfbKernel<gr::blocks::fft::PfbChannelizer<std::complex<float>>, false> {};
 
 template <gr::filter::IIRForm form>
 struct Kernel<gr::filter::iir_filter<float, form>> {

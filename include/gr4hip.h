@@ -361,6 +361,30 @@ int gr4hip_fft_plan(size_t fft_size, int* kind, int* radices16, int* n_passes);
 int gr4hip_window_create(int window, float* h_out, size_t n, float beta);
 int gr4hip_window_create_f64(int window, double* h_out, size_t n, double beta); /* create<double> */
 
+/* Polyphase filter bank in front of the FFT block's transform: PFB spectrometer and channelizer (critically sampled analysis bank, PFB.md).  The reference has no
+ * polyphase form, so it does not pin parity here: the definition below is the project's, and the project's own float64 oracle
+ * (tests/pfb_oracle.py) pins it.  N channels, P taps per channel, prototype h[0 .. P N) (real), input x complex<float>, zero initial history:
+ *   u_m[i] = sum_{k < P} h[k N + i] x[(m - P + 1 + k) N + i]   (float32, k ascending, one fma per term and component; x[n] = 0 for n < 0)
+ *   X_m[c] = sum_{i < N} u_m[i] e^{-2 pi i i c / N}            (the FFT block's unnormalised forward transform)
+ *   d_spectrum[m][c] = X_m[c] (interleaved complex, natural bin order), d_mag2[m][c] = |X_m[c]|^2; either may be NULL, not both.
+ * Frame m leaves when input frame m has arrived (latency (P - 1) N samples); the last (P - 1) N samples are carried across calls in the handle, so the values do
+ * not depend on how a stream is cut into calls.  With P = 1 and h = a window the outputs are those of gr4hip_fft_spectrum / gr4hip_fft_mag2.  Non-finite samples
+ * propagate as float arithmetic does (the P frames whose window holds one); there is no guard, the sums have no cancelling tier.
+ * gr4hip_pfb_design (host code, no device): h[j] = w_{PN}[j] sinc((j - (P N - 1) / 2) / N), w = gr4hip_window_create_f64(window, ., P N, beta), evaluated in
+ * float64 and rounded once; no other normalisation.  gr4hip_pfb_create: h_taps = P N values, NULL = that design with the Hamming window; flags must be 0.
+ * gr4hip_pfb_set_taps keeps the history; it and gr4hip_pfb_reset (history back to zeros) are stream-ordered (LIFECYCLE CALLS above).
+ * Supported: in_dtype C32; n_channels a size of gr4hip_fft_plan kind 0 (a power of two <= 8192); 1 <= taps_per_channel <= 32.  GR4HIP_UNSUPPORTED (the caller
+ * keeps its own path): F32 input, other sizes, more than 32 taps per channel.  GR4HIP_INVALID_ARGUMENT before any device work: a NULL handle or input, fewer than 2
+ * channels, 0 taps per channel, a non-finite tap, count != P N, both outputs NULL, d_in / d_spectrum not aligned to 8 bytes or d_mag2 not to 4, an output that
+ * overlaps the input, more than 2^40 samples in one call (below 256 channels: more than 2^31 - 1 workgroups of 64 / max(1, N / 8) frames).  n_frames == 0 is a no-op. */
+typedef struct gr4hip_pfb gr4hip_pfb_t;
+int gr4hip_pfb_design(float* h_out, size_t n_channels, size_t taps_per_channel, int window, float beta);
+int gr4hip_pfb_create(gr4hip_pfb_t** pfb, int in_dtype, size_t n_channels, size_t taps_per_channel, const float* h_taps /* P N values, or NULL */, int flags);
+int gr4hip_pfb_set_taps(gr4hip_pfb_t* pfb, const float* h_taps, size_t count);
+int gr4hip_pfb_reset(gr4hip_pfb_t* pfb);
+int gr4hip_pfb_process(gr4hip_pfb_t* pfb, const void* d_in, size_t n_frames, float* d_spectrum, float* d_mag2, gr4hip_stream_t stream);
+int gr4hip_pfb_destroy(gr4hip_pfb_t* pfb);
+
 /* ------------------------------------------------------------------------------------------------ headline chain
  * complex<float> fir_filter -> FFT block frames -> |X|^2 (BASELINE.json configs[1]).  One call consumes
  * floor(n_samples / fft_size) frames; FIR history (ntaps-1 samples) is carried across calls.
