@@ -171,6 +171,53 @@ class fir_interpolator(_Handle):
         return out
 
 
+class rational_resampler(_Handle):
+    """Rational resampler, rate `interpolate` / `decimate` (RATIONAL_RESAMPLER.md; the reference has only the rate machinery Resampling<in, out>): zero-stuff by
+    L, fir_filter's sum with gain L, keep every M-th sample -- evaluated as L polyphase branches that compute only the kept outputs.  settings `b` (real taps),
+    `interpolate`, `decimate`; T in {float32, complex64}; n_in a multiple of `decimate`, n_out = n_in / decimate * interpolate."""
+    _destroy = "gr4hip_resamp_destroy"
+
+    def __init__(self, b: Sequence[float], interpolate: int, decimate: int, dtype=torch.float32):
+        super().__init__()
+        self.b = np.ascontiguousarray(b, np.float32)
+        self.dtype = dtype
+        self.interpolate, self.decimate = int(interpolate), int(decimate)
+        if dtype not in (torch.float32, torch.complex64):
+            raise capi.Gr4HipError(capi.UNSUPPORTED, "rational_resampler", f"float32 or complex64 streams, got {dtype}")
+        check(lib().gr4hip_resamp_create(C.byref(self._h), _DTYPE_ID[dtype], self.b.ctypes.data, len(self.b), self.interpolate, self.decimate), "rational_resampler")
+
+    def settings_changed(self, b: Sequence[float]):
+        """new taps at the same rate; the history is kept unless it must grow"""
+        self.b = np.ascontiguousarray(b, np.float32)
+        check(lib().gr4hip_resamp_set_taps(self._h, self.b.ctypes.data, len(self.b)), "rational_resampler.set_taps")
+
+    def reset(self):
+        check(lib().gr4hip_resamp_reset(self._h), "rational_resampler.reset")
+
+    @staticmethod
+    def tile() -> int:
+        """output cycles (of `interpolate` samples) per workgroup"""
+        return int(lib().gr4hip_resamp_tile())
+
+    def process_bulk(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        x = _dev(x, "rational_resampler")
+        if x.dtype != self.dtype:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "rational_resampler", f"expected {self.dtype}, got {x.dtype}")
+        out = _out(out, x.numel() // self.decimate * self.interpolate, self.dtype, x, "rational_resampler.process")
+        check(lib().gr4hip_resamp_process(self._h, x.data_ptr(), x.numel(), out.data_ptr(), None, _stream()), "rational_resampler.process")
+        return out
+
+
+def design_resampler_taps(interpolate: int, decimate: int, half_len: int = 8, window: str = "Hamming", beta: float = 1.6) -> np.ndarray:
+    """the low-pass in front of a rate change by interpolate / decimate: 2 half_len max(L, M) + 1 windowed-sinc taps, cut-off 0.4 / max(L, M) of the L-times rate,
+    DC gain 1, float32 (gr4hip_resamp_design: host code, no device)"""
+    n = C.c_size_t(0)
+    check(lib().gr4hip_resamp_design(None, 0, C.byref(n), int(interpolate), int(decimate), int(half_len), _window_id(window), float(beta)), "design_resampler_taps")
+    h = np.empty(n.value, np.float32)
+    check(lib().gr4hip_resamp_design(h.ctypes.data, h.size, C.byref(n), int(interpolate), int(decimate), int(half_len), _window_id(window), float(beta)), "design_resampler_taps")
+    return h
+
+
 class complex_fir_filter(_Handle):
     """Complex taps x complex data FIR, direct and decimating (SURVEY.md Appendix A's "complex-tap variant"; the reference's fir_filter takes floating-point
     T only, so the definition is the project's: COMPLEX_FIR.md).  settings `b` (complex), `decimate`; complex64 in, complex64 out, n_out = n_in / decimate."""

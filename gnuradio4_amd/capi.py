@@ -95,6 +95,13 @@ SIGNATURES = {
     "gr4hip_fir_interp_reset": (_i, [_vp]),
     "gr4hip_fir_interp_process": (_i, [_vp, _vp, _sz, _vp, _psz, _vp]),
     "gr4hip_fir_interp_destroy": (_i, [_vp]),
+    "gr4hip_resamp_create": (_i, [_pvp, _i, _vp, _sz, _sz, _sz]),
+    "gr4hip_resamp_set_taps": (_i, [_vp, _vp, _sz]),
+    "gr4hip_resamp_reset": (_i, [_vp]),
+    "gr4hip_resamp_process": (_i, [_vp, _vp, _sz, _vp, _psz, _vp]),
+    "gr4hip_resamp_destroy": (_i, [_vp]),
+    "gr4hip_resamp_tile": (_sz, []),
+    "gr4hip_resamp_design": (_i, [_vp, _sz, _psz, _sz, _sz, _sz, _i, _d]),
     "gr4hip_cfir_create": (_i, [_pvp, _vp, _sz, _sz]),
     "gr4hip_cfir_set_taps": (_i, [_vp, _vp, _sz]),
     "gr4hip_cfir_reset": (_i, [_vp]),

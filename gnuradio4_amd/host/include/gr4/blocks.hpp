@@ -4,6 +4,7 @@
 // processBulk bodies are the host ("compute_domain = host") path used by BASELINE configs[0] (CPU scheduler plumbing); with
 // compute_domain = "gpu:hip[:i]" the work loop dispatches to gr::hip::Kernel<Block> (gr4/hip.hpp) instead.
 #pragma once
+#include <bit>
 #include <cmath>
 #include <numbers>
 
@@ -1070,6 +1071,67 @@ struct fir_interpolator : Block<fir_interpolator<T>, Resampling<1, 1, false>> {
                 output[m * L + p] = static_cast<T>(static_cast<float>(L)) * acc;
             }
         }
+        return work::Status::OK;
+    }
+};
+
+// ---- rational resampler, rate interpolate / decimate (RATIONAL_RESAMPLER.md).  The reference has the rate machinery (Resampling<inputChunk, outputChunk>,
+// annotated.hpp:121-128; gr:sample_rate rescaling Block.hpp:1088-1099) and no such block, so like fir_interpolator this is the project's: zero-stuff by L,
+// fir_filter's sum with gain L, keep every M-th sample.  Host body: the evaluated form of include/gr4hip.h -- output c L + p is
+// sum_{q < Kp} (float(L) b[q L + (p M) mod L]) x[c M + floor(p M / L) - q] in float32, q ascending, one fmaf per term, the zero-padded terms included.
+// input_chunk_size = decimate, output_chunk_size = interpolate: a work() call consumes whole cycles and gr:sample_rate is forwarded times L / M.
+// New taps keep the carried inputs (unless more are needed); another L or M clears them.
+template <typename T>
+struct rational_resampler : Block<rational_resampler<T>, Resampling<1, 1, false>> {
+    PortIn<T>          in;
+    PortOut<T>         out;
+    std::vector<float> b{1.f};
+    Size_t             interpolate = 1;
+    Size_t             decimate    = 1;
+    GR_MAKE_REFLECTABLE(rational_resampler, in, out, b, interpolate, decimate);
+    std::vector<T>     _hist; // the last samples in stream order, at least Kp - 1 of them
+    std::vector<T>     _work;
+    std::vector<float> _w;    // [Kp][L], q-major: float(L) b[q L + phi_p]
+    std::size_t        _L = 0, _M = 0;
+
+    void settingsChanged(const property_map&, const property_map&) {
+        if (b.empty()) throw std::invalid_argument("rational_resampler: need at least one tap");
+        if (interpolate == 0 || decimate == 0) throw std::invalid_argument("rational_resampler: interpolate and decimate must be >= 1");
+        this->input_chunk_size  = decimate;
+        this->output_chunk_size = interpolate;
+        const std::size_t L = interpolate, M = decimate, K = b.size(), kp = (K + L - 1) / L;
+        if (L != _L || M != _M) reset(); // another rate: the carried inputs belong to the old one
+        _L = L;
+        _M = M;
+        if (kp > _hist.size()) _hist.assign(std::max<std::size_t>(32, std::bit_ceil(kp)), T{}); // the device handle's rule: capacity max(32, bit_ceil(Kp)), replaced only when it must grow
+        _w.assign(kp * L, 0.f);
+        for (std::size_t p = 0; p < L; ++p) {
+            const std::size_t phi = p * M % L;
+            for (std::size_t q = 0; q * L + phi < K; ++q) _w[q * L + p] = static_cast<float>(L) * b[q * L + phi];
+        }
+    }
+    void reset() { std::fill(_hist.begin(), _hist.end(), T{}); }
+    [[nodiscard]] std::size_t branchLength() const { return (b.size() + interpolate - 1) / std::max<std::size_t>(1, interpolate); }
+    [[nodiscard]] work::Status processBulk(std::span<const T> input, std::span<T> output) noexcept {
+        if (_L == 0) settingsChanged({}, {});
+        const std::size_t L = _L, M = _M, kp = _w.size() / L, H = _hist.size(), cycles = input.size() / M;
+        _work.resize(H + input.size());
+        std::copy(_hist.begin(), _hist.end(), _work.begin());
+        std::copy(input.begin(), input.end(), _work.begin() + static_cast<std::ptrdiff_t>(H));
+        for (std::size_t c = 0; c < cycles; ++c)
+            for (std::size_t p = 0; p < L; ++p) {
+                const T* top = _work.data() + H + c * M + p * M / L; // x[c M + o_p]
+                if constexpr (std::is_same_v<T, std::complex<float>>) {
+                    float re = 0.f, im = 0.f;
+                    for (std::size_t q = 0; q < kp; ++q) { re = std::fmaf(_w[q * L + p], (top - q)->real(), re); im = std::fmaf(_w[q * L + p], (top - q)->imag(), im); }
+                    output[c * L + p] = T(re, im);
+                } else {
+                    T acc{};
+                    for (std::size_t q = 0; q < kp; ++q) acc = std::fma(static_cast<T>(_w[q * L + p]), *(top - q), acc);
+                    output[c * L + p] = acc;
+                }
+            }
+        std::copy(_work.end() - static_cast<std::ptrdiff_t>(H), _work.end(), _hist.begin());
         return work::Status::OK;
     }
 };

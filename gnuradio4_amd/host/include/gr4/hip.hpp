@@ -611,6 +611,25 @@ struct InterpStage final : Stage {
     int enqueue(const void* in, std::size_t n, void* out, std::size_t* n_out, gr4hip_stream_t s) override { return gr4hip_fir_interp_process(h, in, n, out, n_out, s); }
 };
 
+// rational resampler: polyphase kernel, n_out = n / M * L
+template <typename T>
+struct ResampStage final : Stage {
+    gr4hip_resamp_t*   h = nullptr;
+    std::size_t        L, M;
+    std::vector<float> taps;
+    ResampStage(const std::vector<float>& b, std::size_t interp, std::size_t decim) : L(std::max<std::size_t>(1, interp)), M(std::max<std::size_t>(1, decim)), taps(b) {
+        in_bytes = out_bytes = sizeof(T); in_chunk = M; out_chunk = L;
+        check(gr4hip_resamp_create(&h, dtype_of<T>(), taps.data(), taps.size(), L, M), "gr4hip_resamp_create");
+    }
+    ~ResampStage() override { gr4hip_resamp_destroy(h); }
+    void set_taps(const std::vector<float>& b) {
+        taps = b;
+        check(gr4hip_resamp_set_taps(h, taps.data(), taps.size()), "gr4hip_resamp_set_taps"); // (the history is kept)
+    }
+    std::string_view kind() const override { return "fir_resamp"; }
+    int enqueue(const void* in, std::size_t n, void* out, std::size_t* n_out, gr4hip_stream_t s) override { return gr4hip_resamp_process(h, in, n, out, n_out, s); }
+};
+
 // complex-tap FIR (complex data, direct and decimating): gr4hip_cfir_*, n_out = n / decim
 struct CfirStage final : Stage {
     gr4hip_cfir_t*     h = nullptr;
@@ -925,6 +944,20 @@ struct Kernel<gr::filter::fir_interpolator<T>> {
     using B = gr::filter::fir_interpolator<T>;
     static std::unique_ptr<Stage> make_stage(B& b) { return std::make_unique<InterpStage<T>>(b.b, b.interpolate); }
     static work::Status           work(B& b, std::size_t nIn, std::size_t nOut) { return offload_work(b, nIn, nOut, make_stage); }
+};
+template <typename T>
+    requires(std::is_same_v<T, float> || std::is_same_v<T, std::complex<float>>)
+struct Kernel<gr::filter::rational_resampler<T>> {
+    using B = gr::filter::rational_resampler<T>;
+    static std::unique_ptr<Stage> make_stage(B& b) { return std::make_unique<ResampStage<T>>(b.b, b.interpolate, b.decimate); }
+    static work::Status           work(B& b, std::size_t nIn, std::size_t nOut) {
+        return offload_work(b, nIn, nOut, make_stage, [](Stage& st, B& blk) {
+            auto& r = static_cast<ResampStage<T>&>(st);
+            if (r.L != blk.interpolate || r.M != blk.decimate) return false; // another rate: a new stage, zero history
+            r.set_taps(blk.b);
+            return true;
+        });
+    }
 };
 template <>
 struct Kernel<gr::filter::complex_fir_filter<std::complex<float>>> {

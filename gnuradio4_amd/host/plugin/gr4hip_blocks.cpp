@@ -88,6 +88,8 @@ const bool registered = [] {
     r.insert<fir_filter<double>>(named<double>("gr::filter::fir_filter")); // FP64 kernel behind the seam (csrc/f64.hip)
     r.insert<fir_filter<std::complex<float>>>(named<std::complex<float>>("gr::filter::fir_filter"));
     r.insert<complex_fir_filter<std::complex<float>>>(named<std::complex<float>>("gr::filter::complex_fir_filter")); // complex taps (no reference block)
+    r.insert<rational_resampler<float>>(named<float>("gr::filter::rational_resampler")); // rate L / M (RATIONAL_RESAMPLER.md; no reference block)
+    r.insert<rational_resampler<std::complex<float>>>(named<std::complex<float>>("gr::filter::rational_resampler"));
     r.insert<iir_filter<float, IIRForm::DF_I>>(named<float>("gr::filter::iir_filter", ", gr::filter::IIRForm::DF_I"));
     r.insert<iir_filter<float, IIRForm::DF_II>>(named<float>("gr::filter::iir_filter", ", gr::filter::IIRForm::DF_II"));
     r.insert<iir_filter<float, IIRForm::DF_I_TRANSPOSED>>(named<float>("gr::filter::iir_filter", ", gr::filter::IIRForm::DF_I_TRANSPOSED"));

@@ -239,6 +239,34 @@ int gr4hip_fir_interp_reset(gr4hip_fir_interp_t* fir);
 int gr4hip_fir_interp_process(gr4hip_fir_interp_t* fir, const void* d_in, size_t n_in, void* d_out, size_t* n_out, gr4hip_stream_t stream);
 int gr4hip_fir_interp_destroy(gr4hip_fir_interp_t* fir);
 
+/* Rational resampler: polyphase FIR at rate interp / decim = L / M (RATIONAL_RESAMPLER.md).  The reference has no such block, only the rate machinery one would
+ * declare (Resampling<inputChunk, outputChunk>), so the definition is the project's, pinned by its own float64 oracle (tests/rational_resampler_oracle.py).  Real taps
+ * b[0 .. K), data F32 or C32, zero initial history; L and M need not be coprime, the definition is literal:
+ *   u[n] = x[n / L] if n % L == 0 else 0,   v[n] = L sum_k b[k] u[n - k]   (the interpolator's definition above),   y[j] = v[j M]
+ * evaluated, with Kp = ceil(K / L) and j = c L + p (cycle c, slot p < L), o_p = floor(p M / L), phi_p = (p M) mod L, as
+ *   y[c L + p] = sum_{q = 0}^{Kp - 1} w_p[q] x[c M + o_p - q],   w_p[q] = float(L) b[q L + phi_p]   (one float32 rounding; 0 where q L + phi_p >= K)
+ * in float32 from 0 with q ascending, one fmaf per term and component, every slot summing all Kp terms (the zero-padded ones included).  There are no split products
+ * and no guard: this is the GR4HIP_FIR_EXACT_F32 class of arithmetic.
+ *  - n_in must be a multiple of M, n_out = n_in / M * L.  A call consumes whole cycles and always restarts at slot 0: no phase is carried, only the last Kp - 1 inputs
+ *    (capacity max(32, bit_ceil(Kp)), like the interpolator).
+ *  - Output values do not depend on how a stream is cut into calls, bit for bit: every output's sum has one fixed order.
+ *  - M == 1 computes the interpolator's definition, L == 1 the decimating fir_filter's y[m M].
+ *  - A non-finite input at position pos reaches exactly the outputs with c M + o_p - Kp < pos <= c M + o_p, as IEEE arithmetic gives them.
+ * Supported: F32 and C32, 1 <= interp, decim <= 1024, 1 <= ntaps <= 65536 (beyond: GR4HIP_UNSUPPORTED).  NULL handle, taps or buffers, ntaps, interp or decim == 0, a
+ * non-finite tap, n_in % decim != 0, overlapping buffers, buffers not aligned to the element size: GR4HIP_INVALID_ARGUMENT before any device work.  n_in == 0 is a
+ * no-op.  set_taps keeps the history unless it must grow; another L or M needs a new handle.  gr4hip_resamp_tile(): output cycles per workgroup.
+ * gr4hip_resamp_design (host code, no device; h_out == NULL: *ntaps only): the windowed-sinc low-pass in front of the rate change, float64 rounded once:
+ *   K = 2 half_len max(L, M) + 1,  fc = 0.4 / max(L, M) cycles per sample of the L-times rate,  h[k] = w_K[k] 2 fc sinc(2 fc (k - (K - 1) / 2)),  h /= sum h
+ * with w = gr4hip_window_create_f64(window, ., K, beta). */
+typedef struct gr4hip_resamp gr4hip_resamp_t;
+int    gr4hip_resamp_create(gr4hip_resamp_t** rs, int dtype, const float* h_taps, size_t ntaps, size_t interp, size_t decim);
+int    gr4hip_resamp_set_taps(gr4hip_resamp_t* rs, const float* h_taps, size_t ntaps);
+int    gr4hip_resamp_reset(gr4hip_resamp_t* rs);
+int    gr4hip_resamp_process(gr4hip_resamp_t* rs, const void* d_in, size_t n_in, void* d_out, size_t* n_out /* may be NULL */, gr4hip_stream_t stream);
+int    gr4hip_resamp_destroy(gr4hip_resamp_t* rs);
+size_t gr4hip_resamp_tile(void);
+int    gr4hip_resamp_design(float* h_out, size_t cap, size_t* ntaps, size_t interp, size_t decim, size_t half_len, int window, double beta);
+
 /* Complex-tap FIR for complex streams, direct and decimating (SURVEY.md Appendix A lists the "complex-tap variant as an option"; COMPLEX_FIR.md).  The reference has
  * no such block -- its fir_filter is `requires std::floating_point<T>` -- so it does not pin parity here: the definition below is the project's, and the project's own
  * float64 oracle (tests/complex_fir_oracle.py) pins it:
