@@ -465,6 +465,11 @@ class FFT(_Handle):
         check(lib().gr4hip_fft_mag2(self._h, x.data_ptr(), frames, out.data_ptr(), _stream()), "FFT.mag2")
         return out
 
+    def power_integrated(self, x: torch.Tensor, integrator: "SpectrumIntegrator", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """mag2() followed by integrator.process_bulk(), bit for bit, in the transform's launch where it has a sink (gr4hip_fft_mag2_integrate)"""
+        x, frames = self._frames(x)
+        return integrator._run(lib().gr4hip_fft_mag2_integrate, self._h, x, frames, out, "FFT.power_integrated")
+
 
 def design_pfb(n_channels: int, taps_per_channel: int, window="Hamming", beta: float = 1.6) -> np.ndarray:
     """the bank's windowed-sinc prototype h[j] = w[j] sinc((j - (P N - 1) / 2) / N), float32 [P N] (gr4hip_pfb_design: host code, no device)"""
@@ -519,6 +524,55 @@ class PolyphaseFilterBank(_Handle):
     def power(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """the spectrometer: |X|^2, float32 [frames, N]"""
         return self._run(x, out, torch.float32, True)
+
+    def power_integrated(self, x: torch.Tensor, integrator: "SpectrumIntegrator", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """power() followed by integrator.process_bulk(), bit for bit, in the transform's launch where it has a sink (gr4hip_pfb_power_integrate)"""
+        x = _dev(x, "PolyphaseFilterBank")
+        if x.dtype != self.dtype or x.numel() % self.n_channels:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "PolyphaseFilterBank", f"expected whole frames of {self.n_channels} {self.dtype} samples")
+        return integrator._run(lib().gr4hip_pfb_power_integrate, self._h, x, x.numel() // self.n_channels, out, "PolyphaseFilterBank.power_integrated")
+
+
+class SpectrumIntegrator(_Handle):
+    """Sum (mean=True: mean) of n_integrate consecutive power spectra of n_bins values, one spectrum out per n_integrate frames in (the project's own definition,
+    SPECTRUM_INTEGRATOR.md: float32 leaves of 32 frames, folded in float64, one fixed order).  The partial integration is carried across calls; a call returns the
+    spectra it completes, float32 [pending(frames), n_bins]."""
+    _destroy = "gr4hip_specint_destroy"
+
+    def __init__(self, n_bins: int, n_integrate: int, mean: bool = False):
+        super().__init__()
+        self.n_bins, self.n_integrate, self.mean = int(n_bins), int(n_integrate), bool(mean)
+        check(lib().gr4hip_specint_create(C.byref(self._h), self.n_bins, self.n_integrate, capi.SPECINT_MEAN if self.mean else 0), "SpectrumIntegrator")
+
+    def reset(self):
+        """drops the partial integration (from the next call on)"""
+        check(lib().gr4hip_specint_reset(self._h), "SpectrumIntegrator.reset")
+
+    def set_length(self, n_integrate: int):
+        """another integration length; the partial integration is dropped"""
+        check(lib().gr4hip_specint_set_length(self._h, int(n_integrate)), "SpectrumIntegrator.set_length")
+        self.n_integrate = int(n_integrate)
+
+    def pending(self, n_frames: int) -> int:
+        """spectra the next call of n_frames frames completes (host only)"""
+        n = C.c_size_t(0)
+        check(lib().gr4hip_specint_pending(self._h, int(n_frames), C.byref(n)), "SpectrumIntegrator.pending")
+        return int(n.value)
+
+    def _run(self, entry, first, x, frames, out, what):
+        n = self.pending(frames)
+        out = _out(out, n * self.n_bins, torch.float32, x, what, (n, self.n_bins))
+        got = C.c_size_t(0)
+        args = (first,) if first is not None else ()
+        check(entry(*args, self._h, x.data_ptr(), frames, out.data_ptr() if n else None, C.byref(got), _stream()), what)
+        assert got.value == n
+        return out.reshape(-1)[:n * self.n_bins].view(n, self.n_bins)
+
+    def process_bulk(self, frames: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        x = _dev(frames, "SpectrumIntegrator")
+        if x.dtype != torch.float32 or x.numel() % self.n_bins:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "SpectrumIntegrator", f"expected whole float32 frames of {self.n_bins} values")
+        return self._run(lib().gr4hip_specint_process, None, x, x.numel() // self.n_bins, out, "SpectrumIntegrator.process_bulk")
 
 
 class Chain(_Handle):

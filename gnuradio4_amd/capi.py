@@ -16,6 +16,7 @@ DF_I, DF_II, DF_I_TRANSPOSED, DF_II_TRANSPOSED = range(4)
 WINDOWS = ["None", "Rectangular", "Hamming", "Hann", "HannExp", "Blackman", "Nuttall", "BlackmanHarris",
            "BlackmanNuttall", "FlatTop", "Exponential", "Kaiser"]
 FFT_OUTPUT_IN_DB, FFT_OUTPUT_IN_DEG, FFT_UNWRAP_PHASE = 1, 2, 4
+SPECINT_MEAN = 1
 CHAIN_AUTO, CHAIN_UNFUSED, CHAIN_FUSED_TD, CHAIN_FUSED_FD, CHAIN_TIME_DOMAIN = range(5)
 GUARD_STRICT, GUARD_DEFERRED, GUARD_OFF = range(3)
 FIR_AUTO, FIR_TIME_DOMAIN, FIR_EXACT_F32, FIR_TIME_DOMAIN_F32, FIR_TIME_DOMAIN_BF16X3 = range(5)
@@ -117,6 +118,15 @@ SIGNATURES = {
     "gr4hip_pfb_reset": (_i, [_vp]),
     "gr4hip_pfb_process": (_i, [_vp, _vp, _sz, _vp, _vp, _vp]),
     "gr4hip_pfb_destroy": (_i, [_vp]),
+    "gr4hip_specint_create": (_i, [_pvp, _sz, _sz, _i]),
+    "gr4hip_specint_reset": (_i, [_vp]),
+    "gr4hip_specint_set_length": (_i, [_vp, _sz]),
+    "gr4hip_specint_pending": (_i, [_vp, _sz, _psz]),
+    "gr4hip_specint_process": (_i, [_vp, _vp, _sz, _vp, _psz, _vp]),
+    "gr4hip_specint_destroy": (_i, [_vp]),
+    "gr4hip_specint_leaf": (_sz, []),
+    "gr4hip_fft_mag2_integrate": (_i, [_vp, _vp, _vp, _sz, _vp, _psz, _vp]),
+    "gr4hip_pfb_power_integrate": (_i, [_vp, _vp, _vp, _sz, _vp, _psz, _vp]),
     "gr4hip_decimate": (_i, [_i, _vp, _sz, _sz, _vp, _psz, _vp]),
     "gr4hip_iir_create": (_i, [_pvp, _i, _sz, _vp, _sz, _vp, _sz]),
     "gr4hip_iir_reset": (_i, [_vp]),

@@ -17,6 +17,7 @@
 #endif
 #include "fft_kernels.hpp"
 #include "fft_smooth.hpp"
+#include "specint_kernels.hpp"
 
 namespace gr4 {
 
@@ -848,14 +849,16 @@ int gr4hip_fft_set_epilogue(gr4hip_fft_t* f, const gr4hip_ewise_t* prog) {
     return GR4HIP_OK;
 }
 
-int gr4hip_fft_mag2(gr4hip_fft_t* f, const void* d_in, size_t n_frames, float* d_mag2, gr4hip_stream_t stream) {
+// block_kernels_only: never the 8192-point frame pipeline, which equals fft_fast_kernel to float rounding only -- for the integrating entry, whose values must
+// not depend on how many frames a call has
+static int fft_mag2_run(gr4hip_fft_t* f, const void* d_in, size_t n_frames, float* d_mag2, bool block_kernels_only, gr4hip_stream_t stream) {
     GR4_REQUIRE(d_mag2 || n_frames == 0, "fft_mag2: null output");
     GR4_REQUIRE(f, "fft_mag2: null handle");
     EwiseHook post;
     if (f->post) { if (const int rc = ewise_device_ops(f->post, &post, as_stream(stream))) return rc; }
     // 8192-point complex frames, >= one frame per CU: the frame pipeline of the fused chain kernel without its filter (LDS-DMA prefetch of the next
     // frame during the transform of this one); everything else goes to the FFT block kernels
-    if (fft_on_frame_pipeline(f, n_frames)) {
+    if (!block_kernels_only && fft_on_frame_pipeline(f, n_frames)) {
         int rc = fft_pipe(f);
         if (rc) return rc;
         const bool windowed = f->window != GR4HIP_WIN_NONE && f->window != GR4HIP_WIN_RECTANGULAR;
@@ -868,6 +871,35 @@ int gr4hip_fft_mag2(gr4hip_fft_t* f, const void* d_in, size_t n_frames, float* d
     o.mag2      = d_mag2;
     o.mag2_post = post; // every kernel of this file stores |X|^2 through emit_bin or the fast kernel's register epilogue: the program rides in the transform's launch
     return fft_run(f, d_in, n_frames, o, nullptr, nullptr, stream);
+}
+
+int gr4hip_fft_mag2(gr4hip_fft_t* f, const void* d_in, size_t n_frames, float* d_mag2, gr4hip_stream_t stream) { return fft_mag2_run(f, d_in, n_frames, d_mag2, false, stream); }
+
+// |X|^2 summed over the integrator's frames (SPECTRUM_INTEGRATOR.md).  Complex frames of 256 .. 8192 points without an epilogue: fft_fast_kernel's frame loop with
+// the sink in place of the store; everything else: gr4hip_fft_mag2's kernels in pieces through the integrator's scratch, then its fold.
+int gr4hip_fft_mag2_integrate(gr4hip_fft_t* f, gr4hip_specint_t* si, const void* d_in, size_t n_frames, float* d_out, size_t* n_out, gr4hip_stream_t stream) {
+    GR4_REQUIRE(f, "fft_mag2_integrate: null handle");
+    const bool   real = f->in_dtype == GR4HIP_F32;
+    const size_t fb   = f->N * (real ? sizeof(float) : sizeof(float2));
+    if (const int rc = specint_check(si, "fft_mag2_integrate", f->N, d_in, fb, real ? 4 : 8, n_frames, d_out, n_out)) return rc;
+    size_t done = 0;
+    (void)gr4hip_specint_pending(si, n_frames, &done);
+    hipStream_t st = as_stream(stream);
+    if (n_frames > 0 && !real && f->kind == 0 && !f->post && specint_takes_sink(si, f->N, 0)) {
+        SpecintLaunch L;
+        if (const int rc = specint_begin(si, n_frames, st, &L)) return rc;
+        if (const int rc = specint_sink_fft(f->N, static_cast<const float*>(d_in), static_cast<const float*>(f->d_window.ptr), static_cast<const float2*>(f->d_tw.ptr), L, st)) return rc;
+        if (const int rc = specint_finish(si, L, d_out, 1, st)) return rc;
+    } else if (n_frames > 0) {
+        struct Ctx { gr4hip_fft_t* f; const char* in; size_t fb; } ctx{f, static_cast<const char*>(d_in), fb};
+        const auto produce = [](void* c, size_t first, size_t n, float* d_mag2, hipStream_t s) {
+            auto* x = static_cast<Ctx*>(c);
+            return fft_mag2_run(x->f, x->in + first * x->fb, n, d_mag2, true, s);
+        };
+        if (const int rc = specint_compose(si, n_frames, d_out, st, produce, &ctx)) return rc;
+    }
+    *n_out = done;
+    return GR4HIP_OK;
 }
 
 int gr4hip_fft_destroy(gr4hip_fft_t* f) { delete f; return GR4HIP_OK; }

@@ -1,5 +1,6 @@
 // fft_fast_frames.inc -- the body of fft_fast_kernel<LOG2N, REAL> (fft_kernels.hpp), included textually by every kernel that runs its frame loop, so that all of
-// them compile the same statements.  Expects in scope: LOG2N, REAL, FRONT / front (the first-pass load), in, window, tw, out (FftOutputs), n_frames.
+// them compile the same statements.  Expects in scope: LOG2N, REAL, FRONT / front (the first-pass load; FRONT::kSink: it takes |X|^2 instead of the store), in,
+// window, tw, out (FftOutputs), n_frames.
     constexpr int N = 1 << LOG2N, T = N / 16, FPB = 512 / T, NP = N + N / 32, HALF = N / 2;
     constexpr int TWS = REAL ? 2 : 1; // stride of W_N^j in the table
     static_assert(!REAL || LOG2N <= 12, "the real-input split is implemented for the 16 x 16 x R3 plans");
@@ -214,8 +215,12 @@
 #pragma unroll
             for (int j = 0; j < 16; ++j) m[j] = fmaf(X[j].x, X[j].x, X[j].y * X[j].y);
             if (out.mag2_post.n_ops > 0) ewise_apply<float, 16>(m, out.mag2_post.ops, out.mag2_post.n_ops, out.mag2_post.has_div, [](int) { return 0L; }); // (float programs have no index-dependent op)
+            if constexpr (FRONT::kSink) { // the spectrum integrator's sink (specint_kernels.hpp): the values join the lane's leaf sums, nothing is stored
+                front.sink(m);
+            } else {
 #pragma unroll
             for (int j = 0; j < 16; ++j) buf_store_f(r, m[j], eN * 4, j * ST * 4);
+            }
         }
         if (!out.real_input) { // N bins; magnitude and phase are fftshift-ed (bin k -> (k + N/2) mod N), Re/Im natural
             if (out.re) {

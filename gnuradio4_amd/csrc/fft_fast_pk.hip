@@ -7,7 +7,7 @@
 #ifndef GR4_BUF_LOAD_AUX
 #define GR4_BUF_LOAD_AUX 2
 #endif
-#include "pfb_kernels.hpp"
+#include "specint_kernels.hpp"
 
 namespace gr4 {
 int fft_fast_launch_256(const float* d_in, const float* d_window, const float2* d_tw, const FftOutputs& o, long n_frames, hipStream_t st) {
@@ -27,4 +27,10 @@ int pfb_run_launch_8192(int P, const float* x, const float* hist, const float* t
     default: *taken = false; return GR4HIP_OK;
     }
 }
+// the spectrum integrator's sinks of the same two sizes (SPECTRUM_INTEGRATOR.md): their values have to equal these kernels' bit for bit.  8192 points: the 16
+// accumulators do not fit beside the transform's 116 registers, so that size has 256 registers per lane and one workgroup per CU
+int fft_sink_launch_256(const float* x, const float* window, const float2* tw, const SpecintLaunch& L, hipStream_t st) { return fft_sink_launch<8, 2>(x, window, tw, L, st); }
+int fft_sink_launch_8192(const float* x, const float* window, const float2* tw, const SpecintLaunch& L, hipStream_t st) { return fft_sink_launch<13, 2>(x, window, tw, L, st); }
+int pfb_sink_launch_256(const PfbFront& bank, const float2* tw, const SpecintLaunch& L, hipStream_t st) { return pfb_sink_launch<8, 2>(bank, tw, L, st); }
+int pfb_sink_launch_8192(const PfbFront& bank, const float2* tw, const SpecintLaunch& L, hipStream_t st) { return pfb_sink_launch<13, 2>(bank, tw, L, st); }
 } // namespace gr4

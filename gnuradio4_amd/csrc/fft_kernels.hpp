@@ -148,8 +148,9 @@ __device__ __forceinline__ void lds_passes(float2* buf, int t, int tf, const Fft
 // The body of the kernel is fft_fast_frames.inc, included here and by the polyphase filter bank's kernel (pfb_kernels.hpp): the same passes and epilogue
 // behind another first-pass load.  FRONT::kFrontEnd = false is the FFT block's load (frame x window); true hands the lane's 16 points to front.load().
 struct FftWindowFront {
-    static constexpr bool kFrontEnd = false;
+    static constexpr bool kFrontEnd = false, kSink = false;
     template <int N> __device__ __forceinline__ void load(float2 (&)[16], long, unsigned, int, int) const {}
+    __device__ __forceinline__ void sink(const float (&)[16]) const {} // kSink = true: takes the lane's 16 values of |X|^2 instead of their store
     static __device__ __forceinline__ long first_group() { return blockIdx.x; }
     static __device__ __forceinline__ long end_group(long ngroups) { return ngroups; }
     static __device__ __forceinline__ long group_stride() { return gridDim.x; }

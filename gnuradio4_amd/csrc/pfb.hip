@@ -9,7 +9,7 @@
 #ifndef GR4_BUF_STORE_AUX
 #define GR4_BUF_STORE_AUX 2
 #endif
-#include "pfb_kernels.hpp"
+#include "specint_kernels.hpp"
 
 #include <algorithm>
 
@@ -99,6 +99,31 @@ static int pfb_check_taps(const char* who, const float* h, size_t count) {
     return GR4HIP_OK;
 }
 
+// what set_taps / reset left for the next call, on that call's stream
+static int pfb_apply_pending(gr4hip_pfb* f, hipStream_t st) {
+    const size_t hlen = (f->P - 1) * f->N;
+    if (f->taps_dirty) {
+        GR4_HIP_TRY(hipMemcpyAsync(f->d_taps.ptr, f->taps.data(), f->taps.size() * sizeof(float), hipMemcpyHostToDevice, st));
+        f->taps_dirty = false;
+    }
+    if (f->zero_hist) {
+        if (hlen) GR4_HIP_TRY(hipMemsetAsync(f->d_hist[f->cur].ptr, 0, hlen * sizeof(float2), st));
+        f->zero_hist = false;
+    }
+    return GR4HIP_OK;
+}
+
+// the history of the next call, into the other buffer
+static int pfb_carry_history(gr4hip_pfb* f, const void* d_in, size_t n_in, hipStream_t st) {
+    const size_t hlen = (f->P - 1) * f->N;
+    if (!hlen) return GR4HIP_OK;
+    hipLaunchKernelGGL(pfb_hist_kernel, dim3((unsigned)ceil_div(hlen, (size_t)256)), dim3(256), 0, st, static_cast<const float2*>(d_in), (long)n_in,
+                       static_cast<const float2*>(f->d_hist[f->cur].ptr), static_cast<float2*>(f->d_hist[f->cur ^ 1].ptr), (long)hlen);
+    GR4_LAUNCH_CHECK();
+    f->cur ^= 1;
+    return GR4HIP_OK;
+}
+
 extern "C" {
 
 int gr4hip_pfb_design(float* h_out, size_t n_channels, size_t taps_per_channel, int window, float beta) {
@@ -163,7 +188,7 @@ int gr4hip_pfb_process(gr4hip_pfb_t* f, const void* d_in, size_t n_frames, float
     GR4_REQUIRE(d_in, "pfb_process: null input");
     GR4_REQUIRE(d_spectrum || d_mag2, "pfb_process: both outputs are null");
     GR4_REQUIRE((uintptr_t)d_in % 8 == 0 && (uintptr_t)d_spectrum % 8 == 0 && (uintptr_t)d_mag2 % 4 == 0, "pfb_process: complex buffers must be aligned to 8 bytes, |X|^2 to 4");
-    const size_t N = f->N, P = f->P, n_in = n_frames * N, hlen = (P - 1) * N;
+    const size_t N = f->N, P = f->P, n_in = n_frames * N;
     GR4_REQUIRE(n_frames <= (size_t(1) << 40) / N, "pfb_process: %zu frames", n_frames);
     // (below 256 points: one workgroup per fpb frames, no frame loop -- the grid must fit a launch)
     GR4_REQUIRE(N >= 256 || ceil_div(n_frames, (size_t)f->plan.fpb) <= 0x7fffffffu, "pfb_process: %zu frames of %zu points in one call (at most %zu)", n_frames, N, (size_t)0x7fffffffu * f->plan.fpb);
@@ -174,14 +199,7 @@ int gr4hip_pfb_process(gr4hip_pfb_t* f, const void* d_in, size_t n_frames, float
         GR4_REQUIRE(!d_mag2 || a1 <= m0 || m1 <= a0, "pfb_process: d_mag2 overlaps d_in");
     }
     hipStream_t st = as_stream(stream);
-    if (f->taps_dirty) {
-        GR4_HIP_TRY(hipMemcpyAsync(f->d_taps.ptr, f->taps.data(), f->taps.size() * sizeof(float), hipMemcpyHostToDevice, st));
-        f->taps_dirty = false;
-    }
-    if (f->zero_hist) {
-        if (hlen) GR4_HIP_TRY(hipMemsetAsync(f->d_hist[f->cur].ptr, 0, hlen * sizeof(float2), st));
-        f->zero_hist = false;
-    }
+    if (const int rc = pfb_apply_pending(f, st)) return rc;
     PfbFront fe{static_cast<const float*>(d_in), static_cast<const float*>(f->d_hist[f->cur].ptr), static_cast<const float*>(f->d_taps.ptr), (int)P};
     FftOutputs o{};
     o.spectrum    = d_spectrum;
@@ -209,12 +227,36 @@ int gr4hip_pfb_process(gr4hip_pfb_t* f, const void* d_in, size_t n_frames, float
     }
     }
     if (rc) return rc;
-    if (hlen) {
-        hipLaunchKernelGGL(pfb_hist_kernel, dim3((unsigned)ceil_div(hlen, (size_t)256)), dim3(256), 0, st, static_cast<const float2*>(d_in), (long)n_in,
-                           static_cast<const float2*>(f->d_hist[f->cur].ptr), static_cast<float2*>(f->d_hist[f->cur ^ 1].ptr), (long)hlen);
-        GR4_LAUNCH_CHECK();
-        f->cur ^= 1;
+    return pfb_carry_history(f, d_in, n_in, st);
+}
+
+// |X|^2 summed over the integrator's frames (SPECTRUM_INTEGRATOR.md).  256 channels and more: pfb_fast_kernel's frame loop with the sink in place of the
+// store; below that: gr4hip_pfb_process in pieces through the integrator's scratch, then its fold (the history makes the pieces one stream).
+int gr4hip_pfb_power_integrate(gr4hip_pfb_t* f, gr4hip_specint_t* si, const void* d_in, size_t n_frames, float* d_out, size_t* n_out, gr4hip_stream_t stream) {
+    GR4_REQUIRE(f, "pfb_power_integrate: null handle");
+    const size_t N = f->N;
+    if (const int rc = specint_check(si, "pfb_power_integrate", N, d_in, N * sizeof(float2), 8, n_frames, d_out, n_out)) return rc;
+    size_t done = 0;
+    (void)gr4hip_specint_pending(si, n_frames, &done);
+    hipStream_t st = as_stream(stream);
+    if (n_frames > 0 && specint_takes_sink(si, N, f->P)) {
+        if (const int rc = pfb_apply_pending(f, st)) return rc;
+        SpecintLaunch L;
+        if (const int rc = specint_begin(si, n_frames, st, &L)) return rc;
+        const PfbFront fe{static_cast<const float*>(d_in), static_cast<const float*>(f->d_hist[f->cur].ptr), static_cast<const float*>(f->d_taps.ptr), (int)f->P};
+        if (const int rc = specint_sink_pfb(N, fe, static_cast<const float2*>(f->d_tw.ptr), L, st)) return rc;
+        if (const int rc = specint_finish(si, L, d_out, 1, st)) return rc;
+        if (const int rc = pfb_carry_history(f, d_in, n_frames * N, st)) return rc;
+        f->last_run_form = false;
+    } else if (n_frames > 0) {
+        struct Ctx { gr4hip_pfb_t* f; const float2* in; } ctx{f, static_cast<const float2*>(d_in)};
+        const auto produce = [](void* c, size_t first, size_t n, float* d_mag2, hipStream_t s) {
+            auto* x = static_cast<Ctx*>(c);
+            return gr4hip_pfb_process(x->f, x->in + first * x->f->N, n, nullptr, d_mag2, s);
+        };
+        if (const int rc = specint_compose(si, n_frames, d_out, st, produce, &ctx)) return rc;
     }
+    *n_out = done;
     return GR4HIP_OK;
 }
 

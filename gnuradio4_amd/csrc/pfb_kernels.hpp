@@ -14,11 +14,12 @@ namespace gr4 {
 // Descriptors carry exact ranges: the taps [P N], the history [(P - 1) N], and of the input only the frames this group of frame slots needs and the
 // call was given.  The frame-dependent part of an address is in the lane offset, so a frame outside the range reads 0 and nothing outside the spans.
 struct PfbFront {
-    static constexpr bool kFrontEnd = true;
+    static constexpr bool kFrontEnd = true, kSink = false;
     const float* x;    // the call's input, n_frames frames of N complex samples
     const float* hist; // the last P - 1 frames before it
     const float* taps; // h[P N]
     int          P;
+    __device__ __forceinline__ void sink(const float (&)[16]) const {}
 
     // Workgroup g -> group of FPB frames.  Workgroups are dealt to the chip's 8 XCDs round-robin (g mod 8), and each XCD has its own L2: with group g itself, the
     // P - 1 frames a group shares with the one before it were read through ANOTHER XCD's L2.  Where those shared frames are at least a group's own (P - 1 >= FPB)
@@ -97,12 +98,13 @@ struct PfbFront {
 // The sums are those of PfbFront, term for term: the two forms give the same values.
 template <int PT>
 struct PfbRunFront {
-    static constexpr bool kFrontEnd = true;
+    static constexpr bool kFrontEnd = true, kSink = false;
     const float* x;
     const float* hist;
     const float* taps;
     long         L;   // frames per workgroup
     float2*      win; // the lane's window [PT - 1][16], oldest first: an array of the kernel, in registers
+    __device__ __forceinline__ void sink(const float (&)[16]) const {}
 
     __device__ __forceinline__ long first_group() const { return (long)blockIdx.x * L; }
     __device__ __forceinline__ long end_group(long ngroups) const { return first_group() + L < ngroups ? first_group() + L : ngroups; }

@@ -1418,6 +1418,51 @@ struct PfbChannelizer : Block<PfbChannelizer<T>, Resampling<1024, 1024, false>> 
     }
 };
 
+// ---- spectrum integrator behind a power spectrum (SPECTRUM_INTEGRATOR.md -- the reference has no such block, the definition is the project's): the sum (mean:
+// the mean) of n_integrate consecutive frames of vector_size values, one frame out per n_integrate frames in.  One fixed order of additions, on the host as on
+// the device: float32 sums over leaves of gr4hip_specint_leaf() = 32 frames counted from the integration's start, the leaves into a float64 sum in ascending
+// order, one rounding to float32 (mean: after the division by n_integrate in float64).
+// A work() call consumes whole integrations (input_chunk_size = n_integrate * vector_size), so gr:sample_rate is forwarded divided by n_integrate by the
+// Resampling bookkeeping and nothing is carried between calls.  LIMIT: n_integrate * vector_size samples must fit the input edge.  A longer integration is two
+// integrators in a row (A = A1 A2) -- which is ANOTHER order of additions (float32 leaves of the first, rounded to float32, then summed again), not this
+// definition with a larger A.
+template <typename T>
+    requires std::is_same_v<T, float>
+struct SpectrumIntegrator : Block<SpectrumIntegrator<T>, Resampling<1024, 1024, false>> {
+    PortIn<T>  in;
+    PortOut<T> out;
+    Size_t     vector_size = 1024;
+    Size_t     n_integrate = 1;
+    bool       mean        = false;
+    GR_MAKE_REFLECTABLE(SpectrumIntegrator, in, out, vector_size, n_integrate, mean);
+    std::vector<double> _acc;
+    std::vector<float>  _leaf;
+
+    void settingsChanged(const property_map&, const property_map&) {
+        if (vector_size < 2) throw std::invalid_argument("SpectrumIntegrator: vector_size must be >= 2");
+        if (n_integrate == 0) throw std::invalid_argument("SpectrumIntegrator: n_integrate must be >= 1");
+        this->input_chunk_size  = n_integrate * vector_size;
+        this->output_chunk_size = vector_size;
+    }
+    [[nodiscard]] work::Status processBulk(std::span<const T> input, std::span<T> output) {
+        if (this->input_chunk_size != n_integrate * vector_size) settingsChanged({}, {});
+        const std::size_t N = vector_size, A = n_integrate, B = gr4hip_specint_leaf();
+        _acc.resize(N);
+        _leaf.resize(N);
+        for (std::size_t q = 0; (q + 1) * A * N <= input.size(); ++q) {
+            std::fill(_acc.begin(), _acc.end(), 0.0);
+            for (std::size_t s = 0; s < A; s += B) {
+                std::fill(_leaf.begin(), _leaf.end(), 0.f);
+                for (std::size_t f = s; f < std::min(s + B, A); ++f)
+                    for (std::size_t c = 0; c < N; ++c) _leaf[c] = _leaf[c] + input[(q * A + f) * N + c];
+                for (std::size_t c = 0; c < N; ++c) _acc[c] = _acc[c] + static_cast<double>(_leaf[c]);
+            }
+            for (std::size_t c = 0; c < N; ++c) output[q * N + c] = static_cast<float>(mean ? _acc[c] / static_cast<double>(A) : _acc[c]);
+        }
+        return work::Status::OK;
+    }
+};
+
 // ---- gr::blocks::fft::FFT<T> (blocks/fourier/.../fft.hpp:31-251): one DataSet per frame of fftSize samples
 // window (default Hann) -> unnormalised forward DFT -> magnitude (hypot 2/N [dB], fft-shifted) + phase (atan2 [unwrap][deg], shifted) + Re + Im,
 // frequency axis, per-signal min/max.  T = std::complex<float> (N bins) or float (N/2 bins: fft.hpp:140-143, 221-227).

@@ -369,6 +369,31 @@ struct PfbStage final : Stage {
     }
 };
 
+// spectrum integrator (gr4hip_specint_*): whole integrations of A frames of N values in, one frame out each.  `front` set: the stage is the fusion of a
+// PowerSpectrum or PfbPowerSpectrum stage with the integrator behind it -- complex samples in, the transform's |X|^2 summed in its own launch
+// (gr4hip_fft_mag2_integrate / gr4hip_pfb_power_integrate: the values of the two stages in a row, bit for bit)
+struct IntegratorStage final : Stage {
+    gr4hip_specint_t*      h = nullptr;
+    std::size_t            N, A;
+    bool                   mean;
+    std::unique_ptr<Stage> front; // PowerSpectrumStage or PfbStage (|X|^2), or none
+    IntegratorStage(std::size_t n_bins, std::size_t n_integrate, bool mean_, std::unique_ptr<Stage> front_ = nullptr) : N(n_bins), A(n_integrate), mean(mean_), front(std::move(front_)) {
+        in_bytes = front ? 8 : 4; out_bytes = 4; in_chunk = A * N; out_chunk = N;
+        check(gr4hip_specint_create(&h, N, A, mean ? GR4HIP_SPECINT_MEAN : 0), "gr4hip_specint_create");
+    }
+    ~IntegratorStage() override { gr4hip_specint_destroy(h); }
+    std::string_view kind() const override { return !front ? "spectrum_integrator" : dynamic_cast<PfbStage*>(front.get()) ? "pfb_mag2_integrated_c32" : "power_spectrum_integrated_c32"; }
+    int enqueue(const void* in, std::size_t n, void* out, std::size_t* n_out, gr4hip_stream_t s) override {
+        std::size_t spectra = 0;
+        int         rc;
+        if (auto* bank = dynamic_cast<PfbStage*>(front.get())) rc = gr4hip_pfb_power_integrate(bank->h, h, in, n / N, static_cast<float*>(out), &spectra, s);
+        else if (auto* spec = dynamic_cast<PowerSpectrumStage*>(front.get())) rc = gr4hip_fft_mag2_integrate(spec->h, h, in, n / N, static_cast<float*>(out), &spectra, s);
+        else rc = gr4hip_specint_process(h, static_cast<const float*>(in), n / N, static_cast<float*>(out), &spectra, s);
+        *n_out = spectra * N;
+        return rc;
+    }
+};
+
 // fir_filter<complex<float>> -> PowerSpectrum fused into one launch
 struct ChainStage final : Stage {
     gr4hip_chain_t* h = nullptr;
@@ -925,6 +950,12 @@ struct PfbKernel {
 };
 template <> struct Kernel<gr::blocks::fft::PfbPowerSpectrum<std::complex<float>>> : PfbKernel<gr::blocks::fft::PfbPowerSpectrum<std::complex<float>>, true> {};
 template <> struct Kernel<gr::blocks::fft::PfbChannelizer<std::complex<float>>> : PfbKernel<gr::blocks::fft::PfbChannelizer<std::complex<float>>, false> {};
+template <>
+struct Kernel<gr::blocks::fft::SpectrumIntegrator<float>> {
+    using B = gr::blocks::fft::SpectrumIntegrator<float>;
+    static std::unique_ptr<Stage> make_stage(B& b) { return std::make_unique<IntegratorStage>(b.vector_size, b.n_integrate, b.mean); }
+    static work::Status           work(B& b, std::size_t nIn, std::size_t nOut) { return offload_work(b, nIn, nOut, make_stage); }
+};
 
 template <gr::filter::IIRForm form>
 struct Kernel<gr::filter::iir_filter<float, form>> {
@@ -1739,6 +1770,17 @@ inline std::unique_ptr<Stage> fuse_pair(Stage& a, Stage& b) {
         std::vector<float> taps(fir->taps.size());
         for (std::size_t k = 0; k < taps.size(); ++k) taps[k] = static_cast<float>(g * double(fir->taps[k]));
         return std::make_unique<ChainStage>(taps, spec->N, spec->window);
+    }
+    // a power spectrum with the integrator of its size behind it: the sum is taken in the transform's launch
+    if (auto* integ = dynamic_cast<IntegratorStage*>(b.self()); integ && !integ->front) {
+        if (auto* ps = dynamic_cast<PowerSpectrumStage*>(a.self()); ps && ps->N == integ->N) {
+            auto front  = std::make_unique<PowerSpectrumStage>(ps->N, ps->window);
+            front->post = ps->post; // (an epilogue is applied per frame before the sum, as the two stages would)
+            if (!front->post.empty()) front->apply();
+            return std::make_unique<IntegratorStage>(integ->N, integ->A, integ->mean, std::move(front));
+        }
+        if (auto* bank = dynamic_cast<PfbStage*>(a.self()); bank && bank->power && bank->N == integ->N)
+            return std::make_unique<IntegratorStage>(integ->N, integ->A, integ->mean, std::make_unique<PfbStage>(bank->N, bank->P, bank->taps, true));
     }
     return nullptr;
 }

@@ -413,6 +413,37 @@ int gr4hip_pfb_reset(gr4hip_pfb_t* pfb);
 int gr4hip_pfb_process(gr4hip_pfb_t* pfb, const void* d_in, size_t n_frames, float* d_spectrum, float* d_mag2, gr4hip_stream_t stream);
 int gr4hip_pfb_destroy(gr4hip_pfb_t* pfb);
 
+/* Spectrum integrator behind the |X|^2 outputs above: the sum (or mean) of A consecutive power spectra, one spectrum out per A frames in
+ * (SPECTRUM_INTEGRATOR.md).  The reference has no such block: the definition is the project's, tests/spectrum_integrator_oracle.py pins it.  Frames m[f][c],
+ * c < n_bins, float; output q covers frames [q A, (q + 1) A); leaf l of it covers frames q A + [l B, min((l + 1) B, A)), B = gr4hip_specint_leaf() = 32:
+ *   leaf_l[c] = (((0 + m[f0][c]) + m[f0 + 1][c]) + ...)                 float32, frames ascending, one IEEE add per frame
+ *   acc[c]    = ((0 + (double)leaf_0[c]) + (double)leaf_1[c]) + ...     float64, leaves ascending
+ *   y_q[c]    = (float)acc[c]  (flags 0: sum)   or   (float)(acc[c] / (double)A)  (GR4HIP_SPECINT_MEAN)
+ * Every sum has one fixed order, so the values do not depend on how a stream is cut into calls, bit for bit: the handle carries acc, the running leaf and the
+ * frame position inside the integration.  A call that completes no integration writes nothing (d_out may then be NULL); a trailing incomplete integration is
+ * never emitted.  *n_out = spectra written, known on the host without a device sync; gr4hip_specint_pending (host only) says it beforehand.  A = 1 reproduces
+ * the input; non-finite values propagate as IEEE arithmetic gives them and reach exactly the integration that holds their frame.
+ * gr4hip_specint_reset and gr4hip_specint_set_length (which clears the carried state) are stream-ordered (LIFECYCLE CALLS above).
+ * gr4hip_fft_mag2_integrate / gr4hip_pfb_power_integrate: the values of gr4hip_fft_mag2 / gr4hip_pfb_process(d_mag2) followed by gr4hip_specint_process, bit for
+ * bit, without the per-frame spectra in HBM where that measured faster (complex frames, the FFT block at 256 .. 4096 points and the bank with one tap per channel at
+ * 256 .. 8192; SPECTRUM_INTEGRATOR.md); elsewhere the two calls run in pieces through a bounded scratch of 64 MiB in the integrator handle.  At 8192 points they always have the arithmetic gr4hip_fft_mag2 has below 256 frames per call, so that the values
+ * do not depend on the cut.  A gr4hip_fft_set_epilogue program is applied per frame, before the sum.  si's n_bins must be what the transform's |X|^2 call
+ * writes per frame.
+ * GR4HIP_INVALID_ARGUMENT before any device work, outputs untouched: a NULL handle, input or n_out, d_out NULL in a call that completes an integration,
+ * n_bins < 2, n_integrate == 0, unknown flags, buffers not aligned to 4 bytes (complex input: 8), input overlapping output, mismatched n_bins, more than 2^40
+ * values in one call.  GR4HIP_UNSUPPORTED: n_bins > 2^20.  n_frames == 0 is a no-op (*n_out = 0). */
+#define GR4HIP_SPECINT_MEAN 1
+typedef struct gr4hip_specint gr4hip_specint_t;
+int    gr4hip_specint_create(gr4hip_specint_t** si, size_t n_bins, size_t n_integrate, int flags);
+int    gr4hip_specint_reset(gr4hip_specint_t* si);
+int    gr4hip_specint_set_length(gr4hip_specint_t* si, size_t n_integrate);
+int    gr4hip_specint_pending(const gr4hip_specint_t* si, size_t n_frames, size_t* n_out);
+int    gr4hip_specint_process(gr4hip_specint_t* si, const float* d_frames, size_t n_frames, float* d_out, size_t* n_out, gr4hip_stream_t stream);
+int    gr4hip_specint_destroy(gr4hip_specint_t* si);
+size_t gr4hip_specint_leaf(void);
+int    gr4hip_fft_mag2_integrate(gr4hip_fft_t* fft, gr4hip_specint_t* si, const void* d_in, size_t n_frames, float* d_out, size_t* n_out, gr4hip_stream_t stream);
+int    gr4hip_pfb_power_integrate(gr4hip_pfb_t* pfb, gr4hip_specint_t* si, const void* d_in, size_t n_frames, float* d_out, size_t* n_out, gr4hip_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------ headline chain
  * complex<float> fir_filter -> FFT block frames -> |X|^2 (BASELINE.json configs[1]).  One call consumes
  * floor(n_samples / fft_size) frames; FIR history (ntaps-1 samples) is carried across calls.
