@@ -575,6 +575,72 @@ class SpectrumIntegrator(_Handle):
         return self._run(lib().gr4hip_specint_process, None, x, x.numel() // self.n_bins, out, "SpectrumIntegrator.process_bulk")
 
 
+class CrossSpectrum(_Handle):
+    """The averaged cross-spectral matrix of n_streams (2 .. 32) streams of complex spectra of n_bins values, V_ij[c] = sum_m X_i[m][c] conj(X_j[m][c]) over
+    n_integrate frames (mean=True: divided by n_integrate) -- the project's own definition, CROSS_SPECTRUM.md: float32 fma chains over leaves of 64 frames, folded
+    in float64, one fixed order.  Baselines are the lower triangle j <= i, packed p = i (i + 1) / 2 + j.  The partial integration is carried across calls; a call
+    returns the matrices it completes, complex64 [pending(frames), P, n_bins]."""
+    _destroy = "gr4hip_xcorr_destroy"
+
+    def __init__(self, n_streams: int, n_bins: int, n_integrate: int, mean: bool = False):
+        super().__init__()
+        self.n_streams, self.n_bins, self.n_integrate, self.mean = int(n_streams), int(n_bins), int(n_integrate), bool(mean)
+        self.n_baselines = self.n_streams * (self.n_streams + 1) // 2
+        check(lib().gr4hip_xcorr_create(C.byref(self._h), self.n_streams, self.n_bins, self.n_integrate, capi.XCORR_MEAN if self.mean else 0), "CrossSpectrum")
+
+    def reset(self):
+        """drops the partial integration (from the next call on)"""
+        check(lib().gr4hip_xcorr_reset(self._h), "CrossSpectrum.reset")
+
+    def set_length(self, n_integrate: int):
+        """another integration length; the partial integration is dropped"""
+        check(lib().gr4hip_xcorr_set_length(self._h, int(n_integrate)), "CrossSpectrum.set_length")
+        self.n_integrate = int(n_integrate)
+
+    def pending(self, n_frames: int) -> int:
+        """matrices the next call of n_frames frames per stream completes (host only)"""
+        n = C.c_size_t(0)
+        check(lib().gr4hip_xcorr_pending(self._h, int(n_frames), C.byref(n)), "CrossSpectrum.pending")
+        return int(n.value)
+
+    def baseline(self, i: int, j: int) -> int:
+        """the row of the pair (i, j), j <= i, in an emitted matrix"""
+        if not 0 <= j <= i < self.n_streams:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "CrossSpectrum.baseline", f"expected 0 <= j <= i < {self.n_streams}")
+        return i * (i + 1) // 2 + j
+
+    def process_bulk(self, spectra, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """spectra: a sequence of n_streams complex64 tensors of whole frames (the same tensor may appear twice), or one [n_streams, frames, n_bins] tensor"""
+        what = "CrossSpectrum.process_bulk"
+        xs = [_dev(x, what) for x in (spectra.unbind(0) if isinstance(spectra, torch.Tensor) else spectra)]
+        if len(xs) != self.n_streams or any(x.dtype != torch.complex64 or x.numel() != xs[0].numel() or x.device != xs[0].device for x in xs) or xs[0].numel() % self.n_bins:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, what, f"expected {self.n_streams} complex64 streams of equally many whole frames of {self.n_bins} values")
+        frames = xs[0].numel() // self.n_bins
+        n = self.pending(frames)
+        shape = (n, self.n_baselines, self.n_bins)
+        out = _out(out, n * self.n_baselines * self.n_bins, torch.complex64, xs[0], what, shape)
+        ptrs = (C.c_void_p * self.n_streams)(*[x.data_ptr() for x in xs])
+        got = C.c_size_t(0)
+        check(lib().gr4hip_xcorr_process(self._h, ptrs, frames, out.data_ptr() if n else None, C.byref(got), _stream()), what)
+        assert got.value == n
+        return out.reshape(-1)[:n * self.n_baselines * self.n_bins].view(shape)
+
+    def coherence(self, vis: torch.Tensor, i: int, j: int):
+        """(msc, h1) of the pair (i, j), any order, from emitted matrices vis [..., P, n_bins]: the magnitude-squared coherence |V_ij|^2 / (V_ii V_jj), float32
+        [..., n_bins], and the H1 transfer-function estimate V_ij / V_jj, complex64 [..., n_bins] -- both from float64 arithmetic rounded once"""
+        what = "CrossSpectrum.coherence"
+        v = _dev(vis, what)
+        if v.dtype != torch.complex64 or v.dim() < 2 or tuple(v.shape[-2:]) != (self.n_baselines, self.n_bins):
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, what, f"expected complex64 [..., {self.n_baselines}, {self.n_bins}]")
+        lead = tuple(v.shape[:-2])
+        n = v.numel() // (self.n_baselines * self.n_bins)
+        msc = torch.empty(lead + (self.n_bins,), dtype=torch.float32, device=v.device)
+        h1 = torch.empty(lead + (self.n_bins,), dtype=torch.complex64, device=v.device)
+        if n:
+            check(lib().gr4hip_xcorr_coherence(v.data_ptr(), self.n_streams, self.n_bins, n, int(i), int(j), msc.data_ptr(), h1.data_ptr(), _stream()), what)
+        return msc, h1
+
+
 class Chain(_Handle):
     """complex<float> fir_filter -> FFT frames -> |X|^2, one fused device pipeline (BASELINE.json configs[1])."""
     _destroy = "gr4hip_chain_destroy"

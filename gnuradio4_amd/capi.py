@@ -17,6 +17,8 @@ WINDOWS = ["None", "Rectangular", "Hamming", "Hann", "HannExp", "Blackman", "Nut
            "BlackmanNuttall", "FlatTop", "Exponential", "Kaiser"]
 FFT_OUTPUT_IN_DB, FFT_OUTPUT_IN_DEG, FFT_UNWRAP_PHASE = 1, 2, 4
 SPECINT_MEAN = 1
+XCORR_MEAN = 1
+XCORR_MAX_STREAMS = 32
 CHAIN_AUTO, CHAIN_UNFUSED, CHAIN_FUSED_TD, CHAIN_FUSED_FD, CHAIN_TIME_DOMAIN = range(5)
 GUARD_STRICT, GUARD_DEFERRED, GUARD_OFF = range(3)
 FIR_AUTO, FIR_TIME_DOMAIN, FIR_EXACT_F32, FIR_TIME_DOMAIN_F32, FIR_TIME_DOMAIN_BF16X3 = range(5)
@@ -127,6 +129,14 @@ SIGNATURES = {
     "gr4hip_specint_leaf": (_sz, []),
     "gr4hip_fft_mag2_integrate": (_i, [_vp, _vp, _vp, _sz, _vp, _psz, _vp]),
     "gr4hip_pfb_power_integrate": (_i, [_vp, _vp, _vp, _sz, _vp, _psz, _vp]),
+    "gr4hip_xcorr_create": (_i, [_pvp, _sz, _sz, _sz, _i]),
+    "gr4hip_xcorr_reset": (_i, [_vp]),
+    "gr4hip_xcorr_set_length": (_i, [_vp, _sz]),
+    "gr4hip_xcorr_pending": (_i, [_vp, _sz, _psz]),
+    "gr4hip_xcorr_process": (_i, [_vp, _pvp, _sz, _vp, _psz, _vp]),
+    "gr4hip_xcorr_destroy": (_i, [_vp]),
+    "gr4hip_xcorr_leaf": (_sz, []),
+    "gr4hip_xcorr_coherence": (_i, [_vp, _sz, _sz, _sz, _sz, _sz, _vp, _vp, _vp]),
     "gr4hip_decimate": (_i, [_i, _vp, _sz, _sz, _vp, _psz, _vp]),
     "gr4hip_iir_create": (_i, [_pvp, _i, _sz, _vp, _sz, _vp, _sz]),
     "gr4hip_iir_reset": (_i, [_vp]),

@@ -1463,6 +1463,73 @@ struct SpectrumIntegrator : Block<SpectrumIntegrator<T>, Resampling<1024, 1024, 
     }
 };
 
+// ---- cross-spectrum correlator behind n_inputs spectra (CROSS_SPECTRUM.md -- the reference has no such block, the definition is the project's): the averaged
+// cross-spectral matrix V_ij[c] = sum_m X_i[m][c] conj(X_j[m][c]) over n_integrate frames of vector_size bins, baselines j <= i packed p = i (i + 1) / 2 + j, one
+// matrix [P][vector_size] out per n_integrate frames in on every input.  One fixed order of operations, on the host as on the device: per pair and bin a float32
+// fma chain over leaves of gr4hip_xcorr_leaf() = 64 frames counted from the integration's start
+//     re = fmaf(xr_i, xr_j, re);  re = fmaf(xi_i, xi_j, re);  im = fmaf(xi_i, xr_j, im);  im = fmaf(-xr_i, xi_j, im);
+// the leaves into float64 sums in ascending order, one rounding to float32 (mean: after the division by n_integrate in float64); the imaginary part of the
+// diagonal is +0.  A work() call consumes whole integrations (input_chunk_size = n_integrate * vector_size per input, output_chunk_size = P * vector_size), so
+// gr:sample_rate is forwarded scaled by P / n_integrate by the Resampling bookkeeping and nothing is carried between calls.
+template <typename T>
+    requires std::is_same_v<T, float>
+struct CrossSpectrum : Block<CrossSpectrum<T>, Resampling<1024, 3072, false>> {
+    std::vector<PortIn<std::complex<T>>> in{2};
+    PortOut<std::complex<T>>             out;
+    Size_t                               n_inputs    = 2;
+    Size_t                               vector_size = 1024;
+    Size_t                               n_integrate = 1;
+    bool                                 mean        = false;
+    GR_MAKE_REFLECTABLE(CrossSpectrum, in, out, n_inputs, vector_size, n_integrate, mean);
+    std::vector<double> _acc;
+    std::vector<float>  _leaf;
+
+    [[nodiscard]] std::size_t nBaselines() const { return static_cast<std::size_t>(n_inputs) * (n_inputs + 1) / 2; }
+
+    void settingsChanged(const property_map&, const property_map&) {
+        if (n_inputs < 2 || n_inputs > 32) throw std::invalid_argument("CrossSpectrum: n_inputs must be in [2, 32]");
+        if (vector_size < 2) throw std::invalid_argument("CrossSpectrum: vector_size must be >= 2");
+        if (n_integrate == 0) throw std::invalid_argument("CrossSpectrum: n_integrate must be >= 1");
+        if (in.size() != n_inputs) in.resize(n_inputs);
+        this->input_chunk_size  = n_integrate * vector_size;
+        this->output_chunk_size = nBaselines() * vector_size;
+    }
+    [[nodiscard]] work::Status processBulk(std::span<const std::span<const std::complex<T>>> ins, std::span<std::complex<T>> output) {
+        if (this->input_chunk_size != n_integrate * vector_size || this->output_chunk_size != nBaselines() * vector_size) settingsChanged({}, {});
+        const std::size_t S = ins.size(), N = vector_size, A = n_integrate, B = gr4hip_xcorr_leaf(), P = S * (S + 1) / 2;
+        _acc.resize(2 * N);
+        _leaf.resize(2 * N);
+        for (std::size_t q = 0; (q + 1) * A * N <= ins[0].size(); ++q) {
+            for (std::size_t i = 0, p = 0; i < S; ++i) {
+                for (std::size_t j = 0; j <= i; ++j, ++p) {
+                    std::fill(_acc.begin(), _acc.end(), 0.0);
+                    for (std::size_t s = 0; s < A; s += B) {
+                        std::fill(_leaf.begin(), _leaf.end(), 0.f);
+                        for (std::size_t f = s; f < std::min(s + B, A); ++f) {
+                            const std::complex<T>* xi = ins[i].data() + (q * A + f) * N;
+                            const std::complex<T>* xj = ins[j].data() + (q * A + f) * N;
+                            for (std::size_t c = 0; c < N; ++c) {
+                                float re = _leaf[2 * c], im = _leaf[2 * c + 1];
+                                re = std::fmaf(xi[c].real(), xj[c].real(), re);
+                                re = std::fmaf(xi[c].imag(), xj[c].imag(), re);
+                                im = std::fmaf(xi[c].imag(), xj[c].real(), im);
+                                im = std::fmaf(-xi[c].real(), xj[c].imag(), im);
+                                _leaf[2 * c] = re, _leaf[2 * c + 1] = im;
+                            }
+                        }
+                        for (std::size_t c = 0; c < 2 * N; ++c) _acc[c] = _acc[c] + static_cast<double>(_leaf[c]);
+                    }
+                    for (std::size_t c = 0; c < N; ++c) {
+                        const double re = mean ? _acc[2 * c] / static_cast<double>(A) : _acc[2 * c], im = mean ? _acc[2 * c + 1] / static_cast<double>(A) : _acc[2 * c + 1];
+                        output[(q * P + p) * N + c] = std::complex<T>(static_cast<float>(re), i == j ? 0.f : static_cast<float>(im));
+                    }
+                }
+            }
+        }
+        return work::Status::OK;
+    }
+};
+
 // ---- gr::blocks::fft::FFT<T> (blocks/fourier/.../fft.hpp:31-251): one DataSet per frame of fftSize samples
 // window (default Hann) -> unnormalised forward DFT -> magnitude (hypot 2/N [dB], fft-shifted) + phase (atan2 [unwrap][deg], shifted) + Re + Im,
 // frequency axis, per-signal min/max.  T = std::complex<float> (N bins) or float (N/2 bins: fft.hpp:140-143, 221-227).

@@ -1818,6 +1818,50 @@ struct Kernel<gr::blocks::math::MathOpMultiPortImpl<T, op>> {
     }
 };
 
+// CrossSpectrum<float>: n_inputs spectra -> one stream of cross-spectral matrices at the seam, like the N-input math blocks (no Stage: a fan-in is not part of a
+// linear device run).  The input spans go to HBM as rows of one buffer in one copy, one gr4hip_xcorr_process, the matrices back.  A work() call hands over whole
+// integrations, so the handle carries nothing between calls; other settings make a new handle.
+template <>
+struct Kernel<gr::blocks::fft::CrossSpectrum<float>> {
+    using B = gr::blocks::fft::CrossSpectrum<float>;
+    struct State final : Offload {
+        gr4hip_xcorr_t* h = nullptr;
+        std::size_t     S = 0, N = 0, A = 0;
+        bool            mean = false;
+        ~State() override { if (h) gr4hip_xcorr_destroy(h); }
+    };
+    static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
+        try {
+            State*            st = offload_state<State>(blk);
+            const std::size_t S = blk.in.size(), N = blk.vector_size, A = blk.n_integrate;
+            if (!st->h || st->S != S || st->N != N || st->A != A || st->mean != blk.mean) {
+                if (st->h) gr4hip_xcorr_destroy(st->h);
+                st->h = nullptr;
+                check(gr4hip_xcorr_create(&st->h, S, N, A, blk.mean ? GR4HIP_XCORR_MEAN : 0), "gr4hip_xcorr_create");
+                st->S = S; st->N = N; st->A = A; st->mean = blk.mean;
+            }
+            if (nIn % (A * N) != 0 || nOut != nIn / (A * N) * blk.nBaselines() * N) throw std::runtime_error("CrossSpectrum: the work loop must hand over whole integrations");
+            const std::size_t bi = nIn * sizeof(std::complex<float>), bo = nOut * sizeof(std::complex<float>);
+            char*             hin = static_cast<char*>(st->h_in.ensure(S * bi));
+            for (std::size_t s = 0; s < S; ++s) std::memcpy(hin + s * bi, blk.in[s].buffer->read_span(nIn).data(), bi);
+            char* din = static_cast<char*>(st->d_in.ensure(S * bi));
+            check(gr4hip_memcpy_h2d(din, hin, S * bi, nullptr), "h2d");
+            std::vector<const float*> ptrs(S);
+            for (std::size_t s = 0; s < S; ++s) ptrs[s] = reinterpret_cast<const float*>(din + s * bi);
+            std::size_t produced = 0;
+            check(gr4hip_xcorr_process(st->h, ptrs.data(), nIn / N, static_cast<float*>(st->d_out.ensure(bo)), &produced, nullptr), "gr4hip_xcorr_process");
+            if (produced * blk.nBaselines() * N != nOut) throw std::runtime_error("CrossSpectrum: the device wrote another number of matrices than the work loop expects");
+            check(gr4hip_memcpy_d2h(st->h_out.ensure(bo), st->d_out.p, bo, nullptr), "d2h");
+            check(gr4hip_stream_synchronize(nullptr), "sync");
+            if (blk.out.connected()) std::memcpy(blk.out.buffer->write_span(nOut).data(), st->h_out.p, bo);
+            return work::Status::OK;
+        } catch (const std::exception& e) {
+            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
+            return work::Status::ERROR; // never a silent host fallback
+        }
+    }
+};
+
 // FFT block: nOut frames of fftSize samples in, nOut DataSets out.  The four signals and their ranges are computed on the device
 // (gr4hip_fft_process); the host only assembles the descriptive part of the DataSet (axis, names, meta information).
 template <typename T>

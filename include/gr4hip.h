@@ -444,6 +444,41 @@ size_t gr4hip_specint_leaf(void);
 int    gr4hip_fft_mag2_integrate(gr4hip_fft_t* fft, gr4hip_specint_t* si, const void* d_in, size_t n_frames, float* d_out, size_t* n_out, gr4hip_stream_t stream);
 int    gr4hip_pfb_power_integrate(gr4hip_pfb_t* pfb, gr4hip_specint_t* si, const void* d_in, size_t n_frames, float* d_out, size_t* n_out, gr4hip_stream_t stream);
 
+/* Cross-spectrum correlator (X-engine) behind the spectra above: the averaged cross-spectral matrix of S streams, 1 < S <= 32 (CROSS_SPECTRUM.md).  The reference
+ * has no such block: the definition is the project's, tests/cross_spectrum_oracle.py pins it.  Each stream is a sequence of frames X_s[f][c], c < n_bins,
+ * complex<float> -- what gr4hip_fft_spectrum / gr4hip_pfb_process(d_spectrum) write.  Output q covers frames [q A, (q + 1) A); leaf l of it covers frames
+ * q A + [l B, min((l + 1) B, A)), B = gr4hip_xcorr_leaf() = 64; baselines are the lower triangle j <= i, packed p = i (i + 1) / 2 + j, P = S (S + 1) / 2:
+ *   per leaf, per (i, j), per bin, float32, frames ascending, re = im = +0 at the leaf's start:
+ *       re = fmaf(xr_i, xr_j, re);   re = fmaf(xi_i, xi_j, re);
+ *       im = fmaf(xi_i, xr_j, im);   im = fmaf(-xr_i, xi_j, im);
+ *   acc_re, acc_im: float64, leaves ascending, ((0 + (double)leaf_0) + (double)leaf_1) + ...
+ *   V_q[p][c] = ((float)acc_re, (float)acc_im)  (flags 0: sum)   or   ((float)(acc_re / A), (float)(acc_im / A))  (GR4HIP_XCORR_MEAN)
+ *   the imaginary part of the diagonal (i == j) is written as exactly +0.0f
+ * d_out[q][p][c], interleaved complex, bin fastest.  Every sum has one order, so the values do not depend on how the stream is cut into calls or on which kernel
+ * ran, bit for bit: the handle carries acc, the running leaf and the frame position.  A call that completes no integration writes nothing (d_out may then be
+ * NULL); a trailing incomplete integration is never emitted.  *n_out = matrices written, known on the host without a device sync; gr4hip_xcorr_pending (host
+ * only) says it beforehand.  Non-finite values propagate as IEEE arithmetic gives them and reach only the baselines that contain their stream, in the
+ * integration and bin that hold them.  d_spectra is a HOST array of S device pointers, each [n_frames][n_bins] complex; the same pointer may appear twice.
+ * gr4hip_xcorr_reset and gr4hip_xcorr_set_length (which clears the carried state) are stream-ordered (LIFECYCLE CALLS above).
+ * gr4hip_xcorr_coherence: stateless, from n_spectra emitted matrices d_vis[n_spectra][P][n_bins] for one pair (i, j), any i, j < S (i < j: V_ji with the
+ * imaginary part negated); either output may be NULL, not both:
+ *   d_msc[n_spectra][n_bins]         = (float)(((double)re re + (double)im im) / ((double)V_ii (double)V_jj))     magnitude-squared coherence
+ *   d_h1[n_spectra][n_bins] complex  = ((float)((double)re / (double)V_jj), (float)((double)im / (double)V_jj))   H1 = V_ij / V_jj
+ * GR4HIP_INVALID_ARGUMENT before any device work, outputs untouched: a NULL handle, pointer array, entry of it or n_out, d_out NULL in a call that completes an
+ * integration, n_streams < 2, n_bins < 2, n_integrate == 0, unknown flags, inputs or output not aligned to 8 bytes (d_msc: 4), the output overlapping an input,
+ * i or j >= S, more than 2^40 input values per stream in one call.  GR4HIP_UNSUPPORTED: n_streams > 32, n_bins > 2^20, P n_bins > 2^24.  n_frames == 0 is a
+ * no-op (*n_out = 0). */
+#define GR4HIP_XCORR_MEAN 1
+typedef struct gr4hip_xcorr gr4hip_xcorr_t;
+int    gr4hip_xcorr_create(gr4hip_xcorr_t** xc, size_t n_streams, size_t n_bins, size_t n_integrate, int flags);
+int    gr4hip_xcorr_reset(gr4hip_xcorr_t* xc);
+int    gr4hip_xcorr_set_length(gr4hip_xcorr_t* xc, size_t n_integrate);
+int    gr4hip_xcorr_pending(const gr4hip_xcorr_t* xc, size_t n_frames, size_t* n_out);
+int    gr4hip_xcorr_process(gr4hip_xcorr_t* xc, const float* const* d_spectra, size_t n_frames, float* d_out, size_t* n_out, gr4hip_stream_t stream);
+int    gr4hip_xcorr_destroy(gr4hip_xcorr_t* xc);
+size_t gr4hip_xcorr_leaf(void);
+int    gr4hip_xcorr_coherence(const float* d_vis, size_t n_streams, size_t n_bins, size_t n_spectra, size_t i, size_t j, float* d_msc, float* d_h1, gr4hip_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------ headline chain
  * complex<float> fir_filter -> FFT block frames -> |X|^2 (BASELINE.json configs[1]).  One call consumes
  * floor(n_samples / fft_size) frames; FIR history (ntaps-1 samples) is carried across calls.
