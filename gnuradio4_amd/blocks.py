@@ -533,6 +533,71 @@ class PolyphaseFilterBank(_Handle):
         return integrator._run(lib().gr4hip_pfb_power_integrate, self._h, x, x.numel() // self.n_channels, out, "PolyphaseFilterBank.power_integrated")
 
 
+class InverseFFT(_Handle):
+    """The unnormalised inverse of the FFT block's transform (algorithm::FFT's Direction::Backward, algorithm/.../fourier/fft.hpp:260-314; INVERSE_FFT.md):
+    frames of fftSize complex64 bins in natural order -> [frames, fftSize] complex64, or float32 (the packed complex-to-real form: bins 0 .. N/2 are used, the
+    rest is ignored).  scale=True multiplies by 1 / fftSize; `window` is a synthesis window multiplied onto the samples."""
+    _destroy = "gr4hip_ifft_destroy"
+
+    def __init__(self, fftSize: int = 1024, dtype=torch.complex64, window="None", scale: bool = False):
+        super().__init__()
+        if dtype not in (torch.complex64, torch.float32):
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "InverseFFT", f"output dtype must be complex64 or float32, got {dtype}")
+        self.fftSize, self.dtype, self.window, self.scale = int(fftSize), dtype, window, bool(scale)
+        self.input_chunk_size = self.fftSize
+        check(lib().gr4hip_ifft_create(C.byref(self._h), _DTYPE_ID[dtype], self.fftSize, _window_id(window), capi.IFFT_SCALE if self.scale else 0), "InverseFFT")
+
+    def process_bulk(self, spectra: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        x = _dev(spectra, "InverseFFT")
+        if x.dtype != torch.complex64:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "InverseFFT", f"expected {torch.complex64}, got {x.dtype}")
+        if x.numel() % self.fftSize:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "InverseFFT", f"{x.numel()} bins are not whole frames of {self.fftSize}")
+        frames = x.numel() // self.fftSize
+        out = _out(out, frames * self.fftSize, self.dtype, x, "InverseFFT", (frames, self.fftSize))
+        check(lib().gr4hip_ifft_process(self._h, x.data_ptr(), frames, out.data_ptr(), _stream()), "InverseFFT.process")
+        return out
+
+
+class PolyphaseSynthesisBank(_Handle):
+    """Critically sampled polyphase synthesis bank behind the inverse transform (the project's own definition, INVERSE_FFT.md): v_m = IFFT_N(Y_m),
+    y[m N + i] = sum_k g[k N + i] v_{m - k}[i].  complex64 in and out, N values per frame in, N samples out, the last P - 1 transformed frames carried across
+    calls.  `taps` = P N float values (None: design_pfb with `window`).  With the analysis bank's prototype it is that bank's adjoint, not its inverse."""
+    _destroy = "gr4hip_pfb_synth_destroy"
+
+    def __init__(self, n_channels: int, taps_per_channel: int, taps=None, window="Hamming", scale: bool = False):
+        super().__init__()
+        self.n_channels, self.taps_per_channel, self.dtype, self.scale = int(n_channels), int(taps_per_channel), torch.complex64, bool(scale)
+        self.taps = None
+        if taps is not None:
+            self.taps = np.ascontiguousarray(taps, np.float32)
+            if self.taps.size != self.n_channels * self.taps_per_channel:
+                raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "PolyphaseSynthesisBank", f"{self.taps.size} taps, the bank has {self.taps_per_channel} x {self.n_channels}")
+        elif _window_id(window) != _window_id("Hamming"):  # (Hamming is the library's own default design)
+            self.taps = design_pfb(self.n_channels, self.taps_per_channel, window)
+        check(lib().gr4hip_pfb_synth_create(C.byref(self._h), self.n_channels, self.taps_per_channel, self.taps.ctypes.data if self.taps is not None else None,
+                                            capi.IFFT_SCALE if self.scale else 0), "PolyphaseSynthesisBank")
+
+    def set_taps(self, taps):
+        """new prototype from the next call on; the history is kept"""
+        self.taps = np.ascontiguousarray(taps, np.float32)
+        check(lib().gr4hip_pfb_synth_set_taps(self._h, self.taps.ctypes.data, self.taps.size), "PolyphaseSynthesisBank.set_taps")
+
+    def reset(self):
+        check(lib().gr4hip_pfb_synth_reset(self._h), "PolyphaseSynthesisBank.reset")
+
+    def process_bulk(self, spectra: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        x = _dev(spectra, "PolyphaseSynthesisBank")
+        if x.dtype != self.dtype:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "PolyphaseSynthesisBank", f"expected {self.dtype}, got {x.dtype}")
+        if x.numel() % self.n_channels:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "PolyphaseSynthesisBank", f"{x.numel()} values are not whole frames of {self.n_channels}")
+        frames = x.numel() // self.n_channels
+        out = _out(out, frames * self.n_channels, torch.complex64, x, "PolyphaseSynthesisBank", (frames, self.n_channels))
+        check(lib().gr4hip_pfb_synth_process(self._h, x.data_ptr(), frames, out.data_ptr(), _stream()), "PolyphaseSynthesisBank.process")
+        return out
+
+
 class SpectrumIntegrator(_Handle):
     """Sum (mean=True: mean) of n_integrate consecutive power spectra of n_bins values, one spectrum out per n_integrate frames in (the project's own definition,
     SPECTRUM_INTEGRATOR.md: float32 leaves of 32 frames, folded in float64, one fixed order).  The partial integration is carried across calls; a call returns the

@@ -17,6 +17,7 @@ WINDOWS = ["None", "Rectangular", "Hamming", "Hann", "HannExp", "Blackman", "Nut
            "BlackmanNuttall", "FlatTop", "Exponential", "Kaiser"]
 FFT_OUTPUT_IN_DB, FFT_OUTPUT_IN_DEG, FFT_UNWRAP_PHASE = 1, 2, 4
 SPECINT_MEAN = 1
+IFFT_SCALE = 1
 XCORR_MEAN = 1
 XCORR_MAX_STREAMS = 32
 CHAIN_AUTO, CHAIN_UNFUSED, CHAIN_FUSED_TD, CHAIN_FUSED_FD, CHAIN_TIME_DOMAIN = range(5)
@@ -120,6 +121,14 @@ SIGNATURES = {
     "gr4hip_pfb_reset": (_i, [_vp]),
     "gr4hip_pfb_process": (_i, [_vp, _vp, _sz, _vp, _vp, _vp]),
     "gr4hip_pfb_destroy": (_i, [_vp]),
+    "gr4hip_ifft_create": (_i, [_pvp, _i, _sz, _i, _i]),
+    "gr4hip_ifft_process": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "gr4hip_ifft_destroy": (_i, [_vp]),
+    "gr4hip_pfb_synth_create": (_i, [_pvp, _sz, _sz, _vp, _i]),
+    "gr4hip_pfb_synth_set_taps": (_i, [_vp, _vp, _sz]),
+    "gr4hip_pfb_synth_reset": (_i, [_vp]),
+    "gr4hip_pfb_synth_process": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "gr4hip_pfb_synth_destroy": (_i, [_vp]),
     "gr4hip_specint_create": (_i, [_pvp, _sz, _sz, _i]),
     "gr4hip_specint_reset": (_i, [_vp]),
     "gr4hip_specint_set_length": (_i, [_vp, _sz]),

@@ -1,5 +1,5 @@
 // fft_fast_frames.inc -- the body of fft_fast_kernel<LOG2N, REAL> (fft_kernels.hpp), included textually by every kernel that runs its frame loop, so that all of
-// them compile the same statements.  Expects in scope: LOG2N, REAL, FRONT / front (the first-pass load; FRONT::kSink: it takes |X|^2 instead of the store), in,
+// them compile the same statements.  Expects in scope: LOG2N, REAL, FRONT / front (the first-pass load; FRONT::kSink: it takes |X|^2 instead of the store; FRONT::kBinSink: it takes the bins instead of every store), in,
 // window, tw, out (FftOutputs), n_frames.
     constexpr int N = 1 << LOG2N, T = N / 16, FPB = 512 / T, NP = N + N / 32, HALF = N / 2;
     constexpr int TWS = REAL ? 2 : 1; // stride of W_N^j in the table
@@ -204,6 +204,9 @@
         const int     eN = R4 == 2 ? (t >> 1) + 4096 * (t & 1) : fl * N + t;
         const int     eS = R4 == 2 ? (t >> 1) + 4096 * (1 - (t & 1)) : eN;
         auto          soff = [](int j) { return R4 == 2 ? j * ST : (j * ST + HALF) % N; };
+        if constexpr (front_bin_sink<FRONT>::value) { // the inverse transform's store (ifft_kernels.hpp): X[j] is then sample eN + j ST, sample (eN - fl N) + j ST of its frame
+            front_store_bins<N, ST>(front, X, f0, nlive, eN, R4 == 2 ? eN : t);
+        } else {
         if (out.spectrum) {
             const rsrc_t r = make_rsrc(out.spectrum + f0 * N * 2, nlive * N * 8u);
 #pragma unroll
@@ -293,6 +296,7 @@
                 }
             }
         }
+        } // !front_bin_sink
         } // !REAL
         if (out.ranges) { // reduce over the T lanes of the frame: butterflies inside the wave, then (T > 64) through LDS
 #pragma unroll

@@ -8,6 +8,7 @@
 #define GR4_BUF_LOAD_AUX 2
 #endif
 #include "specint_kernels.hpp"
+#include "ifft_kernels.hpp"
 
 namespace gr4 {
 int fft_fast_launch_256(const float* d_in, const float* d_window, const float2* d_tw, const FftOutputs& o, long n_frames, hipStream_t st) {
@@ -33,4 +34,11 @@ int fft_sink_launch_256(const float* x, const float* window, const float2* tw, c
 int fft_sink_launch_8192(const float* x, const float* window, const float2* tw, const SpecintLaunch& L, hipStream_t st) { return fft_sink_launch<13, 2>(x, window, tw, L, st); }
 int pfb_sink_launch_256(const PfbFront& bank, const float2* tw, const SpecintLaunch& L, hipStream_t st) { return pfb_sink_launch<8, 2>(bank, tw, L, st); }
 int pfb_sink_launch_8192(const PfbFront& bank, const float2* tw, const SpecintLaunch& L, hipStream_t st) { return pfb_sink_launch<13, 2>(bank, tw, L, st); }
+// the inverse transform's kernels of the same two sizes (INVERSE_FFT.md): the forward kernels' statements, so the forward kernels' values
+int ifft_fast_launch_256(bool c2r, const float* d_in, float* d_out, const float* d_window, float scale, const float2* d_tw, long n_frames, hipStream_t st) {
+    return ifft_fast_launch<8>(c2r, d_in, d_out, d_window, scale, d_tw, n_frames, st);
+}
+int ifft_fast_launch_8192(bool c2r, const float* d_in, float* d_out, const float* d_window, float scale, const float2* d_tw, long n_frames, hipStream_t st) {
+    return ifft_fast_launch<13>(c2r, d_in, d_out, d_window, scale, d_tw, n_frames, st);
+}
 } // namespace gr4

@@ -11,6 +11,7 @@
 #include <cfloat>
 #include <cmath>
 #include <complex>
+#include <type_traits>
 
 
 namespace gr4 {
@@ -156,6 +157,15 @@ struct FftWindowFront {
     static __device__ __forceinline__ long group_stride() { return gridDim.x; }
     template <int FPB> static __device__ __forceinline__ long group(long g, long) { return g; } // which group of frames workgroup iteration g takes
 };
+// A front that declares kBinSink = true also takes the lane's 16 register-held bins, with their positions, in place of every store of the epilogue (the inverse
+// transform, ifft_kernels.hpp).  The fronts above and the bank's do not name it: for them the body compiles to what it was.
+template <class F, class = void> struct front_bin_sink { static constexpr bool value = false; };
+template <class F> struct front_bin_sink<F, std::enable_if_t<F::kBinSink>> { static constexpr bool value = true; };
+template <int N, int ST, class F>
+__device__ __forceinline__ void front_store_bins(const F& front, const float2 (&X)[16], long f0, unsigned nlive, int eN, int nN) {
+    if constexpr (front_bin_sink<F>::value) front.template store<N, ST>(X, f0, nlive, eN, nN);
+}
+
 template <int LOG2N, bool REAL = false>
 __global__ __launch_bounds__(512, 4) void fft_fast_kernel(const float* __restrict__ in, const float* __restrict__ window, const float2* __restrict__ tw,
                                                           FftOutputs out, long n_frames) {

@@ -54,6 +54,13 @@ __global__ __launch_bounds__(256) void pfb_hist_kernel(const float2* __restrict_
     new_hist[j]  = s >= 0 ? x[s] : old_hist[j + n_in];
 }
 
+// (shared with the synthesis bank, ifft.hip, whose history is the last P - 1 transformed frames)
+int pfb_hist_launch(const float2* x, long n_in, const float2* old_hist, float2* new_hist, long len, hipStream_t st) {
+    hipLaunchKernelGGL(pfb_hist_kernel, dim3((unsigned)ceil_div(len, 256L)), dim3(256), 0, st, x, n_in, old_hist, new_hist, len);
+    GR4_LAUNCH_CHECK();
+    return GR4HIP_OK;
+}
+
 int fft_build_plan(size_t N, FftPlanDev* plan);       // fft.hip
 int fft_upload_twiddles(size_t N, DeviceBuffer* buf); // fft.hip
 
@@ -117,9 +124,7 @@ static int pfb_apply_pending(gr4hip_pfb* f, hipStream_t st) {
 static int pfb_carry_history(gr4hip_pfb* f, const void* d_in, size_t n_in, hipStream_t st) {
     const size_t hlen = (f->P - 1) * f->N;
     if (!hlen) return GR4HIP_OK;
-    hipLaunchKernelGGL(pfb_hist_kernel, dim3((unsigned)ceil_div(hlen, (size_t)256)), dim3(256), 0, st, static_cast<const float2*>(d_in), (long)n_in,
-                       static_cast<const float2*>(f->d_hist[f->cur].ptr), static_cast<float2*>(f->d_hist[f->cur ^ 1].ptr), (long)hlen);
-    GR4_LAUNCH_CHECK();
+    if (const int rc = pfb_hist_launch(static_cast<const float2*>(d_in), (long)n_in, static_cast<const float2*>(f->d_hist[f->cur].ptr), static_cast<float2*>(f->d_hist[f->cur ^ 1].ptr), (long)hlen, st)) return rc;
     f->cur ^= 1;
     return GR4HIP_OK;
 }

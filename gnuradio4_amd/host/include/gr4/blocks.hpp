@@ -1418,6 +1418,148 @@ struct PfbChannelizer : Block<PfbChannelizer<T>, Resampling<1024, 1024, false>> 
     }
 };
 
+// ---- inverse transform and polyphase synthesis bank (INVERSE_FFT.md): frames of fftSize complex bins in natural order (what PfbChannelizer emits) -> samples.
+//   InverseFFT<complex<float>>:  x[n] = sum_k X[k] e^{+2 pi i k n / N}, unnormalised like algorithm::FFT's Direction::Backward (algorithm/.../fourier/fft.hpp:260-314)
+//   InverseFFT<float>:           the packed complex-to-real form (fft.hpp:277-283): bins 0 .. N/2 of each frame, the imaginary parts of bins 0 and N/2 ignored
+//   PfbSynthesizer:              v_m = the transform of frame m, y[m N + i] = sum_{k < P} g[k N + i] v_{m - k}[i]  (the project's own definition)
+// Settings: fftSize, window (a synthesis window on the samples; the bank: the prototype's design window), scale (times 1 / fftSize, before the window).
+// Host bodies, the definition written plainly: a float64 transform rounded to float, then float multiplies (scale, window) / std::fmaf sums (k ascending from 0).
+namespace detail {
+// in-place unnormalised inverse DFT (e^{+...}) of a power-of-two frame in float64
+inline void inverse_dft64(std::vector<std::complex<double>>& v) {
+    const std::size_t N = v.size();
+    for (std::size_t i = 0, j = 0; i < N; ++i) {
+        if (i < j) std::swap(v[i], v[j]);
+        std::size_t b = N >> 1;
+        while (b >= 1 && (j & b)) { j ^= b; b >>= 1; }
+        j |= b;
+    }
+    for (std::size_t len = 2; len <= N; len <<= 1)
+        for (std::size_t k = 0; k < N; k += len)
+            for (std::size_t n = 0; n < len / 2; ++n) {
+                const auto w = std::polar(1.0, 2.0 * std::numbers::pi * static_cast<double>(n) / static_cast<double>(len));
+                const auto t = v[k + n + len / 2] * w;
+                v[k + n + len / 2] = v[k + n] - t;
+                v[k + n] += t;
+            }
+}
+inline void check_inverse_size(std::size_t fftSize) {
+    if (fftSize < 2 || (fftSize & (fftSize - 1)) || fftSize > 8192) throw std::invalid_argument("fftSize must be a power of two in [2, 8192]");
+}
+// the float window of gr4hip_window_create (host code of the library); "None" / "Rectangular": empty = no multiply
+inline std::vector<float> synthesis_window(const std::string& window, std::size_t n) {
+    gr::algorithm::window::Type type{};
+    if (!gr_enum_parse(type, std::string_view(window))) throw std::invalid_argument("unknown window '" + window + "'");
+    if (type == gr::algorithm::window::Type::None || type == gr::algorithm::window::Type::Rectangular) return {};
+    std::vector<float> w(n);
+    if (gr4hip_window_create(static_cast<int>(type), w.data(), n, 1.6f) != GR4HIP_OK) throw std::invalid_argument(std::string("window: ") + gr4hip_last_error());
+    return w;
+}
+} // namespace detail
+
+template <typename T>
+    requires(std::is_same_v<T, std::complex<float>> || std::is_same_v<T, float>)
+struct InverseFFT : Block<InverseFFT<T>, Resampling<1024, 1024, false>> {
+    PortIn<std::complex<float>> in;
+    PortOut<T>                  out;
+    Size_t                      fftSize = 1024;
+    std::string                 window  = "None";
+    bool                        scale   = false;
+    GR_MAKE_REFLECTABLE(InverseFFT, in, out, fftSize, window, scale);
+    std::vector<float> _window;
+    std::size_t        _n = 0;
+
+    void settingsChanged(const property_map&, const property_map&) {
+        detail::check_inverse_size(fftSize);
+        _window = detail::synthesis_window(window, fftSize);
+        _n      = fftSize;
+        this->input_chunk_size = this->output_chunk_size = fftSize; // whole frames
+    }
+    work::Status processBulk(std::span<const std::complex<float>> input, std::span<T> output) {
+        if (_n != fftSize) settingsChanged({}, {});
+        const std::size_t                 N = _n;
+        const float                       s = scale ? 1.f / static_cast<float>(N) : 1.f;
+        std::vector<std::complex<double>> v(N);
+        for (std::size_t f = 0; f + N <= input.size(); f += N) {
+            for (std::size_t k = 0; k < N; ++k) v[k] = std::complex<double>(input[f + k]);
+            if constexpr (std::is_same_v<T, float>) { // the Hermitian expansion of bins 0 .. N/2
+                v[0] = v[0].real();
+                v[N / 2] = v[N / 2].real();
+                for (std::size_t k = 1; k < N / 2; ++k) v[N - k] = std::conj(v[k]);
+            }
+            detail::inverse_dft64(v);
+            for (std::size_t n = 0; n < N; ++n) {
+                std::complex<float> y(static_cast<float>(v[n].real()) * s, static_cast<float>(v[n].imag()) * s);
+                if (!_window.empty()) y = std::complex<float>(y.real() * _window[n], y.imag() * _window[n]);
+                if constexpr (std::is_same_v<T, float>) output[f + n] = y.real();
+                else output[f + n] = y;
+            }
+        }
+        return work::Status::OK;
+    }
+};
+
+template <typename T>
+    requires std::is_same_v<T, std::complex<float>>
+struct PfbSynthesizer : Block<PfbSynthesizer<T>, Resampling<1024, 1024, false>> {
+    PortIn<T>          in;
+    PortOut<T>         out;
+    Size_t             fftSize          = 1024;
+    Size_t             taps_per_channel = 4;
+    std::vector<float> taps;
+    std::string        window = "Hamming";
+    bool               scale  = false;
+    GR_MAKE_REFLECTABLE(PfbSynthesizer, in, out, fftSize, taps_per_channel, taps, window, scale);
+    std::vector<float> _g;    // the prototype in use, P N values
+    std::vector<T>     _hist; // the last P - 1 transformed frames, oldest first
+    std::size_t        _N = 0, _P = 0;
+
+    // throws on every bad setting; a change of fftSize or taps_per_channel clears the history, new taps alone keep it
+    void settingsChanged(const property_map&, const property_map&) {
+        detail::check_inverse_size(fftSize);
+        if (taps_per_channel < 1 || taps_per_channel > 32) throw std::invalid_argument("taps_per_channel must be in [1, 32]");
+        if (!taps.empty() && taps.size() != fftSize * taps_per_channel) throw std::invalid_argument("taps: need taps_per_channel * fftSize values (or none: designed)");
+        std::vector<float> next(taps);
+        if (next.empty()) {
+            gr::algorithm::window::Type type{};
+            if (!gr_enum_parse(type, std::string_view(window))) throw std::invalid_argument("unknown window '" + window + "'");
+            next.resize(fftSize * taps_per_channel);
+            if (gr4hip_pfb_design(next.data(), fftSize, taps_per_channel, static_cast<int>(type), 1.6f) != GR4HIP_OK) throw std::invalid_argument(std::string("pfb design: ") + gr4hip_last_error());
+        }
+        _g = std::move(next);
+        if (fftSize != _N || taps_per_channel != _P) _hist.assign((taps_per_channel - 1) * fftSize, T{});
+        _N = fftSize;
+        _P = taps_per_channel;
+        this->input_chunk_size = this->output_chunk_size = fftSize;
+    }
+    void reset() { std::fill(_hist.begin(), _hist.end(), T{}); }
+    work::Status processBulk(std::span<const T> input, std::span<T> output) {
+        if (_N != fftSize) settingsChanged({}, {});
+        const std::size_t                 N = _N, P = _P, M = input.size() / N, H = (P - 1) * N;
+        const float                       s = scale ? 1.f / static_cast<float>(N) : 1.f;
+        std::vector<T>                    v(H + M * N); // the history, then the call's transformed frames
+        std::vector<std::complex<double>> w(N);
+        std::copy(_hist.begin(), _hist.end(), v.begin());
+        for (std::size_t m = 0; m < M; ++m) {
+            for (std::size_t c = 0; c < N; ++c) w[c] = std::complex<double>(input[m * N + c]);
+            detail::inverse_dft64(w);
+            for (std::size_t i = 0; i < N; ++i) v[H + m * N + i] = T(static_cast<float>(w[i].real()) * s, static_cast<float>(w[i].imag()) * s);
+        }
+        for (std::size_t m = 0; m < M; ++m)
+            for (std::size_t i = 0; i < N; ++i) {
+                float re = 0.f, im = 0.f;
+                for (std::size_t k = 0; k < P; ++k) {
+                    const T& q = v[H + m * N + i - k * N]; // frame m - k
+                    re = std::fmaf(_g[k * N + i], q.real(), re);
+                    im = std::fmaf(_g[k * N + i], q.imag(), im);
+                }
+                output[m * N + i] = T(re, im);
+            }
+        _hist.assign(v.end() - static_cast<std::ptrdiff_t>(H), v.end());
+        return work::Status::OK;
+    }
+};
+
 // ---- spectrum integrator behind a power spectrum (SPECTRUM_INTEGRATOR.md -- the reference has no such block, the definition is the project's): the sum (mean:
 // the mean) of n_integrate consecutive frames of vector_size values, one frame out per n_integrate frames in.  One fixed order of additions, on the host as on
 // the device: float32 sums over leaves of gr4hip_specint_leaf() = 32 frames counted from the integration's start, the leaves into a float64 sum in ascending

@@ -369,6 +369,47 @@ struct PfbStage final : Stage {
     }
 };
 
+// inverse transform (gr4hip_ifft_*): whole frames of N complex bins in, N complex (ifft_c32) or real (ifft_f32) samples out
+struct InverseFftStage final : Stage {
+    gr4hip_ifft_t* h = nullptr;
+    std::size_t    N;
+    int            window;
+    bool           real_out, scale;
+    InverseFftStage(std::size_t fftSize, int window_, bool realOut, bool scale_) : N(fftSize), window(window_), real_out(realOut), scale(scale_) {
+        in_bytes = 8; out_bytes = real_out ? 4 : 8; in_chunk = out_chunk = fftSize;
+        check(gr4hip_ifft_create(&h, real_out ? GR4HIP_F32 : GR4HIP_C32, N, window, scale ? GR4HIP_IFFT_SCALE : 0), "gr4hip_ifft_create");
+    }
+    ~InverseFftStage() override { gr4hip_ifft_destroy(h); }
+    std::string_view kind() const override { return real_out ? "ifft_f32" : "ifft_c32"; }
+    int enqueue(const void* in, std::size_t n, void* out, std::size_t* n_out, gr4hip_stream_t s) override {
+        *n_out = (n / N) * N;
+        return gr4hip_ifft_process(h, in, n / N, out, s);
+    }
+};
+
+// polyphase synthesis bank (gr4hip_pfb_synth_*): whole frames of N channel values in, N samples out
+struct PfbSynthStage final : Stage {
+    gr4hip_pfb_synth_t* h = nullptr;
+    std::size_t         N, P;
+    bool                scale;
+    std::vector<float>  taps;
+    PfbSynthStage(std::size_t fftSize, std::size_t tapsPerChannel, const std::vector<float>& prototype, bool scale_) : N(fftSize), P(tapsPerChannel), scale(scale_), taps(prototype) {
+        in_bytes = out_bytes = 8; in_chunk = out_chunk = fftSize;
+        if (taps.size() != N * P) throw std::invalid_argument("pfb_synth: need taps_per_channel * fftSize taps");
+        check(gr4hip_pfb_synth_create(&h, N, P, taps.data(), scale ? GR4HIP_IFFT_SCALE : 0), "gr4hip_pfb_synth_create");
+    }
+    ~PfbSynthStage() override { gr4hip_pfb_synth_destroy(h); }
+    void set_taps(const std::vector<float>& prototype) {
+        taps = prototype;
+        check(gr4hip_pfb_synth_set_taps(h, taps.data(), taps.size()), "gr4hip_pfb_synth_set_taps"); // (the history is kept)
+    }
+    std::string_view kind() const override { return "pfb_synth_c32"; }
+    int enqueue(const void* in, std::size_t n, void* out, std::size_t* n_out, gr4hip_stream_t s) override {
+        *n_out = (n / N) * N;
+        return gr4hip_pfb_synth_process(h, in, n / N, out, s);
+    }
+};
+
 // spectrum integrator (gr4hip_specint_*): whole integrations of A frames of N values in, one frame out each.  `front` set: the stage is the fusion of a
 // PowerSpectrum or PfbPowerSpectrum stage with the integrator behind it -- complex samples in, the transform's |X|^2 summed in its own launch
 // (gr4hip_fft_mag2_integrate / gr4hip_pfb_power_integrate: the values of the two stages in a row, bit for bit)
@@ -950,6 +991,30 @@ struct PfbKernel {
 };
 template <> struct Kernel<gr::blocks::fft::PfbPowerSpectrum<std::complex<float>>> : PfbKernel<gr::blocks::fft::PfbPowerSpectrum<std::complex<float>>, true> {};
 template <> struct Kernel<gr::blocks::fft::PfbChannelizer<std::complex<float>>> : PfbKernel<gr::blocks::fft::PfbChannelizer<std::complex<float>>, false> {};
+// the inverse transform: every setting is part of the handle, so a change makes a new stage (nothing is carried)
+template <typename T>
+struct Kernel<gr::blocks::fft::InverseFFT<T>> {
+    using B = gr::blocks::fft::InverseFFT<T>;
+    static std::unique_ptr<Stage> make_stage(B& b) { return std::make_unique<InverseFftStage>(b.fftSize, window_id(b.window), std::is_same_v<T, float>, b.scale); }
+    static work::Status           work(B& b, std::size_t nIn, std::size_t nOut) { return offload_work(b, nIn, nOut, make_stage); }
+};
+// the synthesis bank: new taps keep the stage (and its history), another fftSize, taps_per_channel or scale makes a new one (history cleared, like the host body)
+template <>
+struct Kernel<gr::blocks::fft::PfbSynthesizer<std::complex<float>>> {
+    using B = gr::blocks::fft::PfbSynthesizer<std::complex<float>>;
+    static std::unique_ptr<Stage> make_stage(B& b) {
+        if (b._N != b.fftSize) b.settingsChanged({}, {});
+        return std::make_unique<PfbSynthStage>(b._N, b._P, b._g, b.scale);
+    }
+    static work::Status work(B& b, std::size_t nIn, std::size_t nOut) {
+        return offload_work(b, nIn, nOut, make_stage, [](Stage& st, B& blk) {
+            auto& p = static_cast<PfbSynthStage&>(st);
+            if (p.N != blk._N || p.P != blk._P || p.scale != blk.scale) return false;
+            p.set_taps(blk._g);
+            return true;
+        });
+    }
+};
 template <>
 struct Kernel<gr::blocks::fft::SpectrumIntegrator<float>> {
     using B = gr::blocks::fft::SpectrumIntegrator<float>;

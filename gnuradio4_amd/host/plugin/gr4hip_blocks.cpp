@@ -127,6 +127,9 @@ const bool registered = [] {
     r.insert<gr::blocks::fft::PowerSpectrum<std::complex<float>>>(named<std::complex<float>>("gr::blocks::fft::PowerSpectrum"));
     r.insert<gr::blocks::fft::PfbPowerSpectrum<std::complex<float>>>(named<std::complex<float>>("gr::blocks::fft::PfbPowerSpectrum")); // polyphase filter bank (PFB.md; no reference block)
     r.insert<gr::blocks::fft::PfbChannelizer<std::complex<float>>>(named<std::complex<float>>("gr::blocks::fft::PfbChannelizer"));
+    r.insert<gr::blocks::fft::InverseFFT<std::complex<float>>>(named<std::complex<float>>("gr::blocks::fft::InverseFFT")); // inverse transform and synthesis bank (INVERSE_FFT.md)
+    r.insert<gr::blocks::fft::InverseFFT<float>>(named<float>("gr::blocks::fft::InverseFFT"));
+    r.insert<gr::blocks::fft::PfbSynthesizer<std::complex<float>>>(named<std::complex<float>>("gr::blocks::fft::PfbSynthesizer"));
     r.insert<gr::blocks::fft::SpectrumIntegrator<float>>(named<float>("gr::blocks::fft::SpectrumIntegrator")); // SPECTRUM_INTEGRATOR.md; no reference block
     r.insert<gr::blocks::fft::CrossSpectrum<float>>(named<float>("gr::blocks::fft::CrossSpectrum")); // CROSS_SPECTRUM.md; no reference block
     r.insert<gr::hip::OnDevice<fir_filter<float>>>(named<float>("gr::hip::OnDevice<gr::filter::fir_filter", ">"));

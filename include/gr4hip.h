@@ -413,6 +413,41 @@ int gr4hip_pfb_reset(gr4hip_pfb_t* pfb);
 int gr4hip_pfb_process(gr4hip_pfb_t* pfb, const void* d_in, size_t n_frames, float* d_spectrum, float* d_mag2, gr4hip_stream_t stream);
 int gr4hip_pfb_destroy(gr4hip_pfb_t* pfb);
 
+/* Inverse transform and polyphase synthesis bank (INVERSE_FFT.md): from frames of N complex bins in natural order (what gr4hip_fft_spectrum and
+ * gr4hip_pfb_process(d_spectrum) write) back to samples.  N a size of gr4hip_fft_plan kind 0 (a power of two, 2 <= N <= 8192).
+ *   C2C (out_dtype C32):  x[n] = sum_{k < N} X[k] e^{+2 pi i k n / N}                                                            [frames][N] complex out
+ *   C2R (out_dtype F32):  x[n] = Re X[0] + (-1)^n Re X[N/2] + 2 sum_{k = 1}^{N/2 - 1} Re( X[k] e^{+2 pi i k n / N} )             [frames][N] float out
+ * Unnormalised, like the reference's Direction::Backward (algorithm/.../fourier/fft.hpp:260-314); GR4HIP_IFFT_SCALE multiplies every output by 1 / N, once, as
+ * the last operation of the transform (exact for these N, barring underflow).  C2R reads full N-bin frames and uses bins 0 .. N/2 only: the imaginary parts of
+ * bins 0 and N/2 and every bin above N/2 are ignored, as trySimdFFT_C2R packs them (fft.hpp:277-283).  window (ids as in gr4hip_fft_create; NONE: no multiply):
+ * x[n] times gr4hip_window_create(window, ., N, 1.6)[n] after the scale, one float multiply per component.  Non-finite values propagate as float arithmetic
+ * gives them; there is no guard.  The values are conj(forward transform(conj X)) of the FFT block's kernels, bit for bit.  Oracles (tests/synthesis_oracle.py):
+ * N numpy.fft.ifft, and N numpy.fft.irfft of bins 0 .. N/2 with the two imaginary parts zeroed.
+ *
+ * Synthesis bank (the project's own definition, as the analysis bank's is): N channels, P taps per channel, prototype g[0 .. P N) (real), frames of spectra Y_m,
+ *   v_m[i]    = sum_{c < N} Y_m[c] e^{+2 pi i i c / N}          (the C2C transform above; v_m = 0 for m < 0, or the carried history)
+ *   y[m N + i] = sum_{k < P} g[k N + i] v_{m - k}[i]            (float32, from y = 0, k ascending, one fma per term and component)
+ * N values in, N samples out per frame; the last P - 1 frames of v (float32, after the transform and its optional 1 / N) are carried in the handle, so the
+ * values do not depend on how the frame stream is cut into calls.  With P = 1 and g = a window the outputs are those of gr4hip_ifft_process with that window.
+ * With g = h the bank is the adjoint of gr4hip_pfb_process with prototype h, delayed by P - 1 frames; it is NOT a reconstruction of the analysis bank's input
+ * (INVERSE_FFT.md).  h_taps NULL: gr4hip_pfb_design(N, P, Hamming).  gr4hip_pfb_synth_set_taps keeps the history; it and gr4hip_pfb_synth_reset (history back to
+ * zeros) are stream-ordered (LIFECYCLE CALLS above).  A non-finite value in Y_m reaches every sample of output frames m .. m + P - 1 and nothing else.
+ * GR4HIP_INVALID_ARGUMENT before any device work, outputs untouched: a NULL handle, input or output, fft_size / n_channels < 2, 0 taps per channel, a non-finite
+ * tap, count != P N, unknown flags, window or out_dtype, a complex buffer not aligned to 8 bytes (a real output: 4), an output overlapping the input, more than
+ * 2^40 values in one call (below 256 points: more than 2^31 - 1 workgroups of 64 / max(1, N / 8) frames).  GR4HIP_UNSUPPORTED: sizes of gr4hip_fft_plan kinds
+ * 1, 2 and 3, more than 32 taps per channel.  n_frames == 0 is a no-op. */
+#define GR4HIP_IFFT_SCALE 1
+typedef struct gr4hip_ifft      gr4hip_ifft_t;
+typedef struct gr4hip_pfb_synth gr4hip_pfb_synth_t;
+int gr4hip_ifft_create(gr4hip_ifft_t** ifft, int out_dtype /* GR4HIP_C32 | GR4HIP_F32 */, size_t fft_size, int window, int flags);
+int gr4hip_ifft_process(gr4hip_ifft_t* ifft, const void* d_spectra, size_t n_frames, void* d_out, gr4hip_stream_t stream);
+int gr4hip_ifft_destroy(gr4hip_ifft_t* ifft);
+int gr4hip_pfb_synth_create(gr4hip_pfb_synth_t** bank, size_t n_channels, size_t taps_per_channel, const float* h_taps /* P N values, or NULL */, int flags /* 0 | GR4HIP_IFFT_SCALE */);
+int gr4hip_pfb_synth_set_taps(gr4hip_pfb_synth_t* bank, const float* h_taps, size_t count);
+int gr4hip_pfb_synth_reset(gr4hip_pfb_synth_t* bank);
+int gr4hip_pfb_synth_process(gr4hip_pfb_synth_t* bank, const void* d_spectra, size_t n_frames, void* d_out, gr4hip_stream_t stream);
+int gr4hip_pfb_synth_destroy(gr4hip_pfb_synth_t* bank);
+
 /* Spectrum integrator behind the |X|^2 outputs above: the sum (or mean) of A consecutive power spectra, one spectrum out per A frames in
  * (SPECTRUM_INTEGRATOR.md).  The reference has no such block: the definition is the project's, tests/spectrum_integrator_oracle.py pins it.  Frames m[f][c],
  * c < n_bins, float; output q covers frames [q A, (q + 1) A); leaf l of it covers frames q A + [l B, min((l + 1) B, A)), B = gr4hip_specint_leaf() = 32:
