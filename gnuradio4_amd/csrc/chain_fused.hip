@@ -153,13 +153,13 @@ __device__ __forceinline__ int addrA(int row, int col) { return row * kRowA + co
 
 // pass B (p = 32, radix 16): butterfly (c, k) gathers S1[k][c + 16 r], twiddles by W_512^{r k}, scatters to S2[c][32 q + k]
 __device__ __forceinline__ void passB_compute_store(float2* S, float2 (&w)[16], const float2 (&tw)[16], int c, int k) {
-    fft16_tw<1>(w, tw);
+    fft16_tw_fold<1>(w, tw);
 #pragma unroll
     for (int q = 0; q < 16; ++q) S[c * kRowB + 32 * q + k] = w[perm16(q)];
 }
 // same, twiddles from an LDS table [16][32] (the windowed kernel has no registers left for a resident set)
 __device__ __forceinline__ void passB_table_store(float2* S, float2 (&w)[16], const float2* twl, int c, int k) {
-    fft16_tw<1>(w, [&](int r) { return twl[r * 32 + k]; });
+    fft16_tw_fold<1>(w, [&](int r) { return twl[r * 32 + k]; });
 #pragma unroll
     for (int q = 0; q < 16; ++q) S[c * kRowB + 32 * q + k] = w[perm16(q)];
 }
@@ -167,7 +167,7 @@ __device__ __forceinline__ void passB_table_store(float2* S, float2 (&w)[16], co
 __device__ __forceinline__ void passC(const float2* S, float2 (&g)[16], const float2 (&tw)[16], int i3) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) g[r] = S[r * kRowB + i3];
-    fft16_tw<1>(g, tw);
+    fft16_tw_fold<1>(g, tw);
 }
 
 // phase fence: keeps hipcc's scheduler from overlapping independent phases (which costs more registers than the 128 a lane has
@@ -270,7 +270,7 @@ __device__ __forceinline__ void passA_inplace(float2* S, const float2 (&twA)[16]
     float2 v[16];
 #pragma unroll
     for (int m = 0; m < 16; ++m) v[m] = S[addrA(2 * m + par, n0)];
-    fft16<1>(v);
+    fft16_fold<1>(v);
 #pragma unroll
     for (int k1 = 0; k1 < 16; ++k1) {
         const float2 u = k1 == 0 ? v[perm16(k1)] : cmul(v[perm16(k1)], twA[k1]); // twA: W_32^k1 on the odd lane, 1 on the even lane
@@ -604,7 +604,7 @@ __device__ __forceinline__ void chain_fd_body(ChainFdArgs& a, const ChainFdMulti
                     }
                 }
             }
-            fft16<1>(v); // even lanes: E16[k1], odd lanes: O16[k1], at slot perm16(k1)
+            fft16_fold<1>(v); // even lanes: E16[k1], odd lanes: O16[k1], at slot perm16(k1)
             GR4_DRAIN(1);
 #pragma unroll
             for (int k1 = 0; k1 < 16; ++k1) {
@@ -684,7 +684,8 @@ __device__ __forceinline__ void chain_fd_body(ChainFdArgs& a, const ChainFdMulti
         }                                                                                   \
     } while (0)
             // ---- X pass B: twiddles W_512^{r k}, 16-point DFT, scatter to S2[c][32 q + k]
-            // (the twiddles ride in the first butterflies, fft16_tw: slot 0 the three plain products, then two slots per butterfly)
+            // (the twiddles ride in the first butterflies, fft16_tw: slot 0 the three plain products, then two slots per first-step butterfly, one for the plain
+            // second-step butterfly k1 = 0 and two for each of the others)
             auto twB = [&](int r) { return WIN ? twBl[r * 32 + kb] : twBr[r]; };
             GR4_MF(0);
             fft16_tw_pre<1>(w, twB);
@@ -696,15 +697,14 @@ __device__ __forceinline__ void chain_fd_body(ChainFdArgs& a, const ChainFdMulti
                 fft16_tw_s1b<1>(w, twB, n2);
             }
             GR4_MF(9);
-            fft16_twa<1>(w);
-            GR4_MF(10);
-            fft16_twb<1>(w);
+            fft16_s2_fold<1>(w, 0);
 #pragma unroll
-            for (int k1 = 0; k1 < 4; ++k1) {
-                GR4_MF(11 + k1);
-                fft16_s2<1>(w, k1);
+            for (int k1 = 1; k1 < 4; ++k1) { // (the internal W_16 twiddles ride in these butterflies: two slots each)
+                GR4_MF(8 + 2 * k1);
+                fft16_s2a<1>(w, k1);
+                GR4_MF(9 + 2 * k1);
+                fft16_s2b<1>(w, k1);
             }
-            GR4_MF(15);
 #pragma unroll
             for (int q = 0; q < 16; ++q) S[cb * kRowB + 32 * q + kb] = w[perm16(q)];
 #undef GR4_MF

@@ -14,20 +14,20 @@ __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
     return make_float2(r[0], r[1]);
 }
 #else
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(fmaf(a.x, b.x, -a.y * b.y), fmaf(a.x, b.y, a.y * b.x)); }
+__host__ __device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(fmaf(a.x, b.x, -a.y * b.y), fmaf(a.x, b.y, a.y * b.x)); }
 #endif
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 mulmi(float2 a) { return make_float2(a.y, -a.x); }
+__host__ __device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
+__host__ __device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
+__host__ __device__ __forceinline__ float2 mulmi(float2 a) { return make_float2(a.y, -a.x); }
 
-__device__ __forceinline__ void bfly4(float2& v0, float2& v1, float2& v2, float2& v3) {
+__host__ __device__ __forceinline__ void bfly4(float2& v0, float2& v1, float2& v2, float2& v3) {
     const float2 t0 = cadd(v0, v2), t1 = csub(v0, v2), t2 = cadd(v1, v3), t3 = mulmi(csub(v1, v3));
     v0 = cadd(t0, t2); v2 = csub(t0, t2); v1 = cadd(t1, t3); v3 = csub(t1, t3);
 }
 
 // multiply by W_16^m with compile-time m
 template <int M>
-__device__ __forceinline__ float2 mul_w16(float2 a) {
+__host__ __device__ __forceinline__ float2 mul_w16(float2 a) {
     constexpr float c1 = 0.92387953251128675613f, s1 = 0.38268343236508977173f, h = 0.70710678118654752440f;
     if constexpr (M == 0) return a;
     else if constexpr (M == 1) return make_float2(fmaf(a.y, s1, a.x * c1), fmaf(-a.x, s1, a.y * c1));  // (c1 - i s1)
@@ -42,9 +42,9 @@ __host__ __device__ constexpr int perm16(int m) { return 4 * (m & 3) + (m >> 2);
 
 // the three steps of fft16, callable one quarter at a time (the fused pass B interleaves them with MFMA issues)
 template <int ST>
-__device__ __forceinline__ void fft16_s1(float2* v, int n2) { bfly4(v[(n2)*ST], v[(n2 + 4) * ST], v[(n2 + 8) * ST], v[(n2 + 12) * ST]); }
+__host__ __device__ __forceinline__ void fft16_s1(float2* v, int n2) { bfly4(v[(n2)*ST], v[(n2 + 4) * ST], v[(n2 + 8) * ST], v[(n2 + 12) * ST]); }
 template <int ST>
-__device__ __forceinline__ void fft16_twa(float2* v) { // a[n2][k1] is at slot n2 + 4 k1; twiddle W_16^{n2 k1}
+__host__ __device__ __forceinline__ void fft16_twa(float2* v) { // a[n2][k1] is at slot n2 + 4 k1; twiddle W_16^{n2 k1}
     v[5 * ST]  = mul_w16<1>(v[5 * ST]);   // n2=1,k1=1
     v[9 * ST]  = mul_w16<2>(v[9 * ST]);   // n2=1,k1=2
     v[13 * ST] = mul_w16<3>(v[13 * ST]);  // n2=1,k1=3
@@ -52,7 +52,7 @@ __device__ __forceinline__ void fft16_twa(float2* v) { // a[n2][k1] is at slot n
     v[10 * ST] = mul_w16<4>(v[10 * ST]);  // n2=2,k1=2
 }
 template <int ST>
-__device__ __forceinline__ void fft16_twb(float2* v) {
+__host__ __device__ __forceinline__ void fft16_twb(float2* v) {
     v[14 * ST] = mul_w16<6>(v[14 * ST]);  // n2=2,k1=3
     v[7 * ST]  = mul_w16<3>(v[7 * ST]);   // n2=3,k1=1
     v[11 * ST] = mul_w16<6>(v[11 * ST]);  // n2=3,k1=2
@@ -63,10 +63,10 @@ __device__ __forceinline__ void fft16_twb(float2* v) {
     }
 }
 template <int ST>
-__device__ __forceinline__ void fft16_s2(float2* v, int k1) { bfly4(v[(4 * k1) * ST], v[(4 * k1 + 1) * ST], v[(4 * k1 + 2) * ST], v[(4 * k1 + 3) * ST]); }
+__host__ __device__ __forceinline__ void fft16_s2(float2* v, int k1) { bfly4(v[(4 * k1) * ST], v[(4 * k1 + 1) * ST], v[(4 * k1 + 2) * ST], v[(4 * k1 + 3) * ST]); }
 
 template <int ST>
-__device__ __forceinline__ void fft16(float2* v) {
+__host__ __device__ __forceinline__ void fft16(float2* v) {
 #pragma unroll
     for (int n2 = 0; n2 < 4; ++n2) fft16_s1<ST>(v, n2);
     fft16_twa<ST>(v);
@@ -75,33 +75,125 @@ __device__ __forceinline__ void fft16(float2* v) {
     for (int k1 = 0; k1 < 4; ++k1) fft16_s2<ST>(v, k1);
 }
 
+// The second step with its internal twiddles folded in (fft16_fold, fft16_tw_fold: the fused chain's transforms; the FFT block's kernels keep the plain step above, whose
+// roundings their parity tests at 2^18 points sit within an ulp of).  For k1 the butterfly of a[n2][k1] W_16^{n2 k1}, a[n2][k1] at slot n2 + 4 k1: the twiddles ride in
+// the butterfly's own sums instead of being multiplied out in front of a plain bfly4 (91 instructions for the step as hipcc contracts it; 80 here):
+//   pair (v0, W^{2 k1} v2), W^2 = h (1 - i), W^6 = -h (1 + i): the sum and difference of v2's components, h in the fmas that form t0 and t1 (W^4 = -i: free)
+//   pair (W^{k1} v1, W^{3 k1} v3), k1 = 1, 3: W^1 = c1 (1 - i t), W^3 = c1 (t - i), W^9 = c1 (-1 + i t), t = tan(pi / 8): u = W^{k1} v1 / c1 is one fma per component,
+//     A = u + W^{3 k1} v3 / c1 one fma and one sum, B = 2 u - A one fma (one more rounding: eps |A| instead of eps |B|), c1 in the fmas of the four output sums
+//   k1 = 2: W^2 v1 +- W^6 v3 = h x (sums of the components of v1 - v3 and v1 + v3), h in the fmas of the four output sums
+// Two halves per k1, so that the fused pass B can put an MFMA issue between them (8 + 14, 8 + 12, 8 + 14 instructions; k1 = 0: the plain bfly4 in the second half):
+//   fft16_s2a(k1): t0, t1 in slots 4 k1, 4 k1 + 2 and u in slot 4 k1 + 1 (k1 = 2: v1 - v3, v1 + v3 in slots 4 k1 + 1, 4 k1 + 3);   fft16_s2b(k1): the rest
+__host__ __device__ __forceinline__ float2 twice_minus(float2 a, float2 s) { return make_float2(fmaf(2.0f, a.x, -s.x), fmaf(2.0f, a.y, -s.y)); } // 2 a - s
+template <int ST, int K1>
+__host__ __device__ __forceinline__ void fft16_s2a_k(float2* v) {
+    constexpr float h = 0.70710678118654752440f, t = 0.41421356237309504880f;
+    float2 &v0 = v[(4 * K1) * ST], &v1 = v[(4 * K1 + 1) * ST], &v2 = v[(4 * K1 + 2) * ST], &v3 = v[(4 * K1 + 3) * ST];
+    const float2 a = v0, b = v2, c = v1;
+    if constexpr (K1 == 1) {        // + h (s, d)
+        const float s = b.x + b.y, d = b.y - b.x;
+        v0 = make_float2(fmaf(s, h, a.x), fmaf(d, h, a.y));
+        v2 = make_float2(fmaf(-s, h, a.x), fmaf(-d, h, a.y));
+        v1 = make_float2(fmaf(t, c.y, c.x), fmaf(-t, c.x, c.y));
+    } else if constexpr (K1 == 2) { // + (-i) v2
+        const float2 e = v3;
+        v0 = make_float2(a.x + b.y, a.y - b.x);
+        v2 = make_float2(a.x - b.y, a.y + b.x);
+        v1 = csub(c, e);
+        v3 = cadd(c, e);
+    } else if constexpr (K1 == 3) { // + h (d, -s)
+        const float s = b.x + b.y, d = b.y - b.x;
+        v0 = make_float2(fmaf(d, h, a.x), fmaf(-s, h, a.y));
+        v2 = make_float2(fmaf(-d, h, a.x), fmaf(s, h, a.y));
+        v1 = make_float2(fmaf(t, c.x, c.y), fmaf(t, c.y, -c.x));
+    }
+}
+template <int ST, int K1>
+__host__ __device__ __forceinline__ void fft16_s2b_k(float2* v) {
+    constexpr float c1 = 0.92387953251128675613f, h = 0.70710678118654752440f, t = 0.41421356237309504880f;
+    float2 &v0 = v[(4 * K1) * ST], &v1 = v[(4 * K1 + 1) * ST], &v2 = v[(4 * K1 + 2) * ST], &v3 = v[(4 * K1 + 3) * ST];
+    if constexpr (K1 == 0) bfly4(v0, v1, v2, v3);
+    else {
+        constexpr float g = K1 == 2 ? h : c1; // t2 = g A, t3 = -i g B
+        const float2 t0 = v0, t1 = v2;
+        float2       A, B;
+        if constexpr (K1 == 1) {
+            const float2 u = v1, e = v3;
+            A = make_float2(fmaf(t, e.x, u.x) + e.y, fmaf(t, e.y, u.y) - e.x);
+            B = twice_minus(u, A);
+        } else if constexpr (K1 == 2) {
+            const float2 P = v1, Q = v3;
+            A = make_float2(P.x + Q.y, P.y - Q.x);
+            B = make_float2(Q.x + P.y, Q.y - P.x);
+        } else {
+            const float2 u = v1, e = v3;
+            A = make_float2(fmaf(-t, e.y, u.x) - e.x, fmaf(t, e.x, u.y) - e.y);
+            B = twice_minus(u, A);
+        }
+        v0 = make_float2(fmaf(A.x, g, t0.x), fmaf(A.y, g, t0.y));
+        v2 = make_float2(fmaf(-A.x, g, t0.x), fmaf(-A.y, g, t0.y));
+        v1 = make_float2(fmaf(B.y, g, t1.x), fmaf(-B.x, g, t1.y));
+        v3 = make_float2(fmaf(-B.y, g, t1.x), fmaf(B.x, g, t1.y));
+    }
+}
+template <int ST>
+__host__ __device__ __forceinline__ void fft16_s2a(float2* v, int k1) { // (k1 is a literal or the counter of an unrolled loop: the switch folds)
+    switch (k1) {
+    case 1: fft16_s2a_k<ST, 1>(v); break;
+    case 2: fft16_s2a_k<ST, 2>(v); break;
+    case 3: fft16_s2a_k<ST, 3>(v); break;
+    default: break;
+    }
+}
+template <int ST>
+__host__ __device__ __forceinline__ void fft16_s2b(float2* v, int k1) {
+    switch (k1) {
+    case 0: fft16_s2b_k<ST, 0>(v); break;
+    case 1: fft16_s2b_k<ST, 1>(v); break;
+    case 2: fft16_s2b_k<ST, 2>(v); break;
+    default: fft16_s2b_k<ST, 3>(v); break;
+    }
+}
+template <int ST>
+__host__ __device__ __forceinline__ void fft16_s2_fold(float2* v, int k1) {
+    fft16_s2a<ST>(v, k1);
+    fft16_s2b<ST>(v, k1);
+}
+
+template <int ST>
+__host__ __device__ __forceinline__ void fft16_fold(float2* v) {
+#pragma unroll
+    for (int n2 = 0; n2 < 4; ++n2) fft16_s1<ST>(v, n2);
+#pragma unroll
+    for (int k1 = 0; k1 < 4; ++k1) fft16_s2_fold<ST>(v, k1);
+}
+
 // fft16 behind a twiddle layer: the 16-point DFT of tw(r) v[r ST] (r = 1 .. 15, slot 0 untwiddled) from the UNtwiddled values.  A first-step butterfly needs the sum and
 // the difference of a twiddled pair, a' +- w b: the product then the two sums are 4 + 4 instructions; s = a' + w b as two fma chains and d = 2 a' - s are 4 + 2 (one more
 // rounding in d: eps |s| instead of eps |d|).  Both pairs of each of the four first-step butterflies: 16 instructions fewer per transform.  tw(r) is called once per r,
 // where the product is formed (a register array or a table read).  The steps, callable in pieces like fft16's (the fused pass B interleaves them with MFMA issues):
-//   fft16_tw_pre, then fft16_tw_s1a(n2), fft16_tw_s1b(n2) for n2 = 0 .. 3, then fft16_twa, fft16_twb, fft16_s2(k1) as in fft16
-__device__ __forceinline__ float2 cmuladd(float2 b, float2 w, float2 a) { return make_float2(fmaf(b.x, w.x, fmaf(-b.y, w.y, a.x)), fmaf(b.x, w.y, fmaf(b.y, w.x, a.y))); } // a + w b
-__device__ __forceinline__ float2 twice_minus(float2 a, float2 s) { return make_float2(fmaf(2.0f, a.x, -s.x), fmaf(2.0f, a.y, -s.y)); }                                   // 2 a - s
+//   fft16_tw_pre, then fft16_tw_s1a(n2), fft16_tw_s1b(n2) for n2 = 0 .. 3, then fft16_twa, fft16_twb, fft16_s2(k1) as in fft16 -- or the folded second step's halves fft16_s2a(k1), fft16_s2b(k1)
+__host__ __device__ __forceinline__ float2 cmuladd(float2 b, float2 w, float2 a) { return make_float2(fmaf(b.x, w.x, fmaf(-b.y, w.y, a.x)), fmaf(b.x, w.y, fmaf(b.y, w.x, a.y))); } // a + w b
 template <int ST, typename TW>
-__device__ __forceinline__ void fft16_tw_pre(float2* v, TW&& tw) { // the `a` of the pairs (n2, n2 + 8), n2 = 1 .. 3
+__host__ __device__ __forceinline__ void fft16_tw_pre(float2* v, TW&& tw) { // the `a` of the pairs (n2, n2 + 8), n2 = 1 .. 3
 #pragma unroll
     for (int r = 1; r < 4; ++r) v[r * ST] = cmul(v[r * ST], tw(r));
 }
 template <int ST, typename TW>
-__device__ __forceinline__ void fft16_tw_s1a(float2* v, TW&& tw, int n2) { // pair (n2, n2 + 8) -> t0, t1 of bfly4 in place; slot n2 + 4 twiddled
+__host__ __device__ __forceinline__ void fft16_tw_s1a(float2* v, TW&& tw, int n2) { // pair (n2, n2 + 8) -> t0, t1 of bfly4 in place; slot n2 + 4 twiddled
     const float2 a = v[n2 * ST], s = cmuladd(v[(n2 + 8) * ST], tw(n2 + 8), a);
     v[n2 * ST]       = s;
     v[(n2 + 8) * ST] = twice_minus(a, s);
     v[(n2 + 4) * ST] = cmul(v[(n2 + 4) * ST], tw(n2 + 4));
 }
 template <int ST, typename TW>
-__device__ __forceinline__ void fft16_tw_s1b(float2* v, TW&& tw, int n2) { // pair (n2 + 4, n2 + 12) -> t2, t3, then the second half of bfly4
+__host__ __device__ __forceinline__ void fft16_tw_s1b(float2* v, TW&& tw, int n2) { // pair (n2 + 4, n2 + 12) -> t2, t3, then the second half of bfly4
     const float2 t0 = v[n2 * ST], t1 = v[(n2 + 8) * ST], c = v[(n2 + 4) * ST];
     const float2 t2 = cmuladd(v[(n2 + 12) * ST], tw(n2 + 12), c), t3 = mulmi(twice_minus(c, t2));
     v[n2 * ST] = cadd(t0, t2); v[(n2 + 8) * ST] = csub(t0, t2); v[(n2 + 4) * ST] = cadd(t1, t3); v[(n2 + 12) * ST] = csub(t1, t3);
 }
 template <int ST, typename TW>
-__device__ __forceinline__ void fft16_tw(float2* v, TW&& tw) {
+__host__ __device__ __forceinline__ void fft16_tw(float2* v, TW&& tw) {
     fft16_tw_pre<ST>(v, tw);
 #pragma unroll
     for (int n2 = 0; n2 < 4; ++n2) {
@@ -114,7 +206,20 @@ __device__ __forceinline__ void fft16_tw(float2* v, TW&& tw) {
     for (int k1 = 0; k1 < 4; ++k1) fft16_s2<ST>(v, k1);
 }
 template <int ST>
-__device__ __forceinline__ void fft16_tw(float2* v, const float2 (&tw)[16]) { fft16_tw<ST>(v, [&](int r) { return tw[r]; }); }
+__host__ __device__ __forceinline__ void fft16_tw(float2* v, const float2 (&tw)[16]) { fft16_tw<ST>(v, [&](int r) { return tw[r]; }); }
+template <int ST, typename TW>
+__host__ __device__ __forceinline__ void fft16_tw_fold(float2* v, TW&& tw) { // fft16_tw with the folded second step
+    fft16_tw_pre<ST>(v, tw);
+#pragma unroll
+    for (int n2 = 0; n2 < 4; ++n2) {
+        fft16_tw_s1a<ST>(v, tw, n2);
+        fft16_tw_s1b<ST>(v, tw, n2);
+    }
+#pragma unroll
+    for (int k1 = 0; k1 < 4; ++k1) fft16_s2_fold<ST>(v, k1);
+}
+template <int ST>
+__host__ __device__ __forceinline__ void fft16_tw_fold(float2* v, const float2 (&tw)[16]) { fft16_tw_fold<ST>(v, [&](int r) { return tw[r]; }); }
 
 // multiply v[r] by b^r (r = 1..15) given the table values b^1 and b^2
 __device__ __forceinline__ void apply_powers(float2 (&v)[16], float2 b1, float2 b2) {
