@@ -706,6 +706,81 @@ class CrossSpectrum(_Handle):
         return msc, h1
 
 
+class Beamformer(_Handle):
+    """The per-bin weighted sum of n_streams (1 .. 32) streams of complex spectra of n_bins values into n_beams (1 .. 32) beams, Y_b[f][c] = sum_s W[b][s][c]
+    X_s[f][c] -- the project's own definition, BEAMFORMER.md: per beam, frame and bin one float32 fma chain over the streams in ascending order.  The handle
+    holds the weights and nothing else; the state of an integration lives in the SpectrumIntegrator passed to power_integrated."""
+    _destroy = "gr4hip_beamform_destroy"
+
+    def __init__(self, n_streams: int, n_beams: int, n_bins: int):
+        super().__init__()
+        self.n_streams, self.n_beams, self.n_bins = int(n_streams), int(n_beams), int(n_bins)
+        self._weights = None
+        check(lib().gr4hip_beamform_create(C.byref(self._h), self.n_streams, self.n_beams, self.n_bins), "Beamformer")
+
+    @staticmethod
+    def delay_weights(delays_s, bin_freqs_hz, normalise: bool = True) -> np.ndarray:
+        """delay-and-sum weights exp(-2 pi j f tau) (normalise: / n_streams) for delays_s [n_beams][n_streams] in seconds and the bins' frequencies [n_bins] in
+        Hz: complex64 [n_beams, n_streams, n_bins], computed in float64 and rounded once"""
+        tau = np.asarray(delays_s, np.float64)
+        f = np.asarray(bin_freqs_hz, np.float64)
+        if tau.ndim != 2 or f.ndim != 1:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "Beamformer.delay_weights", "expected delays [n_beams][n_streams] and frequencies [n_bins]")
+        w = np.exp(-2j * np.pi * f[None, None, :] * tau[:, :, None])
+        if normalise:
+            w = w / tau.shape[1]
+        return w.astype(np.complex64)
+
+    def set_weights(self, w):
+        """complex64 [n_beams, n_streams, n_bins], or [n_beams, n_streams]: the same weight in every bin (expanded on the host); a device tensor is taken as it
+        is.  Stream-ordered: the weights hold for every call enqueued after this one."""
+        what = "Beamformer.set_weights"
+        full = (self.n_beams, self.n_streams, self.n_bins)
+        if isinstance(w, torch.Tensor) and w.is_cuda:
+            d = w.resolve_conj()
+            if d.dtype != torch.complex64 or tuple(d.shape) not in (full, full[:2]):
+                raise capi.Gr4HipError(capi.INVALID_ARGUMENT, what, f"expected complex64 {full} or {full[:2]}")
+            d = (d[:, :, None].expand(full) if d.dim() == 2 else d).contiguous()
+        else:
+            h = np.asarray(w.cpu().numpy() if isinstance(w, torch.Tensor) else w)
+            if tuple(h.shape) not in (full, full[:2]):
+                raise capi.Gr4HipError(capi.INVALID_ARGUMENT, what, f"expected complex64 {full} or {full[:2]}")
+            h = np.array(np.broadcast_to(h[:, :, None] if h.ndim == 2 else h, full), np.complex64)  # (a copy: torch wants writable memory)
+            d = torch.from_numpy(h).cuda()
+        check(lib().gr4hip_beamform_set_weights(self._h, d.data_ptr(), _stream()), what)
+        self._weights = d  # (kept until the next set_weights: the copy is stream-ordered)
+
+    def _inputs(self, spectra, what):
+        xs = [_dev(x, what) for x in (spectra.unbind(0) if isinstance(spectra, torch.Tensor) else spectra)]
+        if len(xs) != self.n_streams or any(x.dtype != torch.complex64 or x.numel() != xs[0].numel() or x.device != xs[0].device for x in xs) or xs[0].numel() % self.n_bins:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, what, f"expected {self.n_streams} complex64 streams of equally many whole frames of {self.n_bins} values")
+        return xs, xs[0].numel() // self.n_bins, (C.c_void_p * self.n_streams)(*[x.data_ptr() for x in xs])
+
+    def process_bulk(self, spectra, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """spectra: a sequence of n_streams complex64 tensors of whole frames (the same tensor may appear twice), or one [n_streams, frames, n_bins] tensor ->
+        the voltage beams, complex64 [n_beams, frames, n_bins]"""
+        what = "Beamformer.process_bulk"
+        xs, frames, ptrs = self._inputs(spectra, what)
+        shape = (self.n_beams, frames, self.n_bins)
+        out = _out(out, self.n_beams * frames * self.n_bins, torch.complex64, xs[0], what, shape)
+        outs = (C.c_void_p * self.n_beams)(*[out.data_ptr() + b * frames * self.n_bins * 8 for b in range(self.n_beams)])
+        check(lib().gr4hip_beamform_process(self._h, ptrs, frames, outs, self.n_bins, _stream()), what)
+        return out.reshape(-1)[:self.n_beams * frames * self.n_bins].view(shape)
+
+    def power_integrated(self, spectra, integrator: "SpectrumIntegrator", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """|Y_b|^2 followed by integrator.process_bulk() on frames [b][c], bit for bit, without the per-frame power in HBM (gr4hip_beamform_power_integrate):
+        float32 [integrator.pending(frames), n_beams, n_bins]; the integrator has n_beams * n_bins bins"""
+        what = "Beamformer.power_integrated"
+        xs, frames, ptrs = self._inputs(spectra, what)
+        n = integrator.pending(frames)
+        shape = (n, self.n_beams, self.n_bins)
+        out = _out(out, n * self.n_beams * self.n_bins, torch.float32, xs[0], what, shape)
+        got = C.c_size_t(0)
+        check(lib().gr4hip_beamform_power_integrate(self._h, integrator._h, ptrs, frames, out.data_ptr() if n else None, C.byref(got), _stream()), what)
+        assert got.value == n
+        return out.reshape(-1)[:n * self.n_beams * self.n_bins].view(shape)
+
+
 class Chain(_Handle):
     """complex<float> fir_filter -> FFT frames -> |X|^2, one fused device pipeline (BASELINE.json configs[1])."""
     _destroy = "gr4hip_chain_destroy"

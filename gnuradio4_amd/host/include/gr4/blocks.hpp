@@ -1672,6 +1672,64 @@ struct CrossSpectrum : Block<CrossSpectrum<T>, Resampling<1024, 3072, false>> {
     }
 };
 
+// ---- beamformer behind n_inputs spectra (BEAMFORMER.md -- the reference has no such block, the definition is the project's): the per-bin weighted sum of the
+// streams into n_beams beams, Y_b[f][c] = sum_s W[b][s][c] X_s[f][c], one frame [n_beams][vector_size] out per frame of vector_size bins in on every input.  One
+// fixed order of operations, on the host as on the device: per beam, frame and bin a float32 fma chain over the streams in ascending order from re = im = +0
+//     re = fmaf(wr_s, xr_s, re);  re = fmaf(-wi_s, xi_s, re);  im = fmaf(wi_s, xr_s, im);  im = fmaf(wr_s, xi_s, im);
+// weights_real / weights_imag hold W[b][s][c], bin fastest (n_beams n_inputs vector_size values), or W[b][s] (n_beams n_inputs values: the same weight in every
+// bin).  input_chunk_size = vector_size, output_chunk_size = n_beams * vector_size, so gr:sample_rate is forwarded scaled by n_beams by the Resampling
+// bookkeeping and nothing is carried between calls.  Integrated power in a graph is Beamformer -> |.|^2 -> SpectrumIntegrator, from the existing blocks.
+template <typename T>
+    requires std::is_same_v<T, float>
+struct Beamformer : Block<Beamformer<T>, Resampling<1024, 1024, false>> {
+    std::vector<PortIn<std::complex<T>>> in{2};
+    PortOut<std::complex<T>>             out;
+    Size_t                               n_inputs    = 2;
+    Size_t                               n_beams     = 1;
+    Size_t                               vector_size = 1024;
+    std::vector<float>                   weights_real{0.5f, 0.5f};
+    std::vector<float>                   weights_imag{0.f, 0.f};
+    GR_MAKE_REFLECTABLE(Beamformer, in, out, n_inputs, n_beams, vector_size, weights_real, weights_imag);
+
+    // W[b][s][c] of either form
+    [[nodiscard]] std::complex<T> weight(std::size_t b, std::size_t s, std::size_t c) const {
+        const std::size_t S = n_inputs, N = vector_size, i = weights_real.size() == static_cast<std::size_t>(n_beams) * S ? b * S + s : (b * S + s) * N + c;
+        return {weights_real[i], weights_imag[i]};
+    }
+
+    void settingsChanged(const property_map&, const property_map&) {
+        if (n_inputs < 1 || n_inputs > 32) throw std::invalid_argument("Beamformer: n_inputs must be in [1, 32]");
+        if (n_beams < 1 || n_beams > 32) throw std::invalid_argument("Beamformer: n_beams must be in [1, 32]");
+        if (vector_size < 2) throw std::invalid_argument("Beamformer: vector_size must be >= 2");
+        if (weights_real.size() != weights_imag.size()) throw std::invalid_argument("Beamformer: weights_real and weights_imag must have the same length");
+        const std::size_t BS = static_cast<std::size_t>(n_beams) * n_inputs;
+        if (weights_real.size() != BS && weights_real.size() != BS * vector_size) throw std::invalid_argument("Beamformer: need n_beams * n_inputs weights, or that times vector_size");
+        if (in.size() != n_inputs) in.resize(n_inputs);
+        this->input_chunk_size  = vector_size;
+        this->output_chunk_size = n_beams * vector_size;
+    }
+    [[nodiscard]] work::Status processBulk(std::span<const std::span<const std::complex<T>>> ins, std::span<std::complex<T>> output) {
+        if (this->input_chunk_size != vector_size || this->output_chunk_size != n_beams * vector_size) settingsChanged({}, {});
+        const std::size_t S = ins.size(), B = n_beams, N = vector_size;
+        for (std::size_t f = 0; (f + 1) * N <= ins[0].size(); ++f) {
+            for (std::size_t b = 0; b < B; ++b) {
+                for (std::size_t c = 0; c < N; ++c) {
+                    float re = 0.f, im = 0.f;
+                    for (std::size_t s = 0; s < S; ++s) {
+                        const std::complex<T> w = weight(b, s, c), x = ins[s][f * N + c];
+                        re = std::fmaf(w.real(), x.real(), re);
+                        re = std::fmaf(-w.imag(), x.imag(), re);
+                        im = std::fmaf(w.imag(), x.real(), im);
+                        im = std::fmaf(w.real(), x.imag(), im);
+                    }
+                    output[(f * B + b) * N + c] = std::complex<T>(re, im);
+                }
+            }
+        }
+        return work::Status::OK;
+    }
+};
+
 // ---- gr::blocks::fft::FFT<T> (blocks/fourier/.../fft.hpp:31-251): one DataSet per frame of fftSize samples
 // window (default Hann) -> unnormalised forward DFT -> magnitude (hypot 2/N [dB], fft-shifted) + phase (atan2 [unwrap][deg], shifted) + Re + Im,
 // frequency axis, per-signal min/max.  T = std::complex<float> (N bins) or float (N/2 bins: fft.hpp:140-143, 221-227).

@@ -1927,6 +1927,65 @@ struct Kernel<gr::blocks::fft::CrossSpectrum<float>> {
     }
 };
 
+// Beamformer<float>: n_inputs spectra -> one stream of frames [n_beams][vector_size] at the seam, like CrossSpectrum above.  The input spans go to HBM as rows of
+// one buffer in one copy, one gr4hip_beamform_process with out_frame_stride = n_beams * vector_size and d_beams[b] = base + b * vector_size, the frames back.  The
+// weights go to the device when the handle is made and whenever the settings change (Block::_settings_generation).
+template <>
+struct Kernel<gr::blocks::fft::Beamformer<float>> {
+    using B = gr::blocks::fft::Beamformer<float>;
+    struct State final : Offload {
+        gr4hip_beamform_t* h = nullptr;
+        std::size_t        S = 0, NB = 0, N = 0;
+        bool               have_weights = false;
+        DevBuf             d_w;
+        ~State() override { if (h) gr4hip_beamform_destroy(h); }
+    };
+    static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
+        try {
+            State*            st = offload_state<State>(blk);
+            const std::size_t S = blk.in.size(), NB = blk.n_beams, N = blk.vector_size;
+            if (!st->h || st->S != S || st->NB != NB || st->N != N) {
+                if (st->h) gr4hip_beamform_destroy(st->h);
+                st->h = nullptr;
+                check(gr4hip_beamform_create(&st->h, S, NB, N), "gr4hip_beamform_create");
+                st->S = S; st->NB = NB; st->N = N;
+                st->have_weights = false;
+            }
+            if (!st->have_weights || st->settings_generation != blk._settings_generation) {
+                std::vector<float> w(2 * NB * S * N);
+                for (std::size_t b = 0, i = 0; b < NB; ++b)
+                    for (std::size_t s = 0; s < S; ++s)
+                        for (std::size_t c = 0; c < N; ++c, ++i) { const auto v = blk.weight(b, s, c); w[2 * i] = v.real(); w[2 * i + 1] = v.imag(); }
+                const std::size_t bw = w.size() * sizeof(float);
+                check(gr4hip_memcpy_h2d(st->d_w.ensure(bw), w.data(), bw, nullptr), "h2d");
+                check(gr4hip_beamform_set_weights(st->h, static_cast<const float*>(st->d_w.p), nullptr), "gr4hip_beamform_set_weights");
+                check(gr4hip_stream_synchronize(nullptr), "sync"); // w leaves scope
+                st->have_weights        = true;
+                st->settings_generation = blk._settings_generation;
+            }
+            if (nIn % N != 0 || nOut != nIn * NB) throw std::runtime_error("Beamformer: the work loop must hand over whole frames");
+            const std::size_t bi = nIn * sizeof(std::complex<float>), bo = nOut * sizeof(std::complex<float>);
+            char*             hin = static_cast<char*>(st->h_in.ensure(S * bi));
+            for (std::size_t s = 0; s < S; ++s) std::memcpy(hin + s * bi, blk.in[s].buffer->read_span(nIn).data(), bi);
+            char* din = static_cast<char*>(st->d_in.ensure(S * bi));
+            check(gr4hip_memcpy_h2d(din, hin, S * bi, nullptr), "h2d");
+            std::vector<const float*> ptrs(S);
+            for (std::size_t s = 0; s < S; ++s) ptrs[s] = reinterpret_cast<const float*>(din + s * bi);
+            float*              dout = static_cast<float*>(st->d_out.ensure(bo));
+            std::vector<float*> outs(NB);
+            for (std::size_t b = 0; b < NB; ++b) outs[b] = dout + b * N * 2;
+            check(gr4hip_beamform_process(st->h, ptrs.data(), nIn / N, outs.data(), NB * N, nullptr), "gr4hip_beamform_process");
+            check(gr4hip_memcpy_d2h(st->h_out.ensure(bo), st->d_out.p, bo, nullptr), "d2h");
+            check(gr4hip_stream_synchronize(nullptr), "sync");
+            if (blk.out.connected()) std::memcpy(blk.out.buffer->write_span(nOut).data(), st->h_out.p, bo);
+            return work::Status::OK;
+        } catch (const std::exception& e) {
+            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
+            return work::Status::ERROR; // never a silent host fallback
+        }
+    }
+};
+
 // FFT block: nOut frames of fftSize samples in, nOut DataSets out.  The four signals and their ranges are computed on the device
 // (gr4hip_fft_process); the host only assembles the descriptive part of the DataSet (axis, names, meta information).
 template <typename T>

@@ -514,6 +514,39 @@ int    gr4hip_xcorr_destroy(gr4hip_xcorr_t* xc);
 size_t gr4hip_xcorr_leaf(void);
 int    gr4hip_xcorr_coherence(const float* d_vis, size_t n_streams, size_t n_bins, size_t n_spectra, size_t i, size_t j, float* d_msc, float* d_h1, gr4hip_stream_t stream);
 
+/* Beamformer (B-engine) behind the spectra above: the per-bin weighted sum of S streams into B beams, 1 <= S <= 32, 1 <= B <= 32 (BEAMFORMER.md).  The reference
+ * has no such block: the definition is the project's, tests/beamformer_oracle.py pins it.  Each stream is a sequence of frames X_s[f][c], c < n_bins,
+ * complex<float> -- what gr4hip_fft_spectrum / gr4hip_pfb_process(d_spectrum) write.  Weights W[b][s][c], complex<float>, bin fastest, one per beam, stream and
+ * bin.  Voltage beams, per beam, frame and bin, float32, streams ascending, re = im = +0 at the start:
+ *       re = fmaf( wr_s, xr_s, re);   re = fmaf(-wi_s, xi_s, re);
+ *       im = fmaf( wi_s, xr_s, im);   im = fmaf( wr_s, xi_s, im);
+ *   Y_b[f][c] = (re, im)
+ * Detected and integrated power: p_b[f][c] = fmaf(yr, yr, yi * yi) (the operation of gr4hip_fft_mag2), then the spectrum integrator's definition above, unchanged,
+ * on frames of B n_bins floats laid out [b][c]: d_out[q][b][c] of gr4hip_beamform_power_integrate equals gr4hip_specint_process applied to the per-frame power,
+ * bit for bit, with that block's emission rules (nothing is written until an integration completes, d_out may be NULL in a call that completes none, a trailing
+ * incomplete integration is never emitted; *n_out = spectra written); the integration's state lives in si, whose n_bins must be B n_bins.  A = 1 gives the
+ * per-frame power itself.  Every chain has one order, so the values do not depend on how the stream is cut into calls or on which kernel ran, bit for bit.  A
+ * non-finite input value reaches every beam, one whose weight is 0 included (0 NaN = NaN), in exactly its own frame and bin, and in the integrated output
+ * exactly the integration that holds its frame.  Per component |Y - exact| <= (2 S + 1) 2^-24 sum_s |W[b][s][c]| |X_s[f][c]|.
+ * d_spectra is a HOST array of S device pointers, each [n_frames][n_bins] complex; the same pointer may appear twice.  d_beams is a HOST array of B device
+ * pointers: d_beams[b] points at beam b's first frame, frame f lies f out_frame_stride complex values further (stride n_bins: one dense stream per beam, what
+ * gr4hip_ifft_process, the synthesis bank and the X-engine take; stride B n_bins with d_beams[b] = base + b n_bins: frames [f][b][c] in one buffer).
+ * gr4hip_beamform_set_weights copies d_weights ([B][S][n_bins] complex, device memory) on the stream: stream-ordered, it holds for every call enqueued after it.
+ * The handle has no other state.  gr4hip_beamform_create is host code; the device buffers come with the first use.
+ * GR4HIP_INVALID_ARGUMENT before any device work, outputs and *n_out untouched: a NULL handle, array, entry of one or n_out, a process call before any
+ * set_weights, n_streams or n_beams == 0, n_bins < 2, buffers not aligned to 8 bytes (the float output: 4), out_frame_stride < n_bins, an output overlapping an
+ * input or another beam's rows, si with n_bins != B n_bins, d_out NULL in a call that completes an integration, more than 2^40 values per stream in one call.
+ * GR4HIP_UNSUPPORTED: n_streams or n_beams > 32, n_bins > 2^20, B S n_bins > 2^24.  n_frames == 0 is a no-op. */
+typedef struct gr4hip_beamform gr4hip_beamform_t;
+int gr4hip_beamform_create(gr4hip_beamform_t** bf, size_t n_streams, size_t n_beams, size_t n_bins);
+int gr4hip_beamform_set_weights(gr4hip_beamform_t* bf, const float* d_weights /* [B][S][N] complex */, gr4hip_stream_t stream);
+int gr4hip_beamform_process(gr4hip_beamform_t* bf, const float* const* d_spectra /* host array, S device pointers */, size_t n_frames,
+                            float* const* d_beams /* host array, B device pointers */, size_t out_frame_stride /* complex values, >= n_bins */,
+                            gr4hip_stream_t stream);
+int gr4hip_beamform_power_integrate(gr4hip_beamform_t* bf, gr4hip_specint_t* si, const float* const* d_spectra, size_t n_frames,
+                                    float* d_out /* [q][B][N] */, size_t* n_out, gr4hip_stream_t stream);
+int gr4hip_beamform_destroy(gr4hip_beamform_t* bf);
+
 /* ------------------------------------------------------------------------------------------------ headline chain
  * complex<float> fir_filter -> FFT block frames -> |X|^2 (BASELINE.json configs[1]).  One call consumes
  * floor(n_samples / fft_size) frames; FIR history (ntaps-1 samples) is carried across calls.
