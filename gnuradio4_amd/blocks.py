@@ -781,6 +781,80 @@ class Beamformer(_Handle):
         return out.reshape(-1)[:n * self.n_beams * self.n_bins].view(shape)
 
 
+class AdaptiveWeights(_Handle):
+    """Adaptive (MVDR / Capon) beamformer weights from the matrices CrossSpectrum emits: per matrix and bin one n_streams x n_streams (2 .. 32) Hermitian
+    positive-definite solve in float64 on the device, for n_beams (1 .. 32) steering vectors -- the project's own definition, ADAPTIVE_WEIGHTS.md:
+    w = R'^-1 a / (a^H R'^-1 a) through a Cholesky factorisation of R' = R + loading * trace(R) / n_streams * I; the output is conj(w), laid out as
+    Beamformer.set_weights reads it, so that sum_s W_s a_s = 1.  A bin whose matrix is not positive definite is NaN and counted (stats())."""
+    _destroy = "gr4hip_mvdr_destroy"
+
+    def __init__(self, n_streams: int, n_beams: int, n_bins: int, loading: float = 0.0):
+        super().__init__()
+        self.n_streams, self.n_beams, self.n_bins = int(n_streams), int(n_beams), int(n_bins)
+        self.n_baselines = self.n_streams * (self.n_streams + 1) // 2
+        self._steering = None
+        check(lib().gr4hip_mvdr_create(C.byref(self._h), self.n_streams, self.n_beams, self.n_bins), "AdaptiveWeights")
+        self.set_loading(loading)
+
+    @staticmethod
+    def steering_from_delays(delays_s, bin_freqs_hz) -> np.ndarray:
+        """steering vectors exp(+2 pi j f tau) for delays_s [n_beams][n_streams] in seconds and the bins' frequencies [n_bins] in Hz: complex64
+        [n_beams, n_streams, n_bins], computed in float64 and rounded once.  This equals conj(Beamformer.delay_weights(tau, f, normalise=False))."""
+        tau = np.asarray(delays_s, np.float64)
+        f = np.asarray(bin_freqs_hz, np.float64)
+        if tau.ndim != 2 or f.ndim != 1:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "AdaptiveWeights.steering_from_delays", "expected delays [n_beams][n_streams] and frequencies [n_bins]")
+        return np.exp(2j * np.pi * f[None, None, :] * tau[:, :, None]).astype(np.complex64)
+
+    def set_steering(self, a):
+        """complex64 [n_beams, n_streams, n_bins], or [n_beams, n_streams]: the same vector in every bin (expanded on the host); a device tensor is taken as it
+        is.  Stream-ordered: the vectors hold for every call enqueued after this one."""
+        what = "AdaptiveWeights.set_steering"
+        full = (self.n_beams, self.n_streams, self.n_bins)
+        if isinstance(a, torch.Tensor) and a.is_cuda:
+            d = a.resolve_conj()
+            if d.dtype != torch.complex64 or tuple(d.shape) not in (full, full[:2]):
+                raise capi.Gr4HipError(capi.INVALID_ARGUMENT, what, f"expected complex64 {full} or {full[:2]}")
+            d = (d[:, :, None].expand(full) if d.dim() == 2 else d).contiguous()
+        else:
+            h = np.asarray(a.cpu().numpy() if isinstance(a, torch.Tensor) else a)
+            if tuple(h.shape) not in (full, full[:2]):
+                raise capi.Gr4HipError(capi.INVALID_ARGUMENT, what, f"expected complex64 {full} or {full[:2]}")
+            h = np.array(np.broadcast_to(h[:, :, None] if h.ndim == 2 else h, full), np.complex64)  # (a copy: torch wants writable memory)
+            d = torch.from_numpy(h).cuda()
+        check(lib().gr4hip_mvdr_set_steering(self._h, d.data_ptr(), _stream()), what)
+        self._steering = d  # (kept until the next set_steering: the copy is stream-ordered)
+
+    def set_loading(self, loading: float):
+        """relative diagonal loading >= 0: lambda = loading * trace(R) / n_streams is added to the diagonal.  Holds for every call enqueued after this one."""
+        check(lib().gr4hip_mvdr_set_loading(self._h, float(loading)), "AdaptiveWeights.set_loading")
+        self.loading = float(loading)
+
+    def process_bulk(self, vis: torch.Tensor, out: Optional[torch.Tensor] = None, power: bool = False):
+        """vis: complex64 [n_spectra, P, n_bins] (or [P, n_bins]) as CrossSpectrum.process_bulk returns it -> the weights, complex64
+        [n_spectra, n_beams, n_streams, n_bins]; row q goes straight into Beamformer.set_weights.  power=True: also the Capon power estimates 1 / (a^H R'^-1 a),
+        float32 [n_spectra, n_beams, n_bins], as a second value."""
+        what = "AdaptiveWeights.process_bulk"
+        v = _dev(vis, what)
+        per = self.n_baselines * self.n_bins
+        if v.dtype != torch.complex64 or v.numel() % per:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, what, f"expected complex64 matrices of {self.n_baselines} baselines of {self.n_bins} bins")
+        n = v.numel() // per
+        shape = (n, self.n_beams, self.n_streams, self.n_bins)
+        numel = n * self.n_beams * self.n_streams * self.n_bins
+        out = _out(out, numel, torch.complex64, v, what, shape)
+        p = torch.empty((n, self.n_beams, self.n_bins), dtype=torch.float32, device=v.device) if power else None
+        check(lib().gr4hip_mvdr_process(self._h, v.data_ptr(), n, out.data_ptr(), p.data_ptr() if power else None, _stream()), what)
+        w = out.reshape(-1)[:numel].view(shape)
+        return (w, p) if power else w
+
+    def stats(self):
+        """(bins solved, bins failed) over every (matrix, bin) processed since the block was made; waits for the block's last call"""
+        solved, failed = C.c_ulonglong(0), C.c_ulonglong(0)
+        check(lib().gr4hip_mvdr_stats(self._h, C.byref(solved), C.byref(failed)), "AdaptiveWeights.stats")
+        return solved.value, failed.value
+
+
 class Chain(_Handle):
     """complex<float> fir_filter -> FFT frames -> |X|^2, one fused device pipeline (BASELINE.json configs[1])."""
     _destroy = "gr4hip_chain_destroy"

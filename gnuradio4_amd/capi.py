@@ -151,6 +151,12 @@ SIGNATURES = {
     "gr4hip_beamform_process": (_i, [_vp, _pvp, _sz, _pvp, _sz, _vp]),
     "gr4hip_beamform_power_integrate": (_i, [_vp, _vp, _pvp, _sz, _vp, _psz, _vp]),
     "gr4hip_beamform_destroy": (_i, [_vp]),
+    "gr4hip_mvdr_create": (_i, [_pvp, _sz, _sz, _sz]),
+    "gr4hip_mvdr_set_steering": (_i, [_vp, _vp, _vp]),
+    "gr4hip_mvdr_set_loading": (_i, [_vp, _d]),
+    "gr4hip_mvdr_process": (_i, [_vp, _vp, _sz, _vp, _vp, _vp]),
+    "gr4hip_mvdr_stats": (_i, [_vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
+    "gr4hip_mvdr_destroy": (_i, [_vp]),
     "gr4hip_decimate": (_i, [_i, _vp, _sz, _sz, _vp, _psz, _vp]),
     "gr4hip_iir_create": (_i, [_pvp, _i, _sz, _vp, _sz, _vp, _sz]),
     "gr4hip_iir_reset": (_i, [_vp]),

@@ -3,7 +3,7 @@
 set -e
 cd "$(dirname "$0")"
 OUT=../libgr4hip.so
-SRCS="runtime.hip fir.hip fir_interp.hip fir_resamp.hip fir_cplx.hip fir_decim_fd.hip fft.hip fft_fast_pk.hip ifft.hip pfb.hip spectrum_integrator.hip cross_spectrum.hip beamformer.hip math.hip ewise.hip iir.hip chain.hip chain_fused.hip chain_td.hip chain16.hip fir_batched.hip fir_bf16.hip fir_f16.hip fir_decim_f16.hip fir_exact.hip design.hip f64.hip fanin.hip freq_est.hip iq_demod.hip power_metrics.hip schmitt_trigger.hip svd_denoiser.hip signal_generator.hip convert.hip electrical.hip savitzky_golay.hip"
+SRCS="runtime.hip fir.hip fir_interp.hip fir_resamp.hip fir_cplx.hip fir_decim_fd.hip fft.hip fft_fast_pk.hip ifft.hip pfb.hip spectrum_integrator.hip cross_spectrum.hip beamformer.hip adaptive_weights.hip math.hip ewise.hip iir.hip chain.hip chain_fused.hip chain_td.hip chain16.hip fir_batched.hip fir_bf16.hip fir_f16.hip fir_decim_f16.hip fir_exact.hip design.hip f64.hip fanin.hip freq_est.hip iq_demod.hip power_metrics.hip schmitt_trigger.hip svd_denoiser.hip signal_generator.hip convert.hip electrical.hip savitzky_golay.hip"
 mkdir -p ../../build/obj
 OBJS=""
 pids=()

@@ -49,6 +49,7 @@ if stale $OUT/test_host_rational_resampler tests/test_host_rational_resampler.cp
 if stale $OUT/test_host_spectrum_integrator tests/test_host_spectrum_integrator.cpp; then $CXX -O2 tests/test_host_spectrum_integrator.cpp -o $OUT/test_host_spectrum_integrator $LINK -ldl & pids+=($!); fi
 if stale $OUT/test_host_cross_spectrum tests/test_host_cross_spectrum.cpp; then $CXX -O2 tests/test_host_cross_spectrum.cpp -o $OUT/test_host_cross_spectrum $LINK -ldl & pids+=($!); fi
 if stale $OUT/test_host_beamformer tests/test_host_beamformer.cpp; then $CXX -O2 tests/test_host_beamformer.cpp -o $OUT/test_host_beamformer $LINK -ldl & pids+=($!); fi
+if stale $OUT/test_host_adaptive_weights tests/test_host_adaptive_weights.cpp; then $CXX -O2 tests/test_host_adaptive_weights.cpp -o $OUT/test_host_adaptive_weights $LINK -ldl & pids+=($!); fi
 for p in "${pids[@]}"; do wait $p; done
 if [ -n "$PLUGIN_OBJS" ]; then $CXX -fPIC -shared -fvisibility=hidden $PLUGIN_OBJS -o ../libgr4hip_blocks.so -L.. -lgr4hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,/opt/rocm/lib; fi
 echo "built $(realpath $OUT)"

@@ -1730,6 +1730,108 @@ struct Beamformer : Block<Beamformer<T>, Resampling<1024, 1024, false>> {
     }
 };
 
+// ---- adaptive (MVDR / Capon) beamformer weights behind CrossSpectrum (ADAPTIVE_WEIGHTS.md -- the reference has no such block, the definition is the project's):
+// per matrix [P][vector_size] in (what CrossSpectrum<float>::out emits, packed lower triangle p = i (i + 1) / 2 + j, j <= i) one set of weights
+// [n_beams][n_inputs][vector_size] out, laid out as Beamformer's weights.  All arithmetic is double, on the host as on the device, per matrix and bin:
+//     R_ij = V_ij (j < i),  R_ji = conj(V_ij),  R_ii = Re V_ii (the imaginary part is ignored)
+//     lambda = loading * (sum_i R_ii) / S ;   R'_ii = R_ii + lambda
+//     R' = L L^H   Cholesky, columns j ascending, every inner sum with k ascending:
+//         s_j  = R'_jj - sum_{k<j} |L_jk|^2 ;   L_jj = sqrt(s_j)
+//         L_ij = (R'_ij - sum_{k<j} L_ik conj(L_jk)) / L_jj            (i > j)
+//     per beam b:   L y = a_b  (forward, k ascending) ;   d = sum_k |y_k|^2
+//                   L^H u = y  (backward) ;   w = u / d
+//     W[q][b][s][c] = conj(w_s)  rounded once to complex<float>
+// and a pivot s_j that is not > 0 (NaN included) makes every weight of that matrix and bin a quiet NaN.  steering_real / steering_imag hold a[b][s][c], bin
+// fastest (n_beams n_inputs vector_size values), or a[b][s] (the same vector in every bin).  input_chunk_size = P * vector_size, output_chunk_size =
+// n_beams * n_inputs * vector_size, so gr:sample_rate is forwarded scaled by n_beams n_inputs / P by the Resampling bookkeeping and nothing is carried between
+// calls.  LIMIT: P * vector_size samples must fit the input edge.  The Capon power is not a port: gr4hip_mvdr_process(d_power) has it.
+template <typename T>
+    requires std::is_same_v<T, float>
+struct AdaptiveWeights : Block<AdaptiveWeights<T>, Resampling<3072, 2048, false>> {
+    PortIn<std::complex<T>>  in;
+    PortOut<std::complex<T>> out;
+    Size_t                   n_inputs    = 2;
+    Size_t                   n_beams     = 1;
+    Size_t                   vector_size = 1024;
+    std::vector<float>       steering_real{1.f, 1.f};
+    std::vector<float>       steering_imag{0.f, 0.f};
+    double                   loading = 0.0;
+    GR_MAKE_REFLECTABLE(AdaptiveWeights, in, out, n_inputs, n_beams, vector_size, steering_real, steering_imag, loading);
+    std::vector<std::complex<double>> _l, _y;
+
+    [[nodiscard]] std::size_t nBaselines() const { return static_cast<std::size_t>(n_inputs) * (n_inputs + 1) / 2; }
+    // a[b][s][c] of either form
+    [[nodiscard]] std::complex<T> steer(std::size_t b, std::size_t s, std::size_t c) const {
+        const std::size_t S = n_inputs, N = vector_size, i = steering_real.size() == static_cast<std::size_t>(n_beams) * S ? b * S + s : (b * S + s) * N + c;
+        return {steering_real[i], steering_imag[i]};
+    }
+
+    void settingsChanged(const property_map&, const property_map&) {
+        if (n_inputs < 2 || n_inputs > 32) throw std::invalid_argument("AdaptiveWeights: n_inputs must be in [2, 32]");
+        if (n_beams < 1 || n_beams > 32) throw std::invalid_argument("AdaptiveWeights: n_beams must be in [1, 32]");
+        if (vector_size < 2) throw std::invalid_argument("AdaptiveWeights: vector_size must be >= 2");
+        if (!(loading >= 0.0) || !std::isfinite(loading)) throw std::invalid_argument("AdaptiveWeights: loading must be finite and >= 0");
+        if (steering_real.size() != steering_imag.size()) throw std::invalid_argument("AdaptiveWeights: steering_real and steering_imag must have the same length");
+        const std::size_t BS = static_cast<std::size_t>(n_beams) * n_inputs;
+        if (steering_real.size() != BS && steering_real.size() != BS * vector_size) throw std::invalid_argument("AdaptiveWeights: need n_beams * n_inputs steering values, or that times vector_size");
+        this->input_chunk_size  = nBaselines() * vector_size;
+        this->output_chunk_size = BS * vector_size;
+    }
+    [[nodiscard]] work::Status processBulk(std::span<const std::complex<T>> input, std::span<std::complex<T>> output) {
+        if (this->input_chunk_size != nBaselines() * vector_size || this->output_chunk_size != static_cast<std::size_t>(n_beams) * n_inputs * vector_size) settingsChanged({}, {});
+        using Cd = std::complex<double>;
+        const std::size_t S = n_inputs, B = n_beams, N = vector_size, P = nBaselines();
+        const float       qnan = std::numeric_limits<float>::quiet_NaN();
+        _l.resize(P);
+        _y.resize(S);
+        const auto tri = [](std::size_t i, std::size_t j) { return i * (i + 1) / 2 + j; };
+        for (std::size_t q = 0; (q + 1) * P * N <= input.size(); ++q) {
+            for (std::size_t c = 0; c < N; ++c) {
+                double tr = 0.0;
+                for (std::size_t i = 0; i < S; ++i) {
+                    for (std::size_t j = 0; j < i; ++j) _l[tri(i, j)] = Cd(input[(q * P + tri(i, j)) * N + c]);
+                    _l[tri(i, i)] = Cd(static_cast<double>(input[(q * P + tri(i, i)) * N + c].real()), 0.0);
+                    tr            = tr + _l[tri(i, i)].real();
+                }
+                const double lambda = loading * tr / static_cast<double>(S);
+                for (std::size_t i = 0; i < S; ++i) _l[tri(i, i)] = Cd(_l[tri(i, i)].real() + lambda, 0.0);
+                bool ok = true;
+                for (std::size_t j = 0; j < S; ++j) { // R' = L L^H in place
+                    double sj = _l[tri(j, j)].real();
+                    for (std::size_t k = 0; k < j; ++k) sj = sj - std::norm(_l[tri(j, k)]);
+                    ok             = ok && (sj > 0.0);
+                    const double d = std::sqrt(sj);
+                    _l[tri(j, j)]  = Cd(d, 0.0);
+                    for (std::size_t i = j + 1; i < S; ++i) {
+                        Cd t = _l[tri(i, j)];
+                        for (std::size_t k = 0; k < j; ++k) t = t - _l[tri(i, k)] * std::conj(_l[tri(j, k)]);
+                        _l[tri(i, j)] = Cd(t.real() / d, t.imag() / d);
+                    }
+                }
+                for (std::size_t b = 0; b < B; ++b) {
+                    double d = 0.0;
+                    for (std::size_t i = 0; i < S; ++i) { // L y = a_b
+                        Cd t = Cd(steer(b, i, c));
+                        for (std::size_t k = 0; k < i; ++k) t = t - _l[tri(i, k)] * _y[k];
+                        const double lii = _l[tri(i, i)].real();
+                        _y[i]            = Cd(t.real() / lii, t.imag() / lii);
+                        d                = d + std::norm(_y[i]);
+                    }
+                    for (std::size_t i = S; i-- > 0;) { // L^H u = y, u over y
+                        Cd t = _y[i];
+                        for (std::size_t k = i + 1; k < S; ++k) t = t - std::conj(_l[tri(k, i)]) * _y[k];
+                        const double lii = _l[tri(i, i)].real();
+                        _y[i]            = Cd(t.real() / lii, t.imag() / lii);
+                    }
+                    for (std::size_t s = 0; s < S; ++s)
+                        output[((q * B + b) * S + s) * N + c] = ok ? std::complex<T>(static_cast<float>(_y[s].real() / d), static_cast<float>(-(_y[s].imag() / d))) : std::complex<T>(qnan, qnan);
+                }
+            }
+        }
+        return work::Status::OK;
+    }
+};
+
 // ---- gr::blocks::fft::FFT<T> (blocks/fourier/.../fft.hpp:31-251): one DataSet per frame of fftSize samples
 // window (default Hann) -> unnormalised forward DFT -> magnitude (hypot 2/N [dB], fft-shifted) + phase (atan2 [unwrap][deg], shifted) + Re + Im,
 // frequency axis, per-signal min/max.  T = std::complex<float> (N bins) or float (N/2 bins: fft.hpp:140-143, 221-227).

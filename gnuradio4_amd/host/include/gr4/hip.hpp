@@ -1986,6 +1986,59 @@ struct Kernel<gr::blocks::fft::Beamformer<float>> {
     }
 };
 
+// AdaptiveWeights<float>: matrices [P][vector_size] -> weights [n_beams][n_inputs][vector_size] at the seam (no Stage: the block changes the chunk shape like
+// CrossSpectrum above).  The matrices go to HBM in one copy, one gr4hip_mvdr_process, the weights back.  The steering vectors and the loading go to the handle
+// when it is made and whenever the settings change (Block::_settings_generation).
+template <>
+struct Kernel<gr::blocks::fft::AdaptiveWeights<float>> {
+    using B = gr::blocks::fft::AdaptiveWeights<float>;
+    struct State final : Offload {
+        gr4hip_mvdr_t* h = nullptr;
+        std::size_t    S = 0, NB = 0, N = 0;
+        bool           have_steering = false;
+        DevBuf         d_a;
+        ~State() override { if (h) gr4hip_mvdr_destroy(h); }
+    };
+    static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
+        try {
+            State*            st = offload_state<State>(blk);
+            const std::size_t S = blk.n_inputs, NB = blk.n_beams, N = blk.vector_size, P = blk.nBaselines();
+            if (!st->h || st->S != S || st->NB != NB || st->N != N) {
+                if (st->h) gr4hip_mvdr_destroy(st->h);
+                st->h = nullptr;
+                check(gr4hip_mvdr_create(&st->h, S, NB, N), "gr4hip_mvdr_create");
+                st->S = S; st->NB = NB; st->N = N;
+                st->have_steering = false;
+            }
+            if (!st->have_steering || st->settings_generation != blk._settings_generation) {
+                std::vector<float> a(2 * NB * S * N);
+                for (std::size_t b = 0, i = 0; b < NB; ++b)
+                    for (std::size_t s = 0; s < S; ++s)
+                        for (std::size_t c = 0; c < N; ++c, ++i) { const auto v = blk.steer(b, s, c); a[2 * i] = v.real(); a[2 * i + 1] = v.imag(); }
+                const std::size_t ba = a.size() * sizeof(float);
+                check(gr4hip_memcpy_h2d(st->d_a.ensure(ba), a.data(), ba, nullptr), "h2d");
+                check(gr4hip_mvdr_set_steering(st->h, static_cast<const float*>(st->d_a.p), nullptr), "gr4hip_mvdr_set_steering");
+                check(gr4hip_mvdr_set_loading(st->h, blk.loading), "gr4hip_mvdr_set_loading");
+                check(gr4hip_stream_synchronize(nullptr), "sync"); // a leaves scope
+                st->have_steering       = true;
+                st->settings_generation = blk._settings_generation;
+            }
+            if (nIn % (P * N) != 0 || nOut != nIn / (P * N) * NB * S * N) throw std::runtime_error("AdaptiveWeights: the work loop must hand over whole matrices");
+            const std::size_t bi = nIn * sizeof(std::complex<float>), bo = nOut * sizeof(std::complex<float>);
+            std::memcpy(st->h_in.ensure(bi), blk.in.buffer->read_span(nIn).data(), bi);
+            check(gr4hip_memcpy_h2d(st->d_in.ensure(bi), st->h_in.p, bi, nullptr), "h2d");
+            check(gr4hip_mvdr_process(st->h, static_cast<const float*>(st->d_in.p), nIn / (P * N), static_cast<float*>(st->d_out.ensure(bo)), nullptr, nullptr), "gr4hip_mvdr_process");
+            check(gr4hip_memcpy_d2h(st->h_out.ensure(bo), st->d_out.p, bo, nullptr), "d2h");
+            check(gr4hip_stream_synchronize(nullptr), "sync");
+            if (blk.out.connected()) std::memcpy(blk.out.buffer->write_span(nOut).data(), st->h_out.p, bo);
+            return work::Status::OK;
+        } catch (const std::exception& e) {
+            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
+            return work::Status::ERROR; // never a silent host fallback
+        }
+    }
+};
+
 // FFT block: nOut frames of fftSize samples in, nOut DataSets out.  The four signals and their ranges are computed on the device
 // (gr4hip_fft_process); the host only assembles the descriptive part of the DataSet (axis, names, meta information).
 template <typename T>

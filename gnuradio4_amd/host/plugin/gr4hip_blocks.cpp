@@ -133,6 +133,7 @@ const bool registered = [] {
     r.insert<gr::blocks::fft::SpectrumIntegrator<float>>(named<float>("gr::blocks::fft::SpectrumIntegrator")); // SPECTRUM_INTEGRATOR.md; no reference block
     r.insert<gr::blocks::fft::CrossSpectrum<float>>(named<float>("gr::blocks::fft::CrossSpectrum")); // CROSS_SPECTRUM.md; no reference block
     r.insert<gr::blocks::fft::Beamformer<float>>(named<float>("gr::blocks::fft::Beamformer")); // BEAMFORMER.md; no reference block
+    r.insert<gr::blocks::fft::AdaptiveWeights<float>>(named<float>("gr::blocks::fft::AdaptiveWeights")); // ADAPTIVE_WEIGHTS.md; no reference block
     r.insert<gr::hip::OnDevice<fir_filter<float>>>(named<float>("gr::hip::OnDevice<gr::filter::fir_filter", ">"));
     r.insert<gr::hip::OnDevice<fir_filter<std::complex<float>>>>(named<std::complex<float>>("gr::hip::OnDevice<gr::filter::fir_filter", ">"));
     r.insert<gr::hip::OnDevice<gr::blocks::fft::PowerSpectrum<std::complex<float>>>>(named<std::complex<float>>("gr::hip::OnDevice<gr::blocks::fft::PowerSpectrum", ">"));

@@ -547,6 +547,43 @@ int gr4hip_beamform_power_integrate(gr4hip_beamform_t* bf, gr4hip_specint_t* si,
                                     float* d_out /* [q][B][N] */, size_t* n_out, gr4hip_stream_t stream);
 int gr4hip_beamform_destroy(gr4hip_beamform_t* bf);
 
+/* Adaptive (MVDR / Capon) beamformer weights from the X-engine's matrices: per emitted matrix and bin one S x S Hermitian positive-definite solve in float64,
+ * 2 <= S <= 32, for 1 <= B <= 32 steering vectors (ADAPTIVE_WEIGHTS.md).  The reference has no such block: the definition is the project's,
+ * tests/adaptive_weights_oracle.py pins it.  Inputs: V[q][p][c], complex<float>, exactly what gr4hip_xcorr_process writes (packed lower triangle
+ * p = i (i + 1) / 2 + j, j <= i, bin fastest); steering vectors a[b][s][c], complex<float>, in the layout of the beamformer's weights (a_s: the array's response
+ * in stream s to the wanted direction; for delays tau, a = exp(+2 pi j f tau)); loading >= 0, a double held by the handle (default 0).  All arithmetic is
+ * float64 (a float input is exact there); every step reads the step before it:
+ *       R_ij = V_ij (j < i),  R_ji = conj(V_ij),  R_ii = Re V_ii (the imaginary part is ignored)
+ *       lambda = loading * (sum_i R_ii) / S ;   R'_ii = R_ii + lambda
+ *       R' = L L^H   Cholesky, columns j ascending, every inner sum with k ascending:
+ *           s_j  = R'_jj - sum_{k<j} |L_jk|^2 ;   L_jj = sqrt(s_j)
+ *           L_ij = (R'_ij - sum_{k<j} L_ik conj(L_jk)) / L_jj            (i > j)
+ *       per beam b:   L y = a_b  (forward, k ascending) ;   d = sum_k |y_k|^2
+ *                     L^H u = y  (backward) ;   w = u / d
+ *       W[q][b][s][c] = conj(w_s)  rounded once to complex<float>
+ *       P[q][b][c]    = (float)(1 / d)
+ * The beamformer's Y = sum_s W_s X_s is then w^H X and sum_s W_s a_s = 1; P is the Capon power estimate in the units of V.  d_weights + q B S n_bins complex
+ * values is directly what gr4hip_beamform_set_weights takes.  If any pivot s_j is not > 0 (NaN included) the bin of that matrix has failed: every W and P of
+ * that (q, c), for all beams, is a quiet NaN and the bin is counted; neighbouring bins and matrices are untouched.  Every entry of R' feeds some pivot, so a NaN
+ * anywhere in the matrix fails exactly its own bin.  A non-finite steering value goes through IEEE arithmetic, reaches only its own beam in its own bin and is
+ * not counted.  The result of (q, c) is the same bits whatever n_spectra and whichever other matrices share the call.  Per component
+ * |W - exact| <= 2^-24 |W_exact| + (8 + S) cond2(R') 2^-53 ||w||_2 and |P - exact| <= 2^-24 P + 2 (8 + S) cond2(R') 2^-53 P.
+ * gr4hip_mvdr_create is host code; the device buffers come with the first use.  gr4hip_mvdr_set_steering copies d_steer (device memory) on the stream: it holds
+ * for the calls enqueued after it.  gr4hip_mvdr_set_loading is stream-ordered like every lifecycle call (LIFECYCLE CALLS above).  gr4hip_mvdr_stats waits for
+ * the handle's last call: bins_failed = failed (matrix, bin) pairs since create, bins_solved = all other pairs processed since create.
+ * GR4HIP_INVALID_ARGUMENT before any device work, outputs untouched: a NULL handle, d_vis, d_weights or d_steer, a process call before any set_steering,
+ * n_streams < 2, n_beams == 0, n_bins < 2, a negative or non-finite loading, complex buffers not aligned to 8 bytes (d_power: 4), an output overlapping an
+ * input or the other output, more than 2^40 weights in one call.  GR4HIP_UNSUPPORTED: n_streams or n_beams > 32, n_bins > 2^20, B S n_bins > 2^24.
+ * n_spectra == 0 is a no-op. */
+typedef struct gr4hip_mvdr gr4hip_mvdr_t;
+int gr4hip_mvdr_create(gr4hip_mvdr_t** h, size_t n_streams, size_t n_beams, size_t n_bins);
+int gr4hip_mvdr_set_steering(gr4hip_mvdr_t* h, const float* d_steer /* [B][S][N] complex */, gr4hip_stream_t stream);
+int gr4hip_mvdr_set_loading(gr4hip_mvdr_t* h, double loading);
+int gr4hip_mvdr_process(gr4hip_mvdr_t* h, const float* d_vis /* [n_spectra][P][N] complex */, size_t n_spectra, float* d_weights /* [n_spectra][B][S][N] complex */,
+                        float* d_power /* [n_spectra][B][N], may be NULL */, gr4hip_stream_t stream);
+int gr4hip_mvdr_stats(gr4hip_mvdr_t* h, unsigned long long* bins_solved, unsigned long long* bins_failed);
+int gr4hip_mvdr_destroy(gr4hip_mvdr_t* h);
+
 /* ------------------------------------------------------------------------------------------------ headline chain
  * complex<float> fir_filter -> FFT block frames -> |X|^2 (BASELINE.json configs[1]).  One call consumes
  * floor(n_samples / fft_size) frames; FIR history (ntaps-1 samples) is carried across calls.
