@@ -27,6 +27,7 @@
 #define GR4_TD_STORE_NT 0
 #endif
 #include "common.hpp"
+#include "history.hpp"
 #include "buffer_ops.hpp"
 #include "fft_radix.hpp"
 #include "fir_f16_common.hpp" // (hf_wave_sum)
@@ -338,24 +339,17 @@ struct ChainTd {
     size_t       ntaps = 0, N = 0;
     int          KS = 0, Kp = 0, log2n = 0;
     bool         windowed = false;
-    DeviceBuffer d_afrag, d_win, d_tw, d_hist[2];
-    int          cur = 0, dev = 0;
-    bool         zero_hist = true; // reset asked for (or nothing has run yet): d_hist[cur] is zeroed on the stream of the next call that reads it (common.hpp, the stream rule)
+    DeviceBuffer d_afrag, d_win, d_tw;
+    CarriedHistory hist;          // Kp complex samples; the main kernel writes the next one itself
+    int          dev = 0;
 };
 
 int chain_td_supported(size_t ntaps, size_t fft_size, int window) {
     return is_pow2(fft_size) && fft_size >= 256 && fft_size <= 4096 && ntaps >= 1 && ntaps <= 256 && window >= GR4HIP_WIN_NONE && window <= GR4HIP_WIN_KAISER;
 }
 
-int chain_td_reset(ChainTd* c) { // host-side note only: a launch still in flight may be writing d_hist[cur] (its `new_hist`); the zeroing goes behind it on the next call's stream
-    c->zero_hist = true;
-    return GR4HIP_OK;
-}
-static int td_history_on(ChainTd* c, hipStream_t st) {
-    if (c->zero_hist) {
-        GR4_HIP_TRY(hipMemsetAsync(c->d_hist[c->cur].ptr, 0, (size_t)c->Kp * sizeof(float2), st));
-        c->zero_hist = false;
-    }
+int chain_td_reset(ChainTd* c) { // host-side note only: a launch still in flight may be writing the current history (its `new_hist`); the zeroing goes behind it on the next call's stream
+    c->hist.reset();
     return GR4HIP_OK;
 }
 
@@ -398,8 +392,7 @@ int chain_td_create(ChainTd** out, const float* taps, size_t ntaps, size_t fft_s
         }
         rc = up(c->d_tw, ts.data(), ts.size() * sizeof(float));
     }
-    for (int k = 0; k < 2 && !rc; ++k) rc = c->d_hist[k].ensure((size_t)c->Kp * sizeof(float2));
-    if (!rc) rc = chain_td_reset(c);
+    if (!rc) rc = c->hist.resize((size_t)c->Kp * sizeof(float2));
     if (rc) { delete c; return rc; }
     *out = c;
     return GR4HIP_OK;
@@ -411,12 +404,12 @@ void chain_td_destroy(ChainTd* c) { delete c; }
 // (null: a pending reset could not be enqueued)
 const float* chain_td_history(ChainTd* c, int* Kp, hipStream_t st) {
     if (Kp) *Kp = c->Kp;
-    return td_history_on(c, st) ? nullptr : static_cast<const float*>(c->d_hist[c->cur].ptr);
+    return c->hist.on(st) ? nullptr : static_cast<const float*>(c->hist.current());
 }
 // start from the 256 complex samples in front of the next call (the fused frequency-domain kernel's convention)
 int chain_td_set_history256(ChainTd* c, const float* d_hist256, hipStream_t st) {
-    c->zero_hist = false;
-    GR4_HIP_TRY(hipMemcpyAsync(c->d_hist[c->cur].ptr, d_hist256 + 2 * (256 - c->Kp), (size_t)c->Kp * sizeof(float2), hipMemcpyDeviceToDevice, st));
+    c->hist.keep();
+    GR4_HIP_TRY(hipMemcpyAsync(c->hist.current(), d_hist256 + 2 * (256 - c->Kp), (size_t)c->Kp * sizeof(float2), hipMemcpyDeviceToDevice, st));
     return GR4HIP_OK;
 }
 
@@ -429,8 +422,8 @@ static int td_launch(ChainTd* c, const float* d_in, size_t n_frames, float* d_ma
     GR4_HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->dev));
 
     const auto    xc = reinterpret_cast<const float2*>(d_in);
-    const auto    hc = static_cast<const float2*>(c->d_hist[c->cur].ptr);
-    const auto    nh = static_cast<float2*>(c->d_hist[c->cur ^ 1].ptr);
+    const auto    hc = static_cast<const float2*>(c->hist.current());
+    const auto    nh = static_cast<float2*>(c->hist.next());
     const auto    af = static_cast<const td_u32x4*>(c->d_afrag.ptr);
     const float*  wn = c->windowed ? static_cast<const float*>(c->d_win.ptr) : nullptr;
     const auto    tw = static_cast<const float2*>(c->d_tw.ptr);
@@ -457,7 +450,7 @@ static int td_launch(ChainTd* c, const float* d_in, size_t n_frames, float* d_ma
     }
 #undef GR4_TD_CASE
     GR4_LAUNCH_CHECK();
-    c->cur ^= 1;
+    c->hist.flip();
     return GR4HIP_OK;
 }
 
@@ -466,7 +459,7 @@ static int td_launch(ChainTd* c, const float* d_in, size_t n_frames, float* d_ma
 int chain_td_process(ChainTd* c, const float* d_in, size_t n_frames, float* d_mag2, hipStream_t st, bool judged) {
     if (n_frames == 0) return GR4HIP_OK;
     GR4_REQUIRE((uintptr_t)d_in % 8 == 0 && (uintptr_t)d_mag2 % 4 == 0, "fused time-domain chain: misaligned device pointer");
-    if (const int rc = td_history_on(c, st)) return rc;
+    if (const int rc = c->hist.on(st)) return rc;
     switch (c->KS) {
     case 3: return td_launch<3>(c, d_in, n_frames, d_mag2, st, judged);
     case 5: return td_launch<5>(c, d_in, n_frames, d_mag2, st, judged);

@@ -87,6 +87,7 @@ inline size_t dtype_size(int dtype) {
 
 inline bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
 inline int  ilog2(size_t n) { int l = 0; while ((size_t(1) << l) < n) ++l; return l; }
+inline size_t bit_ceil(size_t v) { size_t p = 1; while (p < v) p <<= 1; return p; } // std::bit_ceil (the capacity of the reference's HistoryBuffer)
 template <typename T> inline T ceil_div(T a, T b) { return (a + b - 1) / b; }
 
 // A rotator's phase in TURNS as a 64-bit binary fraction (units of 2^-64 turn): sums and products modulo 2^64 ARE the reduction modulo one turn, so
@@ -154,11 +155,12 @@ struct DeviceBuffer {
 //        (a new DeviceBuffer, or one whose ensure() has just replaced it: hipFree waits for the device).  Complete when it returns, so visible to work enqueued
 //        afterwards on any stream.
 //   (ii) work enqueued on the stream of a process call: hipMemsetAsync / hipMemcpyAsync / kernels on `st`.
-// reset / set_taps / set_prologue / set_algo never touch the device: they note what the state has to become (zero_hist, taps_dirty, ...) and the next process
+// reset / set_taps / set_prologue / set_algo never touch the device: they note what the state has to become (CarriedHistory::reset, taps_dirty, ...) and the next process
 // call applies it on ITS stream, in front of its own launches and therefore behind everything that stream still has in flight for the handle.  That is the
 // reference's contract -- reset() / settingsChanged() run on the block's worker between two work() calls (Block.hpp:606, 916-917, 1296; Scheduler.hpp:1938-1951) --
 // without a device-wide wait, and it holds on hipStreamNonBlocking streams, which the NULL stream does not order against (round 5's race: a NULL-stream hipMemset
-// of the carried history overtaken by the previous launch's carry).  The host image a hipMemcpyAsync reads is owned by the handle (tp_host, row_host, ...), never a
+// of the carried history overtaken by the previous launch's carry).  The carried history of the streaming filters -- the ping-pong pair, its pending zeroing and
+// its carry launch -- has one implementation of this rule: CarriedHistory (history.hpp).  The host image a hipMemcpyAsync reads is owned by the handle (tp_host, row_host, ...), never a
 // local: the copy may still be reading it after the call returns.  tests/test_abi_host.py greps for bare hipMemset( / hipMemcpy( in this directory.
 inline hipError_t upload_fresh(void* dst, const void* src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); }
 

@@ -9,6 +9,7 @@
 //              untangled into the block's outputs in double (N < 16: one frame per workgroup, radix-2 passes)
 //   Rotator    closed-form phase per sample (the float64 oracle's definition up to the rounding of the accumulated sum)
 #include "common.hpp"
+#include "history.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -143,14 +144,6 @@ __global__ __launch_bounds__(256) void fir64_mfma_kernel(const double* __restric
             new_hist[h]  = g >= 0 ? x[g] : hist[hcap + g];
         }
     }
-}
-
-// new_hist[h] = virtual sample n_in - hcap + h of (old_hist ++ x)
-__global__ void hist64_kernel(const double* __restrict__ x, const double* __restrict__ old_hist, double* __restrict__ new_hist, long n_in, int hcap) {
-    const int h = blockIdx.x * blockDim.x + threadIdx.x;
-    if (h >= hcap) return;
-    const long g = n_in - hcap + h;
-    new_hist[h]  = g >= 0 ? x[g] : old_hist[hcap + g];
 }
 
 // ------------------------------------------------------------------------------------------------ IIR
@@ -576,11 +569,11 @@ using namespace gr4;
 struct gr4hip_fir64 {
     std::vector<double> taps;
     size_t              decim = 1, hcap = 32;
-    DeviceBuffer        d_taps, d_hist[2], d_trow; // d_trow: zero-padded tap row of the matrix-pipe kernel
-    int                 cur = 0;
+    DeviceBuffer        d_taps, d_trow; // d_trow: zero-padded tap row of the matrix-pipe kernel
+    CarriedHistory      hist;           // hcap doubles
     // the stream rule (common.hpp): create / reset / set_taps only note what the device state has to become; fir64_state_on() enqueues it on the stream of the next call
     std::vector<double> row_host;
-    bool                taps_dirty = false, zero_hist = true;
+    bool                taps_dirty = false;
 };
 struct gr4hip_iir64 {
     Iir64Desc    d{};
@@ -599,10 +592,8 @@ struct gr4hip_rotator64 {
     double inc = 0.0, phase = 0.0, initial = 0.0;
 };
 
-static size_t bit_ceil_sz(size_t v) { size_t p = 1; while (p < v) p <<= 1; return p; }
-
 static int fir64_upload(gr4hip_fir64* f, const double* taps, size_t ntaps, bool keep_history) {
-    const size_t hcap = std::max<size_t>(32, bit_ceil_sz(ntaps)); // HistoryBuffer{32}, grown by settingsChanged (time_domain_filter.hpp:36-42)
+    const size_t hcap = std::max<size_t>(32, bit_ceil(ntaps)); // HistoryBuffer{32}, grown by settingsChanged (time_domain_filter.hpp:36-42)
     int          rc   = f->d_taps.ensure(ntaps * sizeof(double)); // (growing frees the old table: hipFree waits for the device)
     if (rc) return rc;
     { // fir64_mfma_kernel: row[16 + q] = b[q], zero elsewhere
@@ -613,12 +604,9 @@ static int fir64_upload(gr4hip_fir64* f, const double* taps, size_t ntaps, bool 
         rc = f->d_trow.ensure(row.size() * sizeof(double));
         if (rc) return rc;
     }
-    if (!keep_history || hcap != f->hcap || !f->d_hist[0].ptr) { // a history that has to grow starts empty, as upstream's replaced HistoryBuffer does
-        for (auto& h : f->d_hist) {
-            rc = h.ensure(hcap * sizeof(double));
-            if (rc) return rc;
-        }
-        f->zero_hist = true;
+    if (!keep_history || hcap != f->hcap || !f->hist.current()) { // a history that has to grow starts empty, as upstream's replaced HistoryBuffer does
+        rc = f->hist.resize(hcap * sizeof(double));
+        if (rc) return rc;
     }
     f->hcap = hcap;
     f->taps.assign(taps, taps + ntaps);
@@ -632,11 +620,7 @@ static int fir64_state_on(gr4hip_fir64* f, hipStream_t st) {
         GR4_HIP_TRY(hipMemcpyAsync(f->d_trow.ptr, f->row_host.data(), f->row_host.size() * sizeof(double), hipMemcpyHostToDevice, st));
         f->taps_dirty = false;
     }
-    if (f->zero_hist) {
-        GR4_HIP_TRY(hipMemsetAsync(f->d_hist[f->cur].ptr, 0, f->hcap * sizeof(double), st));
-        f->zero_hist = false;
-    }
-    return GR4HIP_OK;
+    return f->hist.on(st);
 }
 
 extern "C" {
@@ -661,7 +645,7 @@ int gr4hip_fir64_set_taps(gr4hip_fir64_t* f, const double* h_taps, size_t ntaps)
 }
 int gr4hip_fir64_reset(gr4hip_fir64_t* f) {
     GR4_REQUIRE(f, "fir64_reset: null handle");
-    f->zero_hist = true;
+    f->hist.reset();
     return GR4HIP_OK;
 }
 int gr4hip_fir64_process(gr4hip_fir64_t* f, const double* d_in, size_t n_in, double* d_out, size_t* n_out_p, gr4hip_stream_t stream) {
@@ -678,8 +662,8 @@ int gr4hip_fir64_process(gr4hip_fir64_t* f, const double* d_in, size_t n_in, dou
         const int    Kp = K <= 64 ? 64 : K <= 128 ? 128 : K <= 256 ? 256 : (K + 63) / 64 * 64, NPAD = (kF64Seg + Kp) / 16 * 18;
         const size_t lds = ((size_t)NPAD + Kp + 32) * sizeof(double);
         const dim3   grid((unsigned)ceil_div(ceil_div((long)n_in, (long)kF64Seg), (long)kF64SegPerWg));
-        const auto   hp = (const double*)f->d_hist[f->cur].ptr;
-        auto         nh = (double*)f->d_hist[f->cur ^ 1].ptr;
+        const auto   hp = (const double*)f->hist.current();
+        auto         nh = (double*)f->hist.next();
         const auto   tr = (const double*)f->d_trow.ptr;
 #define GR4_F64_MFMA(KSV)                                                                                                                   \
     do {                                                                                                                                    \
@@ -690,7 +674,7 @@ int gr4hip_fir64_process(gr4hip_fir64_t* f, const double* d_in, size_t n_in, dou
         if (Kp == 64) GR4_F64_MFMA(20); else if (Kp == 128) GR4_F64_MFMA(36); else if (Kp == 256) GR4_F64_MFMA(68); else GR4_F64_MFMA(0);
 #undef GR4_F64_MFMA
         GR4_LAUNCH_CHECK();
-        f->cur ^= 1;
+        f->hist.flip();
         return GR4HIP_OK;
     }
     const int   R = D <= 8 ? 4 : D <= 16 ? 2 : 1;
@@ -698,13 +682,9 @@ int gr4hip_fir64_process(gr4hip_fir64_t* f, const double* d_in, size_t n_in, dou
     const auto  kern = R == 4 ? fir64_kernel<4> : R == 2 ? fir64_kernel<2> : fir64_kernel<1>;
     if (lds > 64 * 1024) GR4_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const unsigned grid = (unsigned)ceil_div(n_out, (size_t)kF64BS * R);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kF64BS), lds, st, d_in, (const double*)f->d_hist[f->cur].ptr, (int)f->hcap, (const double*)f->d_taps.ptr, K, D, d_out, (long)n_out, (long)n_in);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kF64BS), lds, st, d_in, (const double*)f->hist.current(), (int)f->hcap, (const double*)f->d_taps.ptr, K, D, d_out, (long)n_out, (long)n_in);
     GR4_LAUNCH_CHECK();
-    hipLaunchKernelGGL(hist64_kernel, dim3((unsigned)ceil_div(f->hcap, (size_t)256)), dim3(256), 0, st, d_in, (const double*)f->d_hist[f->cur].ptr, (double*)f->d_hist[f->cur ^ 1].ptr,
-                       (long)n_in, (int)f->hcap);
-    GR4_LAUNCH_CHECK();
-    f->cur ^= 1;
-    return GR4HIP_OK;
+    return f->hist.advance(d_in, n_in, f->hcap, sizeof(double), st);
 }
 int gr4hip_fir64_destroy(gr4hip_fir64_t* f) { delete f; return GR4HIP_OK; }
 

@@ -12,6 +12,7 @@
 // Long spans leave this kernel: float 33..256 taps and polyphase decimators go to the MFMA kernels of fir_batched.hip, complex <= 256 taps
 // to the frequency-domain kernel of chain_fused.hip (gr4hip_fir_process below decides).
 #include "common.hpp"
+#include "history.hpp"
 #include "fir_exact.hpp"
 #include "ewise.hpp"
 #include "fir_window.hpp"
@@ -260,16 +261,6 @@ __global__ __launch_bounds__(256) void fir_generic_kernel(const float* __restric
     for (int c = 0; c < S; ++c) y[m * S + c] = acc[c];
 }
 
-// new_hist[h] = virtual_input[n_in - hcap + h]  (virtual_input(i<0) = old_hist[hcap + i])
-__global__ void fir_hist_update_kernel(const float* __restrict__ x, const float* __restrict__ old_hist, float* __restrict__ new_hist, long n_in,
-                                       int hcap, int S) {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long)hcap * S) return;
-    const long h = t / S, c = t % S;
-    const long i = n_in - hcap + h;
-    new_hist[t]  = (i >= 0) ? x[i * S + c] : old_hist[(hcap + i) * S + c];
-}
-
 // the stored history changes its meaning (a prologue gain moves into or out of the taps): every sample times `factor`
 __global__ void fir_hist_scale_kernel(float* __restrict__ hist, int nfloats, float factor) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -356,8 +347,7 @@ struct gr4hip_fir {
     double             guard_ratio = kGuardSegmentRatio; // (library-internal callers may tighten it: the chain's kernel pair squares this filter's output -- chain.hip)
     DeviceBuffer       d_flags_fd; // the same for the frequency-domain kernels' spans (judged behind their launch at their own thresholds)
     DeviceBuffer       d_flags;    // one byte per segment of the f16 matrix-pipe kernels' last launch: the segments fir_exact_kernel evaluates again behind it
-    DeviceBuffer       d_hist[2];  // ping-pong history (hcap samples each)
-    int                cur = 0;
+    CarriedHistory     hist;       // hcap samples (S interleaved floats each)
     int                algo = GR4HIP_FIR_AUTO; // gr4hip_fir_set_algo
     bool               f32_user = false;       // (what gr4hip_fir_set_algo asked for: a reset re-arms the guard and goes back to it)
     bool               bf16_user = false;      // GR4HIP_FIR_TIME_DOMAIN_BF16X3: the three-term bf16 products where the default would take the two-term f16 ones
@@ -408,13 +398,10 @@ struct gr4hip_fir {
     // the next call that needs it, behind whatever that stream still has in flight for this handle
     std::vector<float> tp_host;        // d_taps' image ([D][Qpad]) as fir_upload_taps laid it out
     bool               taps_dirty = false; // d_taps / d_tapsf do not hold tp_host / taps yet
-    bool               zero_hist  = true;  // d_hist[cur] is to be zeroed (create, reset, a history that had to grow)
-    double             hist_rescale = 1.0; // d_hist[cur] is to be multiplied by this (a prologue gain that moved into or out of the taps)
+    double             hist_rescale = 1.0; // the current history is to be multiplied by this (a prologue gain that moved into or out of the taps)
     unsigned           last_paths = 0;     // which paths served the last gr4hip_fir_process call (gr4hip_internal_fir_last_paths)
     ~gr4hip_fir() { delete pre; delete post; }
 };
-
-static size_t bit_ceil_sz(size_t v) { size_t p = 1; while (p < v) p <<= 1; return p; }
 
 static int fir_upload_taps(gr4hip_fir* f) {
     const size_t D = f->decim, K = f->ntaps;
@@ -435,16 +422,6 @@ static int fir_upload_taps(gr4hip_fir* f) {
     return GR4HIP_OK;
 }
 
-static int fir_alloc_hist(gr4hip_fir* f) {
-    const size_t bytes = f->hcap * f->S * sizeof(float);
-    for (int k = 0; k < 2; ++k) {
-        int rc = f->d_hist[k].ensure(bytes);
-        if (rc) return rc;
-    }
-    f->zero_hist    = true; // zeroed by fir_state_on, on the stream of the next call (a launch still in flight may be writing either half of the pair)
-    f->hist_rescale = 1.0;
-    return GR4HIP_OK;
-}
 // The handle's device state as the call about to be enqueued on `st` must see it: pending tap upload, pending zeroing / rescaling of the carried history.
 // Everything goes onto `st`, so it is ordered behind the earlier launches of this handle on that stream (Block.hpp:606, 916-917: reset() / settingsChanged() run
 // between two work() calls of the block's own worker) and in front of the launch that follows.
@@ -454,14 +431,11 @@ static int fir_state_on(gr4hip_fir* f, hipStream_t st) {
         GR4_HIP_TRY(hipMemcpyAsync(f->d_tapsf.ptr, f->taps.data(), f->ntaps * sizeof(float), hipMemcpyHostToDevice, st));
         f->taps_dirty = false;
     }
-    if (f->zero_hist) {
-        GR4_HIP_TRY(hipMemsetAsync(f->d_hist[f->cur].ptr, 0, f->hcap * f->S * sizeof(float), st));
-        f->zero_hist    = false;
-        f->hist_rescale = 1.0;
-    }
+    if (f->hist.zero) f->hist_rescale = 1.0; // (a pending zeroing cancels a pending rescale)
+    if (const int rc = f->hist.on(st)) return rc;
     if (f->hist_rescale != 1.0) {
         const int nf = (int)(f->hcap * f->S);
-        hipLaunchKernelGGL(fir_hist_scale_kernel, dim3((unsigned)ceil_div(nf, 256)), dim3(256), 0, st, (float*)f->d_hist[f->cur].ptr, nf, (float)f->hist_rescale);
+        hipLaunchKernelGGL(fir_hist_scale_kernel, dim3((unsigned)ceil_div(nf, 256)), dim3(256), 0, st, (float*)f->hist.current(), nf, (float)f->hist_rescale);
         GR4_LAUNCH_CHECK();
         f->hist_rescale = 1.0;
     }
@@ -577,9 +551,9 @@ int gr4hip_fir_create(gr4hip_fir_t** out, int dtype, const float* h_taps, size_t
     f->ntaps = ntaps;
     f->taps.assign(h_taps, h_taps + ntaps);
     f->user_taps = f->taps;
-    if (ntaps > f->hcap) f->hcap = bit_ceil_sz(ntaps); // time_domain_filter.hpp:38-42
+    if (ntaps > f->hcap) f->hcap = bit_ceil(ntaps); // time_domain_filter.hpp:38-42
     int rc = fir_upload_taps(f);
-    if (!rc) rc = fir_alloc_hist(f);
+    if (!rc) rc = f->hist.resize(f->hcap * f->S * sizeof(float));
     if (rc) { delete f; return rc; }
     *out = f;
     return GR4HIP_OK;
@@ -595,8 +569,8 @@ int gr4hip_fir_set_taps(gr4hip_fir_t* f, const float* h_taps, size_t ntaps) {
     int rc   = fir_apply_gain(f, f->folded); // every table derived from the taps is rebuilt on next use
     if (rc) return rc;
     if (ntaps > f->hcap) { // the reference replaces the HistoryBuffer (history is lost) only when it must grow
-        f->hcap = bit_ceil_sz(ntaps);
-        return fir_alloc_hist(f);
+        f->hcap = bit_ceil(ntaps);
+        return f->hist.resize(f->hcap * f->S * sizeof(float));
     }
     return GR4HIP_OK;
 }
@@ -607,7 +581,8 @@ int gr4hip_fir_reset(gr4hip_fir_t* f) {
     f->f32_products = f->f32_user;
     f->fd_ratio  = -1.f;
     f->pos = 0;
-    return fir_alloc_hist(f);
+    f->hist.reset();
+    return GR4HIP_OK;
 }
 
 int gr4hip_fir_set_prologue(gr4hip_fir_t* f, const gr4hip_ewise_t* prog) { return fir_set_hook(f, prog, true); }
@@ -650,13 +625,8 @@ static const size_t kBandMinDecim = env_size("GR4HIP_FIR_BAND_MIN_DECIM", 10); /
 
 // the handle moves past a span of n_in input samples: its next history is the span's last hcap samples (unless the launch that took it has written them)
 static int fir_advance(gr4hip_fir* f, const float* x, size_t n_in, hipStream_t st, bool hist_written) {
-    if (!hist_written) {
-        const long tot = (long)f->hcap * f->S;
-        hipLaunchKernelGGL(fir_hist_update_kernel, dim3((unsigned)ceil_div(tot, 256L)), dim3(256), 0, st, x, (const float*)f->d_hist[f->cur].ptr, (float*)f->d_hist[f->cur ^ 1].ptr, (long)n_in,
-                           (int)f->hcap, f->S);
-        GR4_LAUNCH_CHECK();
-    }
-    f->cur ^= 1;
+    if (hist_written) f->hist.flip();
+    else if (const int rc = f->hist.advance(x, n_in * f->S, f->hcap * f->S, sizeof(float), st)) return rc; // (the S interleaved floats of a sample as one flat run of floats)
     f->pos += (long)n_in;
     return GR4HIP_OK;
 }
@@ -678,7 +648,7 @@ struct FirCall {
     size_t          unj_from = SIZE_MAX;
     const float*    unj_hist = nullptr;
     bool            hist_written = false; // the launch that finished the span wrote the next history
-    float* next_hist() const { return (float*)f->d_hist[f->cur ^ 1].ptr; }
+    float* next_hist() const { return (float*)f->hist.next(); }
     int    took(bool wrote_hist) { done = n_in; hist_written = wrote_hist; return GR4HIP_OK; }
     int    took_unjudged(bool wrote_hist) { unj_from = done; unj_hist = hist; return took(wrote_hist); }
 };
@@ -1122,7 +1092,7 @@ static int fir_process_core(gr4hip_fir_t* f, const void* d_in, size_t n_in, void
                                               fir_path_generic};
     // hooks run in the register-window kernel and the band-form decimators only: the matrix-pipe and frequency-domain kernels are for plain filters
     FirCall c{f, static_cast<const float*>(d_in), static_cast<float*>(d_out), n_in, n_in / f->decim, as_stream(stream), hk, !hk.any, hk.any ? (int)GR4HIP_FIR_EXACT_F32 : f->algo,
-              (const float*)f->d_hist[f->cur].ptr};
+              (const float*)f->hist.current()};
     for (size_t p = 0; p < sizeof(kPaths) / sizeof(kPaths[0]); ++p) {
         if (c.done == n_in) break;
         const size_t before = c.done;
@@ -1246,7 +1216,7 @@ extern "C" int gr4hip_fir_iir_process(gr4hip_fir_t* f, gr4hip_iir_t* iir, const 
     float           ratio;
     if (guarded && fir_decim_fd_power_ratio(f->dfd, false, &ratio)) f->fd_ratio = ratio;
     if (guarded && f->guard_mode == GR4HIP_GUARD_DEFERRED && f->fd_ratio >= 0.f && f->fd_ratio < kDecimFdMinPowerRatio) { f->fd_blocked = f->f32_products = true; return two_launches(d_in, n_in, d_out); }
-    const float*     hist = (const float*)f->d_hist[f->cur].ptr;
+    const float*     hist = (const float*)f->hist.current();
     const DecimFdIir fuse{tab, nsec, st_in, st_out, warm};
     rc = fir_decim_fd_run(f->dfd, d_in, whole, hist, (int)f->hcap, d_out, st, guarded, &fuse);
     if (rc) return rc;
@@ -1271,9 +1241,9 @@ int gr4hip_internal_fir_set_guard_ratio(gr4hip_fir_t* f, double ratio) {
 }
 int gr4hip_internal_fir_load_history(gr4hip_fir_t* f, const float* d_last256, hipStream_t st) {
     GR4_REQUIRE(f && f->S == 2 && f->hcap <= 256, "fir_load_history: complex filter with <= 256 samples of history expected");
-    f->zero_hist    = false; // (what was pending for the history is superseded; the taps go up with the next call)
+    f->hist.keep(); // (what was pending for the history is superseded; the taps go up with the next call)
     f->hist_rescale = 1.0;
-    GR4_HIP_TRY(hipMemcpyAsync(f->d_hist[f->cur].ptr, d_last256 + (256 - f->hcap) * 2, f->hcap * 2 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    GR4_HIP_TRY(hipMemcpyAsync(f->hist.current(), d_last256 + (256 - f->hcap) * 2, f->hcap * 2 * sizeof(float), hipMemcpyDeviceToDevice, st));
     return GR4HIP_OK;
 }
 

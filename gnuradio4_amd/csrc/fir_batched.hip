@@ -10,6 +10,7 @@
 // is one conflict-free ds_read_b32 per MFMA from the staged (18/16-padded) input segment, D leaves as fully coalesced float4 stores.
 // Bound: MFMA f32 (157.3 TFLOP/s): 2*(Kp+16) flop per output sample.
 #include "common.hpp"
+#include "history.hpp"
 #include "fir_exact.hpp"
 #include "buffer_ops.hpp"
 
@@ -486,8 +487,8 @@ int  fir_f16_launch(int KS, const float* x, long n, const float* hist, int Kh, c
 struct gr4hip_fir_batched {
     size_t       nch = 0, ntaps = 0;
     int          KS = 0, Kp = 0;
-    DeviceBuffer d_afrag, d_hist[2];
-    int          cur = 0;
+    DeviceBuffer   d_afrag;
+    CarriedHistory hist; // [nch][Kp] floats; the carry is this file's own (rows of in_stride samples)
     DeviceBuffer d_bfrag; // > 64 taps: per-channel three-term bf16 tap fragments (fir_bf16.hip)
     int          bfKS = 0;
     DeviceBuffer d_hfrag; // > 32 taps: per-channel two-term f16 tables (fir_f16.hip) -- the default on long spans
@@ -496,7 +497,6 @@ struct gr4hip_fir_batched {
     DeviceBuffer d_gthr;           // per channel (sum b^2) / 128 (fir.hip, kGuardSegmentRatio): the threshold fir_judge_kernel holds the bf16 path's segments against
     unsigned     last_paths = 0;   // which kernel served the last call and whether a second evaluation was enqueued (gr4hip_internal_fir_batched_last_paths)
     size_t       last_nsegs = 0;   // segments per channel the last call left marks for in d_flags (0: none were made)
-    bool         zero_hist = true; // the stream rule (common.hpp): create / reset note it, the next call zeroes d_hist[cur] on its own stream
 };
 
 extern "C" {
@@ -540,8 +540,7 @@ int gr4hip_fir_batched_create(gr4hip_fir_batched_t** out, size_t nchannels, cons
         rc = f->d_gthr.ensure(nchannels * sizeof(float));
         if (!rc) { hipError_t e = upload_fresh(f->d_gthr.ptr, g.data(), nchannels * sizeof(float)); if (e != hipSuccess) { set_error("fir_batched: upload failed: %s", hipGetErrorString(e)); rc = GR4HIP_RUNTIME_ERROR; } }
     }
-    for (int k = 0; k < 2 && !rc; ++k) rc = f->d_hist[k].ensure(nchannels * f->Kp * sizeof(float));
-    if (!rc) rc = gr4hip_fir_batched_reset(f);
+    if (!rc) rc = f->hist.resize(nchannels * f->Kp * sizeof(float));
     if (rc) { delete f; return rc; }
     *out = f;
     return GR4HIP_OK;
@@ -549,7 +548,7 @@ int gr4hip_fir_batched_create(gr4hip_fir_batched_t** out, size_t nchannels, cons
 
 int gr4hip_fir_batched_reset(gr4hip_fir_batched_t* f) {
     GR4_REQUIRE(f, "fir_batched_reset: null handle");
-    f->zero_hist = true; // (a launch still in flight on the caller's stream may be writing the other half of the pair: the zeroing goes behind it, on the next call's stream)
+    f->hist.reset(); // (a launch still in flight on the caller's stream may be writing the other half of the pair: the zeroing goes behind it, on the next call's stream)
     return GR4HIP_OK;
 }
 
@@ -561,11 +560,8 @@ int gr4hip_fir_batched_process(gr4hip_fir_batched_t* f, const float* d_in, size_
     GR4_REQUIRE(d_in && d_out && in_stride >= n && out_stride >= n, "fir_batched_process: null pointer or stride shorter than n");
     GR4_REQUIRE(((uintptr_t)d_out % 16 == 0) && (out_stride % 4 == 0), "fir_batched_process: output must be 16-byte aligned with a stride multiple of 4");
     hipStream_t st = as_stream(stream);
-    if (f->zero_hist) {
-        GR4_HIP_TRY(hipMemsetAsync(f->d_hist[f->cur].ptr, 0, f->nch * f->Kp * sizeof(float), st));
-        f->zero_hist = false;
-    }
-    const float *hist = (const float*)f->d_hist[f->cur].ptr, *af = (const float*)f->d_afrag.ptr;
+    if (const int rc = f->hist.on(st)) return rc;
+    const float *hist = (const float*)f->hist.current(), *af = (const float*)f->d_afrag.ptr;
     const long nsegs = (long)ceil_div(n, (size_t)4096);
     int        rc;
     if (f->hfKS && n >= 32768 && (uintptr_t)d_in % 16 == 0 && in_stride % 4 == 0 && !dev_switch(kDevFirNoBf16x3) && !dev_switch(kDevFirNoF16x2)) { // two-term f16 form (fir_f16.hip): same history layout
@@ -593,9 +589,9 @@ int gr4hip_fir_batched_process(gr4hip_fir_batched_t* f, const float* d_in, size_
     }
     if (rc) return rc;
     hipLaunchKernelGGL(fir_batched_hist_kernel, dim3((unsigned)ceil_div(f->Kp, 64), (unsigned)f->nch), dim3(64), 0, st, d_in, (long)in_stride, hist,
-                       (float*)f->d_hist[f->cur ^ 1].ptr, (long)n, f->Kp);
+                       (float*)f->hist.next(), (long)n, f->Kp);
     GR4_LAUNCH_CHECK();
-    f->cur ^= 1;
+    f->hist.flip();
     return GR4HIP_OK;
 }
 

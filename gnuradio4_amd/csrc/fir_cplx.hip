@@ -19,6 +19,7 @@
 //  * cfir_exact_kernel: the guard's second evaluation (include/gr4hip.h, "ONE guard"): float64 sum in ascending k, rounded once, for the segments the main
 //    kernels marked -- D P_y < (sum |b|^2 / 128) P_x, or a non-finite sample in what the segment read -- behind the launch on the same stream, no host wait.
 #include "common.hpp"
+#include "history.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -185,12 +186,6 @@ __global__ __launch_bounds__(256) void cfir_exact_kernel(const float2* __restric
     }
 }
 
-__global__ void cfir_hist_kernel(const float2* __restrict__ x, long n_in, const float2* __restrict__ hold, float2* __restrict__ hnew, int hcap) {
-    const int h = blockIdx.x * blockDim.x + threadIdx.x;
-    if (h >= hcap) return;
-    hnew[h] = cf_sample(x, hold, hcap, n_in - hcap + h, n_in);
-}
-
 // g_p[j] of the band form (0 outside -1 .. 2K - 1)
 static float cf_g(const float* b, long K, int p, long j) {
     if (j < -1 || j > 2 * K - 1) return 0.f;
@@ -217,16 +212,15 @@ using namespace gr4;
 struct gr4hip_cfir {
     size_t             ntaps = 0, D = 1, hcap = 32;
     std::vector<float> taps, tabk_host; // the host images the stream-ordered uploads read: interleaved taps, the kernel-order tap operand
-    DeviceBuffer       d_taps, d_tabk, d_hist[2], d_flags, d_count;
-    int                cur = 0, n_steps = 0, guard_mode = GR4HIP_GUARD_STRICT;
+    DeviceBuffer       d_taps, d_tabk, d_flags, d_count;
+    CarriedHistory     hist; // hcap complex samples
+    int                n_steps = 0, guard_mode = GR4HIP_GUARD_STRICT;
     long               r_min = 0;
     double             tap_power = 0.0;
-    bool               taps_dirty = false, zero_hist = true, counted = false;
+    bool               taps_dirty = false, counted = false;
     unsigned           last_paths = 0; // bit 0: matrix-pipe kernel, bit 1: direct kernel, bit 2: exact kernel enqueued
     unsigned long long marked_host = 0;
 };
-
-static size_t cf_bit_ceil(size_t v) { size_t p = 1; while (p < v) p <<= 1; return p; }
 
 static int cf_check_taps(const char* who, const float* h_taps, size_t ntaps, size_t decim) {
     GR4_REQUIRE(h_taps, "%s: null taps", who);
@@ -255,25 +249,13 @@ static int cf_upload(gr4hip_cfir* f) {
     f->taps_dirty = true; // uploaded by cf_state_on, on the stream of the next call
     return GR4HIP_OK;
 }
-static int cf_alloc_hist(gr4hip_cfir* f) {
-    for (int k = 0; k < 2; ++k) {
-        int rc = f->d_hist[k].ensure(f->hcap * sizeof(float2));
-        if (rc) return rc;
-    }
-    f->zero_hist = true; // zeroed by cf_state_on, on the stream of the next call
-    return GR4HIP_OK;
-}
 static int cf_state_on(gr4hip_cfir* f, hipStream_t st) {
     if (f->taps_dirty) {
         GR4_HIP_TRY(hipMemcpyAsync(f->d_taps.ptr, f->taps.data(), f->taps.size() * sizeof(float), hipMemcpyHostToDevice, st));
         GR4_HIP_TRY(hipMemcpyAsync(f->d_tabk.ptr, f->tabk_host.data(), f->tabk_host.size() * sizeof(float), hipMemcpyHostToDevice, st));
         f->taps_dirty = false;
     }
-    if (f->zero_hist) {
-        GR4_HIP_TRY(hipMemsetAsync(f->d_hist[f->cur].ptr, 0, f->hcap * sizeof(float2), st));
-        f->zero_hist = false;
-    }
-    return GR4HIP_OK;
+    return f->hist.on(st);
 }
 
 // row length (chunks), row stride (floats) and LDS bytes of the matrix-pipe kernel
@@ -317,9 +299,9 @@ int gr4hip_cfir_create(gr4hip_cfir_t** out, const float* h_taps, size_t ntaps, s
     f->D     = decim;
     f->ntaps = ntaps;
     f->taps.assign(h_taps, h_taps + 2 * ntaps);
-    f->hcap = std::max<size_t>(32, cf_bit_ceil(ntaps));
+    f->hcap = std::max<size_t>(32, bit_ceil(ntaps));
     int rc  = cf_upload(f);
-    if (!rc) rc = cf_alloc_hist(f);
+    if (!rc) rc = f->hist.resize(f->hcap * sizeof(float2));
     if (!rc) rc = f->d_count.ensure(sizeof(unsigned long long));
     if (rc) { delete f; return rc; }
     *out = f;
@@ -333,15 +315,15 @@ int gr4hip_cfir_set_taps(gr4hip_cfir_t* f, const float* h_taps, size_t ntaps) {
     f->ntaps = ntaps;
     if (const int rc = cf_upload(f)) return rc;
     if (ntaps > f->hcap) { // like fir_filter::settingsChanged: the history is replaced (lost) only when it must grow
-        f->hcap = cf_bit_ceil(ntaps);
-        return cf_alloc_hist(f);
+        f->hcap = bit_ceil(ntaps);
+        return f->hist.resize(f->hcap * sizeof(float2));
     }
     return GR4HIP_OK;
 }
 
 int gr4hip_cfir_reset(gr4hip_cfir_t* f) {
     GR4_REQUIRE(f, "cfir_reset: null handle");
-    f->zero_hist = true; // cf_state_on zeroes the history on the stream of the next call
+    f->hist.reset(); // cf_state_on zeroes the history on the stream of the next call
     return GR4HIP_OK;
 }
 
@@ -379,7 +361,7 @@ int gr4hip_cfir_process(gr4hip_cfir_t* f, const void* d_in, size_t n_in, void* d
     GR4_HIP_TRY(hipMemsetAsync(f->d_count.ptr, 0, sizeof(unsigned long long), st));
     const float2*       x     = static_cast<const float2*>(d_in);
     float2*             y     = static_cast<float2*>(d_out);
-    const float2*       hist  = static_cast<const float2*>(f->d_hist[f->cur].ptr);
+    const float2*       hist  = static_cast<const float2*>(f->hist.current());
     const float2*       taps  = static_cast<const float2*>(f->d_taps.ptr);
     unsigned char*      flags = guarded ? static_cast<unsigned char*>(f->d_flags.ptr) : nullptr;
     unsigned long long* count = static_cast<unsigned long long*>(f->d_count.ptr);
@@ -413,9 +395,7 @@ int gr4hip_cfir_process(gr4hip_cfir_t* f, const void* d_in, size_t n_in, void* d
         GR4_LAUNCH_CHECK();
         f->last_paths |= 4u;
     }
-    hipLaunchKernelGGL(cfir_hist_kernel, dim3((unsigned)ceil_div(f->hcap, (size_t)256)), dim3(256), 0, st, x, (long)n_in, hist, static_cast<float2*>(f->d_hist[f->cur ^ 1].ptr), (int)f->hcap);
-    GR4_LAUNCH_CHECK();
-    f->cur ^= 1;
+    if (const int rc = f->hist.advance(x, n_in, f->hcap, (int)sizeof(float2), st)) return rc;
     f->counted = true;
     return GR4HIP_OK;
 }

@@ -15,6 +15,7 @@
 //    HBM at short ones ((4 + 4 L) B per real input sample).  Factors it is not instantiated for take one output per lane straight from the L2.
 // History: the last Kp - 1 input samples (capacity max(32, bit_ceil(Kp)) like HistoryBuffer, :36-42).
 #include "common.hpp"
+#include "history.hpp"
 #include "buffer_ops.hpp"
 
 #include <algorithm>
@@ -247,14 +248,6 @@ __global__ __launch_bounds__(256) void fir_interp_mfma_kernel(const float* __res
     }
 }
 
-template <int S>
-__global__ void fir_interp_hist_kernel(const typename ip_vec<S>::type* __restrict__ x, long n_in, const typename ip_vec<S>::type* __restrict__ hold, typename ip_vec<S>::type* __restrict__ hnew, int hcap) {
-    const int h = blockIdx.x * blockDim.x + threadIdx.x;
-    if (h >= hcap) return;
-    const long pos = n_in - hcap + h; // stream position relative to this call's first sample
-    hnew[h] = pos >= 0 ? x[pos] : (pos >= -(long)hcap ? hold[hcap + pos] : typename ip_vec<S>::type{});
-}
-
 } // namespace gr4
 
 using namespace gr4;
@@ -263,17 +256,16 @@ struct gr4hip_fir_interp {
     int                dtype = GR4HIP_F32, S = 1;
     size_t             ntaps = 0, L = 1, Kp = 0, hcap = 32;
     std::vector<float> taps;
-    DeviceBuffer       d_taps, d_hist[2], d_row; // d_row: zero-padded natural-order tap row of the matrix-pipe kernel
-    int                cur = 0, KS = 0, G = 1;   // KS = 0: no matrix-pipe form for this (L, K)
+    DeviceBuffer       d_taps, d_row; // d_row: zero-padded natural-order tap row of the matrix-pipe kernel
+    CarriedHistory     hist;          // hcap samples
+    int                KS = 0, G = 1; // KS = 0: no matrix-pipe form for this (L, K)
     // the stream rule (common.hpp): create / reset / set_taps only note what the device state has to become; ip_state_on() enqueues it on the stream of the next call
     std::vector<float> t_host, row_host; // images of d_taps / d_row as ip_upload laid them out
-    bool               taps_dirty = false, zero_hist = true;
+    bool               taps_dirty = false;
 };
 
 constexpr size_t kIpMfmaMinOut = 32768; // shorter spans: the register-window kernel (fewer, smaller workgroups)
 static bool ip_env_no_mfma() { static const bool v = std::getenv("GR4HIP_INTERP_NO_MFMA") != nullptr; return v; } // developer switch: the tests compare the two kernels
-
-static size_t ip_bit_ceil(size_t v) { size_t p = 1; while (p < v) p <<= 1; return p; }
 
 static int ip_upload(gr4hip_fir_interp* f) {
     f->Kp = ceil_div(f->ntaps, f->L);
@@ -313,7 +305,7 @@ static int ip_mfma_launch(const gr4hip_fir_interp* f, const void* x, void* y, lo
     const int     spw = (int)std::clamp<long>(nseg / 2048, 1, 4); // >= 2048 workgroups (8 per CU) before a workgroup takes a second segment
     auto          kern = fir_interp_mfma_kernel<G, S>;
     if (lds > 48 * 1024) GR4_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(nseg, (long)spw), G == 1 ? (unsigned)ceil_div(f->L, (size_t)16) : 1u), dim3(256), lds, st, static_cast<const float*>(x), static_cast<const float*>(f->d_hist[f->cur].ptr), (int)f->hcap,
+    hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(nseg, (long)spw), G == 1 ? (unsigned)ceil_div(f->L, (size_t)16) : 1u), dim3(256), lds, st, static_cast<const float*>(x), static_cast<const float*>(f->hist.current()), (int)f->hcap,
                        static_cast<const float*>(f->d_row.ptr), f->KS, static_cast<float*>(y), n_in, spw, new_hist, (int)f->L);
     GR4_LAUNCH_CHECK();
     return GR4HIP_OK;
@@ -327,15 +319,6 @@ static int ip_mfma_dispatch(const gr4hip_fir_interp* f, const void* x, void* y, 
     default: return ip_mfma_launch<1, S>(f, x, y, n_in, st, new_hist);
     }
 }
-static int ip_alloc_hist(gr4hip_fir_interp* f) {
-    const size_t bytes = f->hcap * f->S * sizeof(float);
-    for (int k = 0; k < 2; ++k) {
-        int rc = f->d_hist[k].ensure(bytes);
-        if (rc) return rc;
-    }
-    f->zero_hist = true; // zeroed by ip_state_on, on the stream of the next call (a launch still in flight may be writing either half of the pair)
-    return GR4HIP_OK;
-}
 // pending tap upload / zeroing of the carried history, onto the stream of the call about to be enqueued: behind this handle's earlier launches on it, in front of the next
 static int ip_state_on(gr4hip_fir_interp* f, hipStream_t st) {
     if (f->taps_dirty) {
@@ -343,11 +326,7 @@ static int ip_state_on(gr4hip_fir_interp* f, hipStream_t st) {
         if (!f->row_host.empty()) GR4_HIP_TRY(hipMemcpyAsync(f->d_row.ptr, f->row_host.data(), f->row_host.size() * sizeof(float), hipMemcpyHostToDevice, st));
         f->taps_dirty = false;
     }
-    if (f->zero_hist) {
-        GR4_HIP_TRY(hipMemsetAsync(f->d_hist[f->cur].ptr, 0, f->hcap * f->S * sizeof(float), st));
-        f->zero_hist = false;
-    }
-    return GR4HIP_OK;
+    return f->hist.on(st);
 }
 
 template <int L, int R, int S>
@@ -358,7 +337,7 @@ static int ip_launch(const gr4hip_fir_interp* f, const void* x, void* y, long n_
     auto kern = fir_interp_kernel<L, R, S>;
     if (lds > 48 * 1024) GR4_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const long grid = ceil_div(n_in, (long)kIpBS * R);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kIpBS), lds, st, static_cast<const T*>(x), static_cast<const T*>(f->d_hist[f->cur].ptr), (int)f->hcap,
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kIpBS), lds, st, static_cast<const T*>(x), static_cast<const T*>(f->hist.current()), (int)f->hcap,
                        static_cast<const float*>(f->d_taps.ptr), (int)f->Kp, static_cast<T*>(y), n_in);
     GR4_LAUNCH_CHECK();
     return GR4HIP_OK;
@@ -379,7 +358,7 @@ static int ip_dispatch(const gr4hip_fir_interp* f, const void* x, void* y, long 
     }
     if (rc != GR4HIP_UNSUPPORTED) return rc;
     const unsigned grid = (unsigned)std::min<size_t>(ceil_div((size_t)n_in * f->L, (size_t)256), (size_t)1 << 16);
-    hipLaunchKernelGGL(fir_interp_generic_kernel<S>, dim3(grid), dim3(256), 0, st, static_cast<const T*>(x), static_cast<const T*>(f->d_hist[f->cur].ptr), (int)f->hcap,
+    hipLaunchKernelGGL(fir_interp_generic_kernel<S>, dim3(grid), dim3(256), 0, st, static_cast<const T*>(x), static_cast<const T*>(f->hist.current()), (int)f->hcap,
                        static_cast<const float*>(f->d_taps.ptr), (int)f->Kp, (int)f->L, static_cast<T*>(y), n_in);
     GR4_LAUNCH_CHECK();
     return GR4HIP_OK;
@@ -400,8 +379,8 @@ int gr4hip_fir_interp_create(gr4hip_fir_interp_t** out, int dtype, const float* 
     f->ntaps = ntaps;
     f->taps.assign(h_taps, h_taps + ntaps);
     int rc = ip_upload(f);
-    if (f->Kp > f->hcap) f->hcap = ip_bit_ceil(f->Kp);
-    if (!rc) rc = ip_alloc_hist(f);
+    if (f->Kp > f->hcap) f->hcap = bit_ceil(f->Kp);
+    if (!rc) rc = f->hist.resize(f->hcap * f->S * sizeof(float));
     if (rc) { delete f; return rc; }
     *out = f;
     return GR4HIP_OK;
@@ -414,15 +393,16 @@ int gr4hip_fir_interp_set_taps(gr4hip_fir_interp_t* f, const float* h_taps, size
     int rc   = ip_upload(f);
     if (rc) return rc;
     if (f->Kp > f->hcap) { // like fir_filter::settingsChanged: the history is replaced (lost) only when it must grow
-        f->hcap = ip_bit_ceil(f->Kp);
-        return ip_alloc_hist(f);
+        f->hcap = bit_ceil(f->Kp);
+        return f->hist.resize(f->hcap * f->S * sizeof(float));
     }
     return GR4HIP_OK;
 }
 
 int gr4hip_fir_interp_reset(gr4hip_fir_interp_t* f) {
     GR4_REQUIRE(f, "fir_interp_reset: null handle");
-    return ip_alloc_hist(f);
+    f->hist.reset();
+    return GR4HIP_OK;
 }
 
 int gr4hip_fir_interp_process(gr4hip_fir_interp_t* f, const void* d_in, size_t n_in, void* d_out, size_t* n_out_p, gr4hip_stream_t stream) {
@@ -433,20 +413,15 @@ int gr4hip_fir_interp_process(gr4hip_fir_interp_t* f, const void* d_in, size_t n
     hipStream_t st = as_stream(stream);
     if (const int rc = ip_state_on(f, st)) return rc;
     if (f->KS > 0 && n_in * f->L >= kIpMfmaMinOut && (uintptr_t)d_out % 16 == 0 && (uintptr_t)d_in % (4 * f->S) == 0 && !ip_env_no_mfma()) { // matrix-pipe form; writes the next history itself
-        float* nh = static_cast<float*>(f->d_hist[f->cur ^ 1].ptr);
+        float* nh = static_cast<float*>(f->hist.next());
         int    rc = f->S == 1 ? ip_mfma_dispatch<1>(f, d_in, d_out, (long)n_in, st, nh) : ip_mfma_dispatch<2>(f, d_in, d_out, (long)n_in, st, nh);
         if (rc) return rc;
-        f->cur ^= 1;
+        f->hist.flip();
         return GR4HIP_OK;
     }
     int rc = f->S == 1 ? ip_dispatch<1>(f, d_in, d_out, (long)n_in, st) : ip_dispatch<2>(f, d_in, d_out, (long)n_in, st);
     if (rc) return rc;
-    const unsigned hg = (unsigned)ceil_div(f->hcap, (size_t)256);
-    if (f->S == 1) hipLaunchKernelGGL(fir_interp_hist_kernel<1>, dim3(hg), dim3(256), 0, st, static_cast<const float*>(d_in), (long)n_in, static_cast<const float*>(f->d_hist[f->cur].ptr), static_cast<float*>(f->d_hist[f->cur ^ 1].ptr), (int)f->hcap);
-    else hipLaunchKernelGGL(fir_interp_hist_kernel<2>, dim3(hg), dim3(256), 0, st, static_cast<const float2*>(d_in), (long)n_in, static_cast<const float2*>(f->d_hist[f->cur].ptr), static_cast<float2*>(f->d_hist[f->cur ^ 1].ptr), (int)f->hcap);
-    GR4_LAUNCH_CHECK();
-    f->cur ^= 1;
-    return GR4HIP_OK;
+    return f->hist.advance(d_in, n_in, f->hcap, f->S * (int)sizeof(float), st);
 }
 
 int gr4hip_fir_interp_destroy(gr4hip_fir_interp_t* f) {

@@ -18,6 +18,7 @@
 // per output) at short branches, LDS reads at long ones ((1 + 1 / kRsR) reads per multiply-add step in the gather form, 2 / kRsR in the window form).
 // A single cycle whose span does not fit in LDS (M + Kp - 1 samples past 80 KiB) takes fir_resamp_direct_kernel: one output per lane straight from the L2.
 #include "common.hpp"
+#include "history.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -149,14 +150,6 @@ __global__ void fir_resamp_direct_kernel(const typename rs_vec<S>::type* __restr
     }
 }
 
-// the last hcap stream positions into the other half of the pair; also right for a call shorter than the history
-template <int S>
-__global__ void fir_resamp_hist_kernel(const typename rs_vec<S>::type* __restrict__ x, long n_in, const typename rs_vec<S>::type* __restrict__ hold, typename rs_vec<S>::type* __restrict__ hnew, int hcap) {
-    const int h = blockIdx.x * blockDim.x + threadIdx.x;
-    if (h >= hcap) return;
-    hnew[h] = rs_sample(x, hold, hcap, n_in - hcap + h);
-}
-
 } // namespace gr4
 
 using namespace gr4;
@@ -168,8 +161,8 @@ struct gr4hip_resamp {
     int                dtype = GR4HIP_F32, S = 1;
     size_t             ntaps = 0, L = 1, M = 1, Kp = 0, hcap = 32;
     std::vector<float> taps;
-    DeviceBuffer       d_taps, d_slots, d_hist[2];
-    int                cur = 0;
+    DeviceBuffer       d_taps, d_slots;
+    CarriedHistory     hist; // hcap samples
     // launch shape of the main kernel, fixed by (L, M, Kp, S): rs_plan
     int      lanes = kRsBS, G = 1, cc = 0; // cc = 0: fir_resamp_direct_kernel
     bool     taps_lds = false;
@@ -178,10 +171,8 @@ struct gr4hip_resamp {
     // the stream rule (common.hpp): create / reset / set_taps only note what the device state has to become; rs_state_on() enqueues it on the stream of the next call
     std::vector<float> t_host; // image of d_taps: [Kp][L]
     std::vector<int>   o_host; // image of d_slots: [L]
-    bool               taps_dirty = false, zero_hist = true;
+    bool               taps_dirty = false;
 };
-
-static size_t rs_bit_ceil(size_t v) { size_t p = 1; while (p < v) p <<= 1; return p; }
 
 static int rs_check_taps(const char* who, const float* h_taps, size_t ntaps) {
     GR4_REQUIRE(h_taps, "%s: null taps", who);
@@ -228,25 +219,13 @@ static int rs_upload(gr4hip_resamp* f) {
     rs_plan(f);
     return GR4HIP_OK;
 }
-static int rs_alloc_hist(gr4hip_resamp* f) {
-    for (int k = 0; k < 2; ++k) {
-        int rc = f->d_hist[k].ensure(f->hcap * f->S * sizeof(float));
-        if (rc) return rc;
-    }
-    f->zero_hist = true; // zeroed by rs_state_on, on the stream of the next call (a launch still in flight may be writing either half of the pair)
-    return GR4HIP_OK;
-}
 static int rs_state_on(gr4hip_resamp* f, hipStream_t st) {
     if (f->taps_dirty) {
         GR4_HIP_TRY(hipMemcpyAsync(f->d_taps.ptr, f->t_host.data(), f->t_host.size() * sizeof(float), hipMemcpyHostToDevice, st));
         GR4_HIP_TRY(hipMemcpyAsync(f->d_slots.ptr, f->o_host.data(), f->o_host.size() * sizeof(int), hipMemcpyHostToDevice, st));
         f->taps_dirty = false;
     }
-    if (f->zero_hist) {
-        GR4_HIP_TRY(hipMemsetAsync(f->d_hist[f->cur].ptr, 0, f->hcap * f->S * sizeof(float), st));
-        f->zero_hist = false;
-    }
-    return GR4HIP_OK;
+    return f->hist.on(st);
 }
 
 template <int S>
@@ -254,7 +233,7 @@ static int rs_launch(gr4hip_resamp* f, const void* d_in, void* d_out, long n_in,
     using T           = typename rs_vec<S>::type;
     const T*     x    = static_cast<const T*>(d_in);
     T*           y    = static_cast<T*>(d_out);
-    const T*     hist = static_cast<const T*>(f->d_hist[f->cur].ptr);
+    const T*     hist = static_cast<const T*>(f->hist.current());
     const float* taps = static_cast<const float*>(f->d_taps.ptr);
     const int*   so   = static_cast<const int*>(f->d_slots.ptr);
     const long   n_cyc = n_in / (long)f->M;
@@ -285,10 +264,7 @@ static int rs_launch(gr4hip_resamp* f, const void* d_in, void* d_out, long n_in,
         GR4_LAUNCH_CHECK();
         f->last_paths = (f->taps_lds ? kRsPathLdsTaps : kRsPathGlobalTaps) | (MW ? kRsPathWindow : 0u);
     }
-    hipLaunchKernelGGL(fir_resamp_hist_kernel<S>, dim3((unsigned)ceil_div(f->hcap, (size_t)256)), dim3(256), 0, st, x, n_in, hist, static_cast<T*>(f->d_hist[f->cur ^ 1].ptr), (int)f->hcap);
-    GR4_LAUNCH_CHECK();
-    f->cur ^= 1;
-    return GR4HIP_OK;
+    return f->hist.advance(x, (size_t)n_in, f->hcap, (int)sizeof(T), st);
 }
 
 extern "C" {
@@ -339,8 +315,8 @@ int gr4hip_resamp_create(gr4hip_resamp_t** out, int dtype, const float* h_taps, 
     f->ntaps = ntaps;
     f->taps.assign(h_taps, h_taps + ntaps);
     int rc  = rs_upload(f);
-    f->hcap = std::max<size_t>(32, rs_bit_ceil(f->Kp));
-    if (!rc) rc = rs_alloc_hist(f);
+    f->hcap = std::max<size_t>(32, bit_ceil(f->Kp));
+    if (!rc) rc = f->hist.resize(f->hcap * f->S * sizeof(float));
     if (rc) { delete f; return rc; }
     *out = f;
     return GR4HIP_OK;
@@ -353,15 +329,15 @@ int gr4hip_resamp_set_taps(gr4hip_resamp_t* f, const float* h_taps, size_t ntaps
     f->ntaps = ntaps;
     if (const int rc = rs_upload(f)) return rc;
     if (f->Kp > f->hcap) { // like fir_filter::settingsChanged: the history is replaced (lost) only when it must grow
-        f->hcap = rs_bit_ceil(f->Kp);
-        return rs_alloc_hist(f);
+        f->hcap = bit_ceil(f->Kp);
+        return f->hist.resize(f->hcap * f->S * sizeof(float));
     }
     return GR4HIP_OK;
 }
 
 int gr4hip_resamp_reset(gr4hip_resamp_t* f) {
     GR4_REQUIRE(f, "resamp_reset: null handle");
-    f->zero_hist = true; // rs_state_on zeroes the history on the stream of the next call
+    f->hist.reset(); // rs_state_on zeroes the history on the stream of the next call
     return GR4HIP_OK;
 }
 

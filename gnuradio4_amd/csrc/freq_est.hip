@@ -301,7 +301,7 @@ static int fe_geometry(int method, const gr4hip_freqest_params* p, FeGeom& g) {
     }
     const size_t m = std::max(p->min_fft_size, (size_t)per);
     if (m > kFeMaxWindow) { set_error("freqest: FFT size beyond 2^20"); return GR4HIP_UNSUPPORTED; }
-    const size_t N = m <= 1 ? 1 : size_t(1) << ilog2(m); // std::bit_ceil
+    const size_t N = bit_ceil(m);
     if (N < 4) { set_error("freqest: FFT size %zu < 4", N); return GR4HIP_UNSUPPORTED; }
     const float  scaled = (float)(N / 2) * 2.f; // (:298-300)
     const size_t half = N / 2;

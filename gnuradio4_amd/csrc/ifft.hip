@@ -14,6 +14,7 @@
 #define GR4_BUF_LOAD_AUX 2
 #endif
 #include "ifft_kernels.hpp"
+#include "history.hpp"
 
 #include <algorithm>
 
@@ -84,7 +85,6 @@ __global__ __launch_bounds__(256) void pfb_synth_combine_kernel(const float2* __
 
 int fft_build_plan(size_t N, FftPlanDev* plan);                                                                             // fft.hip
 int fft_upload_twiddles(size_t N, DeviceBuffer* buf);                                                                       // fft.hip
-int pfb_hist_launch(const float2* x, long n_in, const float2* old_hist, float2* new_hist, long len, hipStream_t st);      // pfb.hip
 
 // one launch: n_frames frames of plan.N bins at d_in -> samples at d_out
 static int ifft_launch(const FftPlanDev& plan, bool c2r, const float* d_in, void* d_out, const float* d_window, float scale, const float2* d_tw, long n_frames, hipStream_t st) {
@@ -125,9 +125,9 @@ struct gr4hip_pfb_synth {
     float              scale = 1.f;
     std::vector<float> taps; // the host image the stream-ordered upload reads
     FftPlanDev         plan{};
-    DeviceBuffer       d_taps, d_tw, d_hist[2], d_scratch;
-    int                cur = 0;
-    bool               taps_dirty = false, zero_hist = true;
+    DeviceBuffer       d_taps, d_tw, d_scratch;
+    CarriedHistory     hist; // the last P - 1 transformed frames: (P - 1) N complex samples (none for P = 1)
+    bool               taps_dirty = false;
 };
 
 // the size rules of both handles: INVALID_ARGUMENT for what no transform has, UNSUPPORTED for what these kernels do not run
@@ -229,7 +229,7 @@ int gr4hip_pfb_synth_create(gr4hip_pfb_synth_t** out, size_t n_channels, size_t 
     if (!rc) rc = fft_upload_twiddles(f->N, &f->d_tw);
     if (!rc) rc = f->d_taps.ensure(L * sizeof(float));
     if (!rc && upload_fresh(f->d_taps.ptr, f->taps.data(), L * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); set_error("pfb_synth: prototype upload failed"); rc = GR4HIP_RUNTIME_ERROR; }
-    for (int k = 0; k < 2 && !rc && f->P > 1; ++k) rc = f->d_hist[k].ensure((f->P - 1) * f->N * sizeof(float2));
+    if (!rc) rc = f->hist.resize((f->P - 1) * f->N * sizeof(float2));
     if (rc) { delete f; return rc; }
     *out = f;
     return GR4HIP_OK;
@@ -247,7 +247,7 @@ int gr4hip_pfb_synth_set_taps(gr4hip_pfb_synth_t* f, const float* h_taps, size_t
 
 int gr4hip_pfb_synth_reset(gr4hip_pfb_synth_t* f) {
     GR4_REQUIRE(f, "pfb_synth_reset: null handle");
-    f->zero_hist = true; // zeroed on the stream of the next call
+    f->hist.reset(); // zeroed on the stream of the next call
     return GR4HIP_OK;
 }
 
@@ -262,15 +262,9 @@ int gr4hip_pfb_synth_process(gr4hip_pfb_synth_t* f, const void* d_spectra, size_
         GR4_HIP_TRY(hipMemcpyAsync(f->d_taps.ptr, f->taps.data(), f->taps.size() * sizeof(float), hipMemcpyHostToDevice, st));
         f->taps_dirty = false;
     }
-    if (P == 1) { // one tap per channel is a synthesis window: the transform's own sink applies it, nothing is carried
-        f->zero_hist = false;
+    if (const int rc = f->hist.on(st)) return rc;
+    if (P == 1) // one tap per channel is a synthesis window: the transform's own sink applies it, nothing is carried
         return ifft_launch(f->plan, false, static_cast<const float*>(d_spectra), d_out, static_cast<const float*>(f->d_taps.ptr), f->scale, tw, (long)n_frames, st);
-    }
-    const size_t hlen = (P - 1) * N;
-    if (f->zero_hist) {
-        GR4_HIP_TRY(hipMemsetAsync(f->d_hist[f->cur].ptr, 0, hlen * sizeof(float2), st));
-        f->zero_hist = false;
-    }
     // the call in pieces through the bounded scratch: transform, sums, history of the next piece.  A piece is a cut like any other.
     const size_t piece = std::max<size_t>(1, kSynthScratchBytes / (N * sizeof(float2)));
     if (const int rc = f->d_scratch.ensure(std::min(piece, n_frames) * N * sizeof(float2))) return rc;
@@ -281,7 +275,7 @@ int gr4hip_pfb_synth_process(gr4hip_pfb_synth_t* f, const void* d_spectra, size_
         const auto*  in = static_cast<const float*>(d_spectra) + done * N * 2;
         float2*      y  = static_cast<float2*>(d_out) + done * N;
         if (const int rc = ifft_launch(f->plan, false, in, V, nullptr, f->scale, tw, (long)n, st)) return rc;
-        const auto* hist = static_cast<const float2*>(f->d_hist[f->cur].ptr);
+        const auto* hist = static_cast<const float2*>(f->hist.current());
         const auto* g    = static_cast<const float*>(f->d_taps.ptr);
         if ((uintptr_t)y % 16 == 0) {
             const size_t lanes = n * N / 2;
@@ -291,8 +285,7 @@ int gr4hip_pfb_synth_process(gr4hip_pfb_synth_t* f, const void* d_spectra, size_
             hipLaunchKernelGGL(pfb_synth_combine_kernel<1>, dim3((unsigned)std::min<size_t>(ceil_div(lanes, (size_t)256), 0x7fffffffu)), dim3(256), 0, st, V, hist, g, y, log2n, (int)P, (long)n);
         }
         GR4_LAUNCH_CHECK();
-        if (const int rc = pfb_hist_launch(V, (long)(n * N), hist, static_cast<float2*>(f->d_hist[f->cur ^ 1].ptr), (long)hlen, st)) return rc;
-        f->cur ^= 1;
+        if (const int rc = f->hist.advance(V, n * N, (P - 1) * N, (int)sizeof(float2), st)) return rc;
     }
     return GR4HIP_OK;
 }

@@ -10,6 +10,7 @@
 #define GR4_BUF_STORE_AUX 2
 #endif
 #include "specint_kernels.hpp"
+#include "history.hpp"
 
 #include <algorithm>
 
@@ -45,22 +46,6 @@ __global__ void pfb_block_kernel(PfbFront fe, const float2* __restrict__ tw, Fft
     for (int k = t; k < N; k += tf) emit_bin(out, frame, N, k, buf[k]);
 }
 
-// the last P - 1 frames after a call of n_in samples: sample j of the new history is sample n_in - len + j of the call, or -- below 0, a call of fewer than
-// P - 1 frames -- sample j + n_in of the old history.  Old and new are two buffers: nothing is read that this launch writes.
-__global__ __launch_bounds__(256) void pfb_hist_kernel(const float2* __restrict__ x, long n_in, const float2* __restrict__ old_hist, float2* __restrict__ new_hist, long len) {
-    const long j = (long)blockIdx.x * 256 + threadIdx.x;
-    if (j >= len) return;
-    const long s = n_in - len + j;
-    new_hist[j]  = s >= 0 ? x[s] : old_hist[j + n_in];
-}
-
-// (shared with the synthesis bank, ifft.hip, whose history is the last P - 1 transformed frames)
-int pfb_hist_launch(const float2* x, long n_in, const float2* old_hist, float2* new_hist, long len, hipStream_t st) {
-    hipLaunchKernelGGL(pfb_hist_kernel, dim3((unsigned)ceil_div(len, 256L)), dim3(256), 0, st, x, n_in, old_hist, new_hist, len);
-    GR4_LAUNCH_CHECK();
-    return GR4HIP_OK;
-}
-
 int fft_build_plan(size_t N, FftPlanDev* plan);       // fft.hip
 int fft_upload_twiddles(size_t N, DeviceBuffer* buf); // fft.hip
 
@@ -74,10 +59,10 @@ struct gr4hip_pfb {
     size_t             N = 0, P = 0;
     std::vector<float> taps; // the host image the stream-ordered upload reads
     FftPlanDev         plan{};
-    DeviceBuffer       d_taps, d_tw, d_hist[2];
-    int                cur = 0;
+    DeviceBuffer       d_taps, d_tw;
+    CarriedHistory     hist; // the last P - 1 frames: (P - 1) N complex samples (none for P = 1)
     long               run_length = 0; // N = 8192, P = 2 .. 4: frames per workgroup of the run form (test hook); 0: the simple form
-    bool               taps_dirty = false, zero_hist = true, last_run_form = false;
+    bool               taps_dirty = false, last_run_form = false;
 };
 
 static int pfb_design(float* h, size_t N, size_t P, int window, float beta) {
@@ -108,25 +93,11 @@ static int pfb_check_taps(const char* who, const float* h, size_t count) {
 
 // what set_taps / reset left for the next call, on that call's stream
 static int pfb_apply_pending(gr4hip_pfb* f, hipStream_t st) {
-    const size_t hlen = (f->P - 1) * f->N;
     if (f->taps_dirty) {
         GR4_HIP_TRY(hipMemcpyAsync(f->d_taps.ptr, f->taps.data(), f->taps.size() * sizeof(float), hipMemcpyHostToDevice, st));
         f->taps_dirty = false;
     }
-    if (f->zero_hist) {
-        if (hlen) GR4_HIP_TRY(hipMemsetAsync(f->d_hist[f->cur].ptr, 0, hlen * sizeof(float2), st));
-        f->zero_hist = false;
-    }
-    return GR4HIP_OK;
-}
-
-// the history of the next call, into the other buffer
-static int pfb_carry_history(gr4hip_pfb* f, const void* d_in, size_t n_in, hipStream_t st) {
-    const size_t hlen = (f->P - 1) * f->N;
-    if (!hlen) return GR4HIP_OK;
-    if (const int rc = pfb_hist_launch(static_cast<const float2*>(d_in), (long)n_in, static_cast<const float2*>(f->d_hist[f->cur].ptr), static_cast<float2*>(f->d_hist[f->cur ^ 1].ptr), (long)hlen, st)) return rc;
-    f->cur ^= 1;
-    return GR4HIP_OK;
+    return f->hist.on(st);
 }
 
 extern "C" {
@@ -165,7 +136,7 @@ int gr4hip_pfb_create(gr4hip_pfb_t** out, int in_dtype, size_t n_channels, size_
     if (!rc) rc = fft_upload_twiddles(f->N, &f->d_tw);
     if (!rc) rc = f->d_taps.ensure(L * sizeof(float));
     if (!rc && upload_fresh(f->d_taps.ptr, f->taps.data(), L * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); set_error("pfb: prototype upload failed"); rc = GR4HIP_RUNTIME_ERROR; }
-    for (int k = 0; k < 2 && !rc && f->P > 1; ++k) rc = f->d_hist[k].ensure((f->P - 1) * f->N * sizeof(float2));
+    if (!rc) rc = f->hist.resize((f->P - 1) * f->N * sizeof(float2));
     if (rc) { delete f; return rc; }
     *out = f;
     return GR4HIP_OK;
@@ -183,7 +154,7 @@ int gr4hip_pfb_set_taps(gr4hip_pfb_t* f, const float* h_taps, size_t count) {
 
 int gr4hip_pfb_reset(gr4hip_pfb_t* f) {
     GR4_REQUIRE(f, "pfb_reset: null handle");
-    f->zero_hist = true; // zeroed on the stream of the next call
+    f->hist.reset(); // zeroed on the stream of the next call
     return GR4HIP_OK;
 }
 
@@ -205,7 +176,7 @@ int gr4hip_pfb_process(gr4hip_pfb_t* f, const void* d_in, size_t n_frames, float
     }
     hipStream_t st = as_stream(stream);
     if (const int rc = pfb_apply_pending(f, st)) return rc;
-    PfbFront fe{static_cast<const float*>(d_in), static_cast<const float*>(f->d_hist[f->cur].ptr), static_cast<const float*>(f->d_taps.ptr), (int)P};
+    PfbFront fe{static_cast<const float*>(d_in), static_cast<const float*>(f->hist.current()), static_cast<const float*>(f->d_taps.ptr), (int)P};
     FftOutputs o{};
     o.spectrum    = d_spectrum;
     o.mag2        = d_mag2;
@@ -232,7 +203,7 @@ int gr4hip_pfb_process(gr4hip_pfb_t* f, const void* d_in, size_t n_frames, float
     }
     }
     if (rc) return rc;
-    return pfb_carry_history(f, d_in, n_in, st);
+    return f->hist.advance(d_in, n_in, (P - 1) * N, (int)sizeof(float2), st);
 }
 
 // |X|^2 summed over the integrator's frames (SPECTRUM_INTEGRATOR.md).  256 channels and more: pfb_fast_kernel's frame loop with the sink in place of the
@@ -248,10 +219,10 @@ int gr4hip_pfb_power_integrate(gr4hip_pfb_t* f, gr4hip_specint_t* si, const void
         if (const int rc = pfb_apply_pending(f, st)) return rc;
         SpecintLaunch L;
         if (const int rc = specint_begin(si, n_frames, st, &L)) return rc;
-        const PfbFront fe{static_cast<const float*>(d_in), static_cast<const float*>(f->d_hist[f->cur].ptr), static_cast<const float*>(f->d_taps.ptr), (int)f->P};
+        const PfbFront fe{static_cast<const float*>(d_in), static_cast<const float*>(f->hist.current()), static_cast<const float*>(f->d_taps.ptr), (int)f->P};
         if (const int rc = specint_sink_pfb(N, fe, static_cast<const float2*>(f->d_tw.ptr), L, st)) return rc;
         if (const int rc = specint_finish(si, L, d_out, 1, st)) return rc;
-        if (const int rc = pfb_carry_history(f, d_in, n_frames * N, st)) return rc;
+        if (const int rc = f->hist.advance(d_in, n_frames * N, (f->P - 1) * N, (int)sizeof(float2), st)) return rc;
         f->last_run_form = false;
     } else if (n_frames > 0) {
         struct Ctx { gr4hip_pfb_t* f; const float2* in; } ctx{f, static_cast<const float2*>(d_in)};

@@ -67,11 +67,19 @@ def test_lifecycle_calls_never_touch_the_device_outside_a_stream():
     # every mutator is a host-side note: no HIP call at all between its braces (the device work is in *_state_on / history_on, which take the stream)
     for f, fn in (("chain_fused.hip", "int chain_fused_reset(ChainFused* c) {"), ("chain_td.hip", "int chain_td_reset(ChainTd* c) {"), ("fir_batched.hip", "int gr4hip_fir_batched_reset("),
                   ("iir.hip", "int gr4hip_iir_reset(gr4hip_iir_t* f) {"), ("fir.hip", "int gr4hip_fir_reset(gr4hip_fir_t* f) {"), ("math.hip", "int gr4hip_rotator_reset("),
-                  ("f64.hip", "int gr4hip_fir64_reset("), ("f64.hip", "int gr4hip_iir64_reset("), ("fir_interp.hip", "int gr4hip_fir_interp_reset(")):
+                  ("f64.hip", "int gr4hip_fir64_reset("), ("f64.hip", "int gr4hip_iir64_reset("), ("fir_interp.hip", "int gr4hip_fir_interp_reset("),
+                  ("fir_resamp.hip", "int gr4hip_resamp_reset("), ("fir_cplx.hip", "int gr4hip_cfir_reset("), ("pfb.hip", "int gr4hip_pfb_reset("),
+                  ("ifft.hip", "int gr4hip_pfb_synth_reset(")):
         t = open(os.path.join(src, f), errors="replace").read()
         i = t.index(fn)
         body = t[i:t.index("\n}\n", i)]
         assert not re.search(r"\bhip[A-Z]\w*\(", body), (f, fn, body)
+    # what those mutators call on the carried history (history.hpp: one-line members, the body ends at the first closing brace)
+    t = open(os.path.join(src, "history.hpp"), errors="replace").read()
+    for fn in ("void reset() {", "void keep() {"):
+        i = t.index(fn)
+        body = t[i:t.index("}", i) + 1]
+        assert body.count("{") == 1 and not re.search(r"\bhip[A-Z]\w*\(", body), (fn, body)
 
 
 def test_status_strings_and_errors(L):
