@@ -37,6 +37,8 @@ enum DevSwitch {
     kDevFftBluesteinGeneric,  // GR4HIP_FFT_BLUESTEIN_GENERIC: the chirp convolution on the run-time radix-8 passes (one frame per workgroup) instead of the compile-time 16 x 16 x R3 plan
     kDevFftFourStep64k,       // GR4HIP_FFT_FOUR_STEP_64K: 65536-point transforms through the three-kernel four-step pipeline instead of the two-kernel 256 x 256 form
     kDevSiggenGaussPermille,  // GR4HIP_SIGGEN_GAUSS_PERMILLE: an integer; non-zero: the Gaussian signal generator launches this many attempts per 1000 needed pairs (0: its own formula); the tests reach the tail kernel with it
+    kDevInterpNoMfma,         // GR4HIP_INTERP_NO_MFMA: the interpolating FIR's register-window / generic kernels also on the long spans that the matrix-pipe kernel takes (the tests compare them)
+    kDevInterpSpw,            // GR4HIP_INTERP_SPW: an integer; 1 .. 4: the interpolating FIR's matrix-pipe kernel gives every workgroup this many segments (0: clamp(segments / 2048, 1, 4)); the tests reach the multi-segment loop at spans of a few segments with it
     kDevSwitchCount
 };
 int dev_switch(DevSwitch s);

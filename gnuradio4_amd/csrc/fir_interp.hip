@@ -12,7 +12,12 @@
 //  * otherwise (short spans; L = 3, 5, 6; branches longer than 272 taps): fir_interp_kernel<L, R, S> -- a lane owns R consecutive input positions and
 //    all L phases of them: R L accumulators, one sliding register window of the staged input (one LDS read per tap step), the L branch taps of step q
 //    are wave-uniform (scalar loads), the R L outputs of a lane are contiguous in memory; FP32 FMA rate at long filters (2 K / L flop per output),
-//    HBM at short ones ((4 + 4 L) B per real input sample).  Factors it is not instantiated for take one output per lane straight from the L2.
+//    HBM at short ones ((4 + 4 L) B per real input sample).  Factors it is not instantiated for, and windows of more than 150 KB of LDS, take one
+//    output per lane straight from the L2 (fir_interp_generic_kernel).
+// The matrix-pipe form also needs an output on a 16-byte boundary (it ends on float4 stores) and exists for KS <= 68 K-steps and a tap row of
+// 4 KS L <= 16384 floats (ip_upload).  Which kernel served a call, in which instantiation and grid, is on record for the tests
+// (gr4hip_internal_fir_interp_last_path below; tests/test_gpu_fir_interp_paths.py); the developer switches GR4HIP_INTERP_NO_MFMA and GR4HIP_INTERP_SPW
+// (common.hpp) move a call between the kernels and set the matrix-pipe kernel's segments per workgroup.
 // History: the last Kp - 1 input samples (capacity max(32, bit_ceil(Kp)) like HistoryBuffer, :36-42).
 #include "common.hpp"
 #include "history.hpp"
@@ -262,10 +267,14 @@ struct gr4hip_fir_interp {
     // the stream rule (common.hpp): create / reset / set_taps only note what the device state has to become; ip_state_on() enqueues it on the stream of the next call
     std::vector<float> t_host, row_host; // images of d_taps / d_row as ip_upload laid them out
     bool               taps_dirty = false;
+    // what the last gr4hip_fir_interp_process call enqueued (gr4hip_internal_fir_interp_last_path): {kernel (0 nothing, 1 register-window, 2 generic, 3 matrix pipe),
+    // G of kernel 3 / R of kernel 1, KS, segments per workgroup of kernel 3, grid.x, grid.y, 1: the kernel wrote the next history and the handle flipped, hcap}
+    int                last_path[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 constexpr size_t kIpMfmaMinOut = 32768; // shorter spans: the register-window kernel (fewer, smaller workgroups)
-static bool ip_env_no_mfma() { static const bool v = std::getenv("GR4HIP_INTERP_NO_MFMA") != nullptr; return v; } // developer switch: the tests compare the two kernels
+// developer switches (common.hpp): GR4HIP_INTERP_NO_MFMA keeps long spans on the register-window / generic kernel (tests/test_gpu_fir_interp_paths.py compares the
+// kernels with it); GR4HIP_INTERP_SPW = 1 .. 4 sets the matrix-pipe kernel's segments per workgroup, so that spans of a few segments run its multi-segment loop
 
 static int ip_upload(gr4hip_fir_interp* f) {
     f->Kp = ceil_div(f->ntaps, f->L);
@@ -297,21 +306,24 @@ static int ip_upload(gr4hip_fir_interp* f) {
 }
 
 template <int G, int S>
-static int ip_mfma_launch(const gr4hip_fir_interp* f, const void* x, void* y, long n_in, hipStream_t st, float* new_hist) {
+static int ip_mfma_launch(gr4hip_fir_interp* f, const void* x, void* y, long n_in, hipStream_t st, float* new_hist) {
     constexpr int SI = 4096 / S;
     const int     Hq = 4 * f->KS - G, NS = SI + Hq, ROW = ((NS / G + 31) / 32) * 32 + 16;
     const size_t  lds = ((size_t)S * G * ROW + 16 + 4 * (size_t)f->KS * f->L) * sizeof(float);
     const long    nseg = ceil_div(n_in, (long)SI);
-    const int     spw = (int)std::clamp<long>(nseg / 2048, 1, 4); // >= 2048 workgroups (8 per CU) before a workgroup takes a second segment
+    const int     dev_spw = dev_switch(kDevInterpSpw); // (developer switch: the multi-segment loop at spans of a few segments, for the tests)
+    const int     spw = dev_spw >= 1 && dev_spw <= 4 ? dev_spw : (int)std::clamp<long>(nseg / 2048, 1, 4); // >= 2048 workgroups (8 per CU) before a workgroup takes a second segment
+    const dim3    grid((unsigned)ceil_div(nseg, (long)spw), G == 1 ? (unsigned)ceil_div(f->L, (size_t)16) : 1u);
     auto          kern = fir_interp_mfma_kernel<G, S>;
     if (lds > 48 * 1024) GR4_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(nseg, (long)spw), G == 1 ? (unsigned)ceil_div(f->L, (size_t)16) : 1u), dim3(256), lds, st, static_cast<const float*>(x), static_cast<const float*>(f->hist.current()), (int)f->hcap,
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, static_cast<const float*>(x), static_cast<const float*>(f->hist.current()), (int)f->hcap,
                        static_cast<const float*>(f->d_row.ptr), f->KS, static_cast<float*>(y), n_in, spw, new_hist, (int)f->L);
     GR4_LAUNCH_CHECK();
+    f->last_path[0] = 3, f->last_path[1] = G, f->last_path[3] = spw, f->last_path[4] = (int)grid.x, f->last_path[5] = (int)grid.y;
     return GR4HIP_OK;
 }
 template <int S>
-static int ip_mfma_dispatch(const gr4hip_fir_interp* f, const void* x, void* y, long n_in, hipStream_t st, float* new_hist) {
+static int ip_mfma_dispatch(gr4hip_fir_interp* f, const void* x, void* y, long n_in, hipStream_t st, float* new_hist) {
     switch (f->G) {
     case 8: return ip_mfma_launch<8, S>(f, x, y, n_in, st, new_hist);
     case 4: return ip_mfma_launch<4, S>(f, x, y, n_in, st, new_hist);
@@ -330,7 +342,7 @@ static int ip_state_on(gr4hip_fir_interp* f, hipStream_t st) {
 }
 
 template <int L, int R, int S>
-static int ip_launch(const gr4hip_fir_interp* f, const void* x, void* y, long n_in, hipStream_t st) {
+static int ip_launch(gr4hip_fir_interp* f, const void* x, void* y, long n_in, hipStream_t st) {
     using T          = typename ip_vec<S>::type;
     const size_t lds = ((f->Kp - 1) + (size_t)kIpBS * R) * sizeof(T);
     if (lds > 150 * 1024) return GR4HIP_UNSUPPORTED;
@@ -340,11 +352,12 @@ static int ip_launch(const gr4hip_fir_interp* f, const void* x, void* y, long n_
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kIpBS), lds, st, static_cast<const T*>(x), static_cast<const T*>(f->hist.current()), (int)f->hcap,
                        static_cast<const float*>(f->d_taps.ptr), (int)f->Kp, static_cast<T*>(y), n_in);
     GR4_LAUNCH_CHECK();
+    f->last_path[0] = 1, f->last_path[1] = R, f->last_path[4] = (int)grid, f->last_path[5] = 1;
     return GR4HIP_OK;
 }
 
 template <int S>
-static int ip_dispatch(const gr4hip_fir_interp* f, const void* x, void* y, long n_in, hipStream_t st) {
+static int ip_dispatch(gr4hip_fir_interp* f, const void* x, void* y, long n_in, hipStream_t st) {
     using T = typename ip_vec<S>::type;
     int rc  = GR4HIP_UNSUPPORTED;
     switch (f->L) { // R L accumulators (x S): 8 .. 16 per lane
@@ -361,6 +374,7 @@ static int ip_dispatch(const gr4hip_fir_interp* f, const void* x, void* y, long 
     hipLaunchKernelGGL(fir_interp_generic_kernel<S>, dim3(grid), dim3(256), 0, st, static_cast<const T*>(x), static_cast<const T*>(f->hist.current()), (int)f->hcap,
                        static_cast<const float*>(f->d_taps.ptr), (int)f->Kp, (int)f->L, static_cast<T*>(y), n_in);
     GR4_LAUNCH_CHECK();
+    f->last_path[0] = 2, f->last_path[4] = (int)grid, f->last_path[5] = 1;
     return GR4HIP_OK;
 }
 
@@ -408,15 +422,18 @@ int gr4hip_fir_interp_reset(gr4hip_fir_interp_t* f) {
 int gr4hip_fir_interp_process(gr4hip_fir_interp_t* f, const void* d_in, size_t n_in, void* d_out, size_t* n_out_p, gr4hip_stream_t stream) {
     GR4_REQUIRE(f, "fir_interp_process: null handle");
     if (n_out_p) *n_out_p = n_in * f->L;
+    std::memset(f->last_path, 0, sizeof(f->last_path));
+    f->last_path[2] = f->KS, f->last_path[7] = (int)f->hcap;
     if (n_in == 0) return GR4HIP_OK;
     GR4_REQUIRE(d_in && d_out, "fir_interp_process: null device pointer");
     hipStream_t st = as_stream(stream);
     if (const int rc = ip_state_on(f, st)) return rc;
-    if (f->KS > 0 && n_in * f->L >= kIpMfmaMinOut && (uintptr_t)d_out % 16 == 0 && (uintptr_t)d_in % (4 * f->S) == 0 && !ip_env_no_mfma()) { // matrix-pipe form; writes the next history itself
+    if (f->KS > 0 && n_in * f->L >= kIpMfmaMinOut && (uintptr_t)d_out % 16 == 0 && (uintptr_t)d_in % (4 * f->S) == 0 && !dev_switch(kDevInterpNoMfma)) { // matrix-pipe form; writes the next history itself
         float* nh = static_cast<float*>(f->hist.next());
         int    rc = f->S == 1 ? ip_mfma_dispatch<1>(f, d_in, d_out, (long)n_in, st, nh) : ip_mfma_dispatch<2>(f, d_in, d_out, (long)n_in, st, nh);
         if (rc) return rc;
         f->hist.flip();
+        f->last_path[6] = 1;
         return GR4HIP_OK;
     }
     int rc = f->S == 1 ? ip_dispatch<1>(f, d_in, d_out, (long)n_in, st) : ip_dispatch<2>(f, d_in, d_out, (long)n_in, st);
@@ -426,6 +443,14 @@ int gr4hip_fir_interp_process(gr4hip_fir_interp_t* f, const void* d_in, size_t n
 
 int gr4hip_fir_interp_destroy(gr4hip_fir_interp_t* f) {
     delete f;
+    return GR4HIP_OK;
+}
+
+// Test hook, not ABI (declared in no header): what the last gr4hip_fir_interp_process call enqueued -> rec = {kernel, G | R, KS, spw, grid.x, grid.y, flipped, hcap}
+// (the fields of gr4hip_fir_interp::last_path).  KS and hcap are the handle's at that call, also where it enqueued nothing (n_in == 0).
+int gr4hip_internal_fir_interp_last_path(const gr4hip_fir_interp_t* f, int* rec /*[8]*/) {
+    GR4_REQUIRE(f && rec, "fir_interp_last_path: bad argument");
+    std::memcpy(rec, f->last_path, sizeof(f->last_path));
     return GR4HIP_OK;
 }
 

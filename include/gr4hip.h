@@ -121,7 +121,8 @@ const char* gr4hip_last_error(void); /* thread-local text of the last failure */
  * guard) are per-handle settings: gr4hip_fir_set_algo, gr4hip_rotator_set_algo, gr4hip_chain_create / gr4hip_chain_set_guard_mode.
  * Names: GR4HIP_FIR_NO_BF16X3, GR4HIP_FIR_NO_DECIM_FD, GR4HIP_IIR_THREE_PASS, GR4HIP_IIR_LOOKBACK, GR4HIP_IIR_NO_SPLIT, GR4HIP_IIR_SEQ_SLOTS (an integer), GR4HIP_FFT_BLUESTEIN_PIPELINE,
  * GR4HIP_FFT_NO_PIPELINE, GR4HIP_ROTATOR_LEAP, GR4HIP_ROTATOR_WALK, GR4HIP_CHAIN16, GR4HIP_FFT_SMOOTH_RUNTIME, GR4HIP_EWISE_NO_DIV_RCP, GR4HIP_SIGGEN_GAUSS_PERMILLE (an integer:
- * the attempts the Gaussian signal generator launches per 1000 needed pairs, 0 = its own formula; whatever it launches, the values are the same). */
+ * the attempts the Gaussian signal generator launches per 1000 needed pairs, 0 = its own formula; whatever it launches, the values are the same), GR4HIP_INTERP_NO_MFMA (the
+ * interpolating FIR stays off the matrix pipe), GR4HIP_INTERP_SPW (an integer: 1 .. 4 segments per workgroup of the interpolating FIR's matrix-pipe kernel, 0 = its own formula). */
 int gr4hip_developer_switch(const char* name, int value);
 const char* gr4hip_status_string(int status);
 int         gr4hip_device_count(int* count);

@@ -198,6 +198,8 @@ def test_developer_switch_names():
     from gnuradio4_amd import capi
     L = capi.lib()
     assert L.gr4hip_developer_switch(b"GR4HIP_FFT_SMOOTH_RUNTIME", 1) == 0 and L.gr4hip_developer_switch(b"GR4HIP_FFT_SMOOTH_RUNTIME", 0) == 0
+    for name, value in ((b"GR4HIP_INTERP_NO_MFMA", 1), (b"GR4HIP_INTERP_SPW", 3)):  # the interpolating FIR's: a flag and an integer
+        assert L.gr4hip_developer_switch(name, value) == 0 and L.gr4hip_developer_switch(name, 0) == 0
     assert L.gr4hip_developer_switch(b"GR4HIP_NO_SUCH_SWITCH", 1) < 0 and b"unknown switch" in L.gr4hip_last_error()
 
 

@@ -916,6 +916,9 @@ def test_interpolating_fir_matrix_pipe_long_streams(G, interp, ntaps, cplx):
     truth, _ = O.fir_interp(b, x, interp)
     f = G.fir_interpolator(b, interp, torch.complex64 if cplx else torch.float32)
     assert _rel(f.process_bulk(dev(x)).cpu().numpy(), truth) <= TOL
+    hook, rec = G.capi.lib().gr4hip_internal_fir_interp_last_path, (C.c_int * 8)()  # (test hook, not in include/gr4hip.h; tests/test_gpu_fir_interp_paths.py)
+    hook.restype, hook.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_int)]
+    assert hook(f._h, rec) == 0 and rec[0] == 3, tuple(rec)  # the whole-stream call took the matrix-pipe kernel
     f.reset()
     cuts = [0, 70_001, 70_004, 74_100, 140_000, 140_900, n] if interp <= 16 else [0, 20_001, 20_004, 21_000, n]  # long spans (matrix pipe), short ones in between
     got = np.concatenate([f.process_bulk(dev(x[a:c])).cpu().numpy() for a, c in zip(cuts[:-1], cuts[1:])])
