@@ -598,31 +598,39 @@ class PolyphaseSynthesisBank(_Handle):
         return out
 
 
-class SpectrumIntegrator(_Handle):
+class _Integrating(_Handle):
+    """what the handles that carry a partial integration across calls share: gr4hip_<_prefix>_reset / _set_length / _pending, reported as <_name>.<call>"""
+    _prefix = _name = None
+
+    def _call(self, call, *args):
+        check(getattr(lib(), f"gr4hip_{self._prefix}_{call}")(self._h, *args), f"{self._name}.{call}")
+
+    def reset(self):
+        """drops the partial integration (from the next call on)"""
+        self._call("reset")
+
+    def set_length(self, n_integrate: int):
+        """another integration length; the partial integration is dropped"""
+        self._call("set_length", int(n_integrate))
+        self.n_integrate = int(n_integrate)
+
+    def pending(self, n_frames: int) -> int:
+        """results (spectra, matrices) the next call of n_frames frames (per stream) completes (host only)"""
+        n = C.c_size_t(0)
+        self._call("pending", int(n_frames), C.byref(n))
+        return int(n.value)
+
+
+class SpectrumIntegrator(_Integrating):
     """Sum (mean=True: mean) of n_integrate consecutive power spectra of n_bins values, one spectrum out per n_integrate frames in (the project's own definition,
     SPECTRUM_INTEGRATOR.md: float32 leaves of 32 frames, folded in float64, one fixed order).  The partial integration is carried across calls; a call returns the
     spectra it completes, float32 [pending(frames), n_bins]."""
-    _destroy = "gr4hip_specint_destroy"
+    _destroy, _prefix, _name = "gr4hip_specint_destroy", "specint", "SpectrumIntegrator"
 
     def __init__(self, n_bins: int, n_integrate: int, mean: bool = False):
         super().__init__()
         self.n_bins, self.n_integrate, self.mean = int(n_bins), int(n_integrate), bool(mean)
         check(lib().gr4hip_specint_create(C.byref(self._h), self.n_bins, self.n_integrate, capi.SPECINT_MEAN if self.mean else 0), "SpectrumIntegrator")
-
-    def reset(self):
-        """drops the partial integration (from the next call on)"""
-        check(lib().gr4hip_specint_reset(self._h), "SpectrumIntegrator.reset")
-
-    def set_length(self, n_integrate: int):
-        """another integration length; the partial integration is dropped"""
-        check(lib().gr4hip_specint_set_length(self._h, int(n_integrate)), "SpectrumIntegrator.set_length")
-        self.n_integrate = int(n_integrate)
-
-    def pending(self, n_frames: int) -> int:
-        """spectra the next call of n_frames frames completes (host only)"""
-        n = C.c_size_t(0)
-        check(lib().gr4hip_specint_pending(self._h, int(n_frames), C.byref(n)), "SpectrumIntegrator.pending")
-        return int(n.value)
 
     def _run(self, entry, first, x, frames, out, what):
         n = self.pending(frames)
@@ -640,33 +648,18 @@ class SpectrumIntegrator(_Handle):
         return self._run(lib().gr4hip_specint_process, None, x, x.numel() // self.n_bins, out, "SpectrumIntegrator.process_bulk")
 
 
-class CrossSpectrum(_Handle):
+class CrossSpectrum(_Integrating):
     """The averaged cross-spectral matrix of n_streams (2 .. 32) streams of complex spectra of n_bins values, V_ij[c] = sum_m X_i[m][c] conj(X_j[m][c]) over
     n_integrate frames (mean=True: divided by n_integrate) -- the project's own definition, CROSS_SPECTRUM.md: float32 fma chains over leaves of 64 frames, folded
     in float64, one fixed order.  Baselines are the lower triangle j <= i, packed p = i (i + 1) / 2 + j.  The partial integration is carried across calls; a call
     returns the matrices it completes, complex64 [pending(frames), P, n_bins]."""
-    _destroy = "gr4hip_xcorr_destroy"
+    _destroy, _prefix, _name = "gr4hip_xcorr_destroy", "xcorr", "CrossSpectrum"
 
     def __init__(self, n_streams: int, n_bins: int, n_integrate: int, mean: bool = False):
         super().__init__()
         self.n_streams, self.n_bins, self.n_integrate, self.mean = int(n_streams), int(n_bins), int(n_integrate), bool(mean)
         self.n_baselines = self.n_streams * (self.n_streams + 1) // 2
         check(lib().gr4hip_xcorr_create(C.byref(self._h), self.n_streams, self.n_bins, self.n_integrate, capi.XCORR_MEAN if self.mean else 0), "CrossSpectrum")
-
-    def reset(self):
-        """drops the partial integration (from the next call on)"""
-        check(lib().gr4hip_xcorr_reset(self._h), "CrossSpectrum.reset")
-
-    def set_length(self, n_integrate: int):
-        """another integration length; the partial integration is dropped"""
-        check(lib().gr4hip_xcorr_set_length(self._h, int(n_integrate)), "CrossSpectrum.set_length")
-        self.n_integrate = int(n_integrate)
-
-    def pending(self, n_frames: int) -> int:
-        """matrices the next call of n_frames frames per stream completes (host only)"""
-        n = C.c_size_t(0)
-        check(lib().gr4hip_xcorr_pending(self._h, int(n_frames), C.byref(n)), "CrossSpectrum.pending")
-        return int(n.value)
 
     def baseline(self, i: int, j: int) -> int:
         """the row of the pair (i, j), j <= i, in an emitted matrix"""

@@ -286,12 +286,7 @@ int gr4hip_mvdr_set_steering(gr4hip_mvdr_t* h, const float* d_steer, gr4hip_stre
     GR4_REQUIRE(h, "mvdr_set_steering: null handle");
     GR4_REQUIRE(d_steer, "mvdr_set_steering: null steering vectors");
     GR4_REQUIRE((uintptr_t)d_steer % 8 == 0, "mvdr_set_steering: the steering vectors must be aligned to 8 bytes");
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
-        (void)hipGetLastError();
-        set_error("mvdr: no HIP device visible");
-        return GR4HIP_NO_DEVICE;
-    }
+    if (const int rc = have_device("mvdr")) return rc;
     const hipStream_t st = as_stream(stream);
     if (!h->d_cnt.ptr) {
         if (const int rc = h->d_cnt.ensure(sizeof(unsigned long long))) return rc;

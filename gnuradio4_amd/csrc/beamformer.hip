@@ -43,7 +43,7 @@ template <bool POWER>
 __device__ __forceinline__ void bf_unit(const SpecintGeom& g, long n_frames, long k, long* first, int* count) {
     if constexpr (POWER) {
         bool complete;
-        specint_leaf_range(g, k, first, count, &complete);
+        leaf_range(g, k, first, count, &complete);
     } else {
         *first = k * kBfChunk;
         *count = (int)(n_frames - *first < kBfChunk ? n_frames - *first : kBfChunk);
@@ -445,12 +445,7 @@ int gr4hip_beamform_set_weights(gr4hip_beamform_t* bf, const float* d_weights, g
     GR4_REQUIRE(bf, "beamform_set_weights: null handle");
     GR4_REQUIRE(d_weights, "beamform_set_weights: null weights");
     GR4_REQUIRE((uintptr_t)d_weights % 8 == 0, "beamform_set_weights: the weights must be aligned to 8 bytes");
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
-        (void)hipGetLastError();
-        set_error("beamform: no HIP device visible");
-        return GR4HIP_NO_DEVICE;
-    }
+    if (const int rc = have_device("beamform")) return rc;
     const size_t bytes = bf->B * bf->S * bf->N * 2 * sizeof(float);
     if (const int rc = bf->d_w.ensure(bytes)) return rc;
     GR4_HIP_TRY(hipMemcpyAsync(bf->d_w.ptr, d_weights, bytes, hipMemcpyDeviceToDevice, as_stream(stream)));
@@ -503,15 +498,11 @@ int gr4hip_beamform_power_integrate(gr4hip_beamform_t* bf, gr4hip_specint_t* si,
     if (const int rc = bf_inputs(bf, who, d_spectra, &L.in)) return rc;
     for (size_t s = 0; s < bf->S; ++s) // the integrator's own refusals, per input: bins, null output, alignment, overlap
         if (const int rc = specint_check(si, who, M, d_spectra[s], bf->N * 8, 8, n_frames, d_out, n_out)) return rc;
-    size_t n = 0;
-    (void)gr4hip_specint_pending(si, n_frames, &n);
+    const size_t      n     = si->integ.pending(n_frames);
     const hipStream_t st    = as_stream(stream);
-    const size_t      piece = std::max<size_t>(1, kBfPieceValues / (bf->N * std::max(bf->S, bf->B))); // (a cut like any other: the values do not depend on it)
+    const size_t      piece = std::max<size_t>(1, kBfPieceValues / (bf->N * std::max(bf->S, bf->B)));
     const BfIn        in0   = L.in;
-    for (size_t f = 0; f < n_frames; f += piece) {
-        const size_t m = std::min(piece, n_frames - f);
-        size_t       done = 0;
-        (void)gr4hip_specint_pending(si, m, &done);
+    const int         rc    = si->integ.for_each_piece(n_frames, piece, d_out, [&](size_t f, size_t m, float* out) {
         for (size_t s = 0; s < bf->S; ++s) L.in.s[s] = in0.s[s] + f * bf->N * 2;
         SpecintLaunch SL;
         if (const int rc = specint_begin(si, m, st, &SL)) return rc;
@@ -520,9 +511,9 @@ int gr4hip_beamform_power_integrate(gr4hip_beamform_t* bf, gr4hip_specint_t* si,
         L.carry    = SL.carry;
         L.leaves   = SL.leaves;
         if (const int rc = bf_run<true>(bf, L, st)) return rc;
-        if (const int rc = specint_finish(si, SL, d_out, 1, st)) return rc;
-        if (d_out) d_out += done * M;
-    }
+        return specint_finish(si, SL, out, 1, st);
+    });
+    if (rc) return rc;
     *n_out = n;
     return GR4HIP_OK;
 }

@@ -80,6 +80,8 @@ constexpr float kDecimFdMinPowerRatio = 2.5e-3f;
 // still in flight -> "kernel launch failed: unknown error" in the next gr4hip_iir_create, one run in two).  So: ignored means cleared.
 inline void hip_quiet(hipError_t e) { if (e != hipSuccess) (void)hipGetLastError(); }
 
+int have_device(const char* who); // GR4HIP_NO_DEVICE and "<who>: no HIP device visible" where the process sees no GPU (runtime.hip)
+
 inline hipStream_t as_stream(gr4hip_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 inline size_t dtype_size(int dtype) {

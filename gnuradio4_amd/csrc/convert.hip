@@ -473,12 +473,7 @@ int gr4hip_convert_params_check(const gr4hip_convert_params* p) {
 int gr4hip_convert_create(gr4hip_convert_t** out, const gr4hip_convert_params* p) {
     GR4_REQUIRE(out, "convert: null output handle");
     if (const int rc = gr4hip_convert_params_check(p)) return rc;
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
-        (void)hipGetLastError();
-        set_error("convert: no HIP device visible");
-        return GR4HIP_NO_DEVICE;
-    }
+    if (const int rc = have_device("convert")) return rc;
     auto* h = new (std::nothrow) gr4hip_convert();
     GR4_REQUIRE(h, "out of host memory");
     h->p          = *p;

@@ -1,5 +1,5 @@
 // cross_spectrum.hip -- the cross-spectrum correlator (X-engine) on gfx950 (CROSS_SPECTRUM.md): C-ABI gr4hip_xcorr_*, its two leaf kernels (streaming VALU form,
-// matrix-pipe form), the emit kernel and the coherence kernel.
+// matrix-pipe form) and the coherence kernel.
 //
 //   S streams of frames X_s[f][c], c < N, complex<float>; baselines j <= i packed p = i (i + 1) / 2 + j; leaf l of integration q: frames q A + [64 l, min(64 (l + 1), A))
 //   per leaf, per (i, j), per bin, float32, frames ascending, re = im = +0 at the leaf's start:
@@ -9,11 +9,9 @@
 //
 // The reference has no such block: the definition is this project's, tests/cross_spectrum_oracle.py pins it.  One launch sums the call's leaves (each from +0, the
 // call's first from the carried running leaf) into leaves[k][p][c] (interleaved complex), a second small one folds them into the float64 accumulator, writes the
-// finished matrices and stores the carry of the next call into the other of two carry buffers -- the spectrum integrator's scheme (spectrum_integrator.hip) with
-// 2 P N float "bins" per leaf.
-#include "common.hpp"
-
-#include <algorithm>
+// finished matrices and stores the carry of the next call into the other of two carry buffers -- the leaf integrator (leaf_integrator.hpp) with leaves of 64
+// frames, rows of 2 P N floats and the Hermitian rule for the diagonal.
+#include "leaf_integrator.hpp"
 
 namespace gr4 {
 
@@ -31,41 +29,12 @@ struct XcorrIn {
     const float* s[kXcorrMaxStreams];
 };
 
-// The geometry of one call: n frames that start `pos` frames into an integration touch the leaves K = k0 .. k0 + nl - 1, counted from that integration's first leaf.
-struct XcorrGeom {
-    long pos; // frames of the integration in progress that earlier calls took (< A)
-    long n;   // frames of this call
-    long A;   // frames per integration
-    long lpi; // leaves per integration: ceil(A / 64)
-    long k0;  // pos / 64: the call's first leaf
-    long nl;  // leaves the call touches
-    long nq;  // integrations the call touches: ceil((pos + n) / A)
-};
-
-static XcorrGeom xcorr_geom(long pos, long n, long A) {
-    XcorrGeom  g{pos, n, A, (A + kXcorrLeaf - 1) / kXcorrLeaf, pos / kXcorrLeaf, 0, (pos + n + A - 1) / A};
-    const long last = pos + n - 1; // n >= 1
-    g.nl            = (last / A) * g.lpi + (last % A) / kXcorrLeaf - g.k0 + 1;
-    return g;
-}
-
-// call-leaf k: its first frame in the call, the frames of it the call holds, and whether the call holds its end
-__host__ __device__ __forceinline__ void xcorr_leaf_range(const XcorrGeom& g, long k, long* first, int* count, bool* complete) {
-    const long K = g.k0 + k, q = K / g.lpi, l = K - q * g.lpi;
-    const long s = q * g.A + l * kXcorrLeaf;
-    const long e = s + kXcorrLeaf < (q + 1) * g.A ? s + kXcorrLeaf : (q + 1) * g.A;
-    const long a = s > g.pos ? s : g.pos, b = e < g.pos + g.n ? e : g.pos + g.n;
-    *first    = a - g.pos;
-    *count    = (int)(b - a);
-    *complete = e <= g.pos + g.n;
-}
-
 __device__ __forceinline__ f32x2 load_stream(const float* p) { return __builtin_nontemporal_load(reinterpret_cast<const f32x2*>(p)); } // read once: the FFT kernels' nt hint
 
 // ---- form 1, streaming VALU: element i of [nl][N], one bin of one call-leaf.  The lane walks the leaf's frames, loads the S values of its bin (coalesced along
 // bins) and issues the four fmaf of every pair in the defined order into 2 P float accumulators.
 template <int S>
-__global__ __launch_bounds__(256) void xcorr_valu_kernel(XcorrIn in, XcorrGeom g, const float* __restrict__ carry, float* __restrict__ leaves, int N, long total) {
+__global__ __launch_bounds__(256) void xcorr_valu_kernel(XcorrIn in, LeafGeom<kXcorrLeaf> g, const float* __restrict__ carry, float* __restrict__ leaves, int N, long total) {
     constexpr int P = S * (S + 1) / 2;
     const long    i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
@@ -74,7 +43,7 @@ __global__ __launch_bounds__(256) void xcorr_valu_kernel(XcorrIn in, XcorrGeom g
     long       first;
     int        count;
     bool       complete;
-    xcorr_leaf_range(g, k, &first, &count, &complete);
+    leaf_range(g, k, &first, &count, &complete);
     float re[P], im[P];
 #pragma unroll
     for (int p = 0; p < P; ++p) {
@@ -123,7 +92,7 @@ constexpr int kXmFrameStride  = kXmBins * 2;                      // floats
 constexpr int kXmStreamStride = kXmFrames * kXmFrameStride + 4;   // floats; + 4: the 8 streams of an A fragment fall into different banks
 
 template <int MT, int NT>
-__global__ __launch_bounds__(256) void xcorr_mfma_kernel(XcorrIn in, int S, XcorrGeom g, const float* __restrict__ carry, float* __restrict__ leaves, int N, int tiles) {
+__global__ __launch_bounds__(256) void xcorr_mfma_kernel(XcorrIn in, int S, LeafGeom<kXcorrLeaf> g, const float* __restrict__ carry, float* __restrict__ leaves, int N, int tiles) {
     constexpr int SP = 16 * NT; // staged streams: 8 MT <= 16 NT
     __shared__ float lds[SP * kXmStreamStride];
     const long k  = blockIdx.x / tiles;
@@ -132,7 +101,7 @@ __global__ __launch_bounds__(256) void xcorr_mfma_kernel(XcorrIn in, int S, Xcor
     long       first;
     int        count;
     bool       complete;
-    xcorr_leaf_range(g, k, &first, &count, &complete);
+    leaf_range(g, k, &first, &count, &complete);
     const int t = threadIdx.x, l = t & 63, w = t >> 6;
     const int col = l & 15, quad = l >> 4; // quad = k of the operands, row group of the result
 
@@ -257,48 +226,6 @@ __global__ __launch_bounds__(256) void xcorr_mfma_kernel(XcorrIn in, int S, Xcor
     }
 }
 
-// ---- emit, the integrator's scheme.  Element i of [nq][M], M = 2 P N: one component of one baseline and bin of the j-th integration the call touches.  Its
-// leaves in ascending order into a float64 sum that starts from the carried one (j = 0) or from 0; a complete integration is written to out[j], the last one
-// leaves the carry of the next call: its sum, and the call's last leaf where the call does not hold that leaf's end.
-__global__ __launch_bounds__(256) void xcorr_emit_kernel(const float* __restrict__ leaves, XcorrGeom g, const double* __restrict__ acc_in, double* __restrict__ acc_out,
-                                                         float* __restrict__ leaf_out, float* __restrict__ out, long M, int N, int mean, long total) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    const long j = i / M;
-    const long e = i - j * M;
-    const long end = g.pos + g.n, k_last = g.nl - 1;
-    long       first;
-    int        count;
-    bool       last_complete;
-    xcorr_leaf_range(g, k_last, &first, &count, &last_complete);
-    const long ka = j * g.lpi > g.k0 ? j * g.lpi - g.k0 : 0, kb = (j + 1) * g.lpi - g.k0 < g.nl ? (j + 1) * g.lpi - g.k0 : g.nl; // [ka, kb): the call-leaves of integration j
-    const long ke = (kb == g.nl && !last_complete) ? kb - 1 : kb;                                                                 // [ka, ke): the complete ones
-    double       a = j == 0 ? acc_in[e] : 0.0;
-    const float* p = leaves + e;
-    long         k = ka;
-    for (; k + 8 <= ke; k += 8) { // eight loads in flight, the adds in leaf order
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = p[(k + u) * M];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) a = a + (double)v[u];
-    }
-    for (; k < ke; ++k) a = a + (double)p[k * M];
-    const bool done = (j + 1) * g.A <= end;
-    if (done) {
-        float v = mean ? (float)(a / (double)g.A) : (float)a;
-        if (e & 1) { // the imaginary part of the diagonal p = i (i + 3) / 2, where 8 p + 9 = (2 i + 3)^2, is +0 by definition
-            const int r = 8 * (int)(e / (2L * N)) + 9, s = (int)__builtin_sqrtf((float)r);
-            if (s * s == r) v = 0.f;
-        }
-        out[i] = v;
-    }
-    if (j == g.nq - 1) {
-        acc_out[e]  = done ? 0.0 : a;
-        leaf_out[e] = ke < kb ? p[ke * M] : 0.f;
-    }
-}
-
 // ---- coherence and H1 of one pair from emitted matrices: element idx of [n_spectra][N].  pij: the packed baseline (max, min); conj: i < j, V_ij = conj(V_ji)
 __global__ __launch_bounds__(256) void xcorr_coherence_kernel(const float* __restrict__ vis, int N, long P, long pij, int conj, long pii, long pjj, float* __restrict__ msc,
                                                               float* __restrict__ h1, long total) {
@@ -322,13 +249,10 @@ __global__ __launch_bounds__(256) void xcorr_coherence_kernel(const float* __res
 using namespace gr4;
 
 struct gr4hip_xcorr {
-    size_t       S = 0, N = 0, A = 0, P = 0;
-    int          flags = 0;
-    size_t       pos = 0; // frames of the integration in progress (host side: n_out needs no device sync)
-    DeviceBuffer d_acc[2], d_leaf[2], d_leaves;
-    int          cur = 0, last_path = 0;
-    int          force_path = 0; // test hook: 1 = the VALU form where it exists (S <= 8), 2 = the matrix-pipe form, 0 = the default
-    bool         zero_state = true;
+    size_t                            S = 0, N = 0, P = 0;
+    LeafIntegrator<kXcorrLeaf, true>  integ; // M = 2 P N
+    int                               last_path  = 0;
+    int                               force_path = 0; // test hook: 1 = the VALU form where it exists (S <= 8), 2 = the matrix-pipe form, 0 = the default
 };
 
 namespace gr4 {
@@ -340,12 +264,12 @@ static int xcorr_path(const gr4hip_xcorr* x) {
 }
 
 template <int S>
-static void xcorr_valu_launch(const XcorrIn& in, const XcorrGeom& g, const float* carry, float* leaves, int N, hipStream_t st) {
+static void xcorr_valu_launch(const XcorrIn& in, const LeafGeom<kXcorrLeaf>& g, const float* carry, float* leaves, int N, hipStream_t st) {
     const long total = g.nl * (long)N;
     hipLaunchKernelGGL(xcorr_valu_kernel<S>, dim3((unsigned)ceil_div(total, 256L)), dim3(256), 0, st, in, g, carry, leaves, N, total);
 }
 
-static int xcorr_leaves(int path, int S, const XcorrIn& in, const XcorrGeom& g, const float* carry, float* leaves, int N, hipStream_t st) {
+static int xcorr_leaves(int path, int S, const XcorrIn& in, const LeafGeom<kXcorrLeaf>& g, const float* carry, float* leaves, int N, hipStream_t st) {
     if (path == 1) {
         switch (S) {
         case 2: xcorr_valu_launch<2>(in, g, carry, leaves, N, st); break;
@@ -373,37 +297,13 @@ static int xcorr_leaves(int path, int S, const XcorrIn& in, const XcorrGeom& g, 
 
 // one piece: n frames of every stream, already offset
 static int xcorr_fold(gr4hip_xcorr* x, const XcorrIn& in, size_t n_frames, float* d_out, hipStream_t st) {
-    const size_t M = 2 * x->P * x->N;
-    if (!x->d_acc[0].ptr) { // the carry buffers, on first use: create is host code
-        int n_dev = 0;
-        if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
-            (void)hipGetLastError();
-            set_error("xcorr: no HIP device visible");
-            return GR4HIP_NO_DEVICE;
-        }
-        for (int k = 0; k < 2; ++k) {
-            if (const int rc = x->d_acc[k].ensure(M * sizeof(double))) return rc;
-            if (const int rc = x->d_leaf[k].ensure(M * sizeof(float))) return rc;
-        }
-        x->zero_state = true;
-    }
-    if (x->zero_state) {
-        GR4_HIP_TRY(hipMemsetAsync(x->d_acc[x->cur].ptr, 0, M * sizeof(double), st));
-        GR4_HIP_TRY(hipMemsetAsync(x->d_leaf[x->cur].ptr, 0, M * sizeof(float), st));
-        x->zero_state = false;
-    }
-    const XcorrGeom g = xcorr_geom((long)x->pos, (long)n_frames, (long)x->A);
-    if (const int rc = x->d_leaves.ensure((size_t)g.nl * M * sizeof(float))) return rc;
-    float*    leaves = static_cast<float*>(x->d_leaves.ptr);
-    const int path   = xcorr_path(x);
-    if (const int rc = xcorr_leaves(path, (int)x->S, in, g, static_cast<const float*>(x->d_leaf[x->cur].ptr), leaves, (int)x->N, st)) return rc;
-    const long total = g.nq * (long)M;
-    hipLaunchKernelGGL(xcorr_emit_kernel, dim3((unsigned)ceil_div(total, 256L)), dim3(256), 0, st, (const float*)leaves, g, static_cast<const double*>(x->d_acc[x->cur].ptr),
-                       static_cast<double*>(x->d_acc[x->cur ^ 1].ptr), static_cast<float*>(x->d_leaf[x->cur ^ 1].ptr), d_out, (long)M, (int)x->N,
-                       (x->flags & GR4HIP_XCORR_MEAN) ? 1 : 0, total);
-    GR4_LAUNCH_CHECK();
-    x->cur ^= 1;
-    x->pos       = (size_t)((g.pos + g.n) % g.A);
+    LeafGeom<kXcorrLeaf> g;
+    const float*         carry;
+    float*               leaves;
+    if (const int rc = x->integ.begin(n_frames, st, "xcorr", &g, &carry, &leaves)) return rc;
+    const int path = xcorr_path(x);
+    if (const int rc = xcorr_leaves(path, (int)x->S, in, g, carry, leaves, (int)x->N, st)) return rc;
+    if (const int rc = x->integ.finish(g, d_out, st)) return rc;
     x->last_path = path;
     return GR4HIP_OK;
 }
@@ -418,7 +318,7 @@ int gr4hip_xcorr_create(gr4hip_xcorr_t** out, size_t n_streams, size_t n_bins, s
     GR4_REQUIRE(out, "xcorr: null output handle");
     GR4_REQUIRE(n_streams >= 2, "xcorr: n_streams must be >= 2 (got %zu)", n_streams);
     GR4_REQUIRE(n_bins >= 2, "xcorr: n_bins must be >= 2 (got %zu)", n_bins);
-    GR4_REQUIRE(n_integrate >= 1 && n_integrate <= (size_t(1) << 40), "xcorr: n_integrate must be in [1, 2^40] (got %zu)", n_integrate);
+    GR4_REQUIRE(n_integrate >= 1 && n_integrate <= kLeafMaxFrames, "xcorr: n_integrate must be in [1, 2^40] (got %zu)", n_integrate);
     GR4_REQUIRE((flags & ~GR4HIP_XCORR_MEAN) == 0, "xcorr: unknown flags %d", flags);
     if (n_streams > (size_t)kXcorrMaxStreams) { set_error("xcorr: %zu streams (supported: up to %d)", n_streams, kXcorrMaxStreams); return GR4HIP_UNSUPPORTED; }
     if (n_bins > kXcorrMaxBins) { set_error("xcorr: %zu bins (supported: up to %zu)", n_bins, kXcorrMaxBins); return GR4HIP_UNSUPPORTED; }
@@ -426,33 +326,34 @@ int gr4hip_xcorr_create(gr4hip_xcorr_t** out, size_t n_streams, size_t n_bins, s
     if (P * n_bins > kXcorrMaxState) { set_error("xcorr: %zu baselines of %zu bins (supported: up to %zu values of carried state)", P, n_bins, kXcorrMaxState); return GR4HIP_UNSUPPORTED; }
     auto* x = new (std::nothrow) gr4hip_xcorr();
     GR4_REQUIRE(x, "out of host memory");
-    x->S     = n_streams;
-    x->N     = n_bins;
-    x->A     = n_integrate;
-    x->P     = P;
-    x->flags = flags;
-    *out     = x; // the device buffers come with the first process call: everything up to there is host code
+    x->S          = n_streams;
+    x->N          = n_bins;
+    x->P          = P;
+    x->integ.M    = 2 * P * n_bins;
+    x->integ.N    = n_bins;
+    x->integ.A    = n_integrate;
+    x->integ.mean = (flags & GR4HIP_XCORR_MEAN) != 0;
+    *out          = x; // the device buffers come with the first process call: everything up to there is host code
     return GR4HIP_OK;
 }
 
 int gr4hip_xcorr_reset(gr4hip_xcorr_t* x) {
     GR4_REQUIRE(x, "xcorr_reset: null handle");
-    x->pos        = 0;
-    x->zero_state = true; // zeroed on the stream of the next call
+    x->integ.reset();
     return GR4HIP_OK;
 }
 
 int gr4hip_xcorr_set_length(gr4hip_xcorr_t* x, size_t n_integrate) {
     GR4_REQUIRE(x, "xcorr_set_length: null handle");
-    GR4_REQUIRE(n_integrate >= 1 && n_integrate <= (size_t(1) << 40), "xcorr_set_length: n_integrate must be in [1, 2^40] (got %zu)", n_integrate);
-    x->A = n_integrate;
-    return gr4hip_xcorr_reset(x);
+    GR4_REQUIRE(n_integrate >= 1 && n_integrate <= kLeafMaxFrames, "xcorr_set_length: n_integrate must be in [1, 2^40] (got %zu)", n_integrate);
+    x->integ.set_length(n_integrate);
+    return GR4HIP_OK;
 }
 
 int gr4hip_xcorr_pending(const gr4hip_xcorr_t* x, size_t n_frames, size_t* n_out) {
     GR4_REQUIRE(x && n_out, "xcorr_pending: null argument");
-    GR4_REQUIRE(n_frames <= (size_t(1) << 40), "xcorr_pending: %zu frames", n_frames);
-    *n_out = (x->pos + n_frames) / x->A;
+    GR4_REQUIRE(n_frames <= kLeafMaxFrames, "xcorr_pending: %zu frames", n_frames);
+    *n_out = x->integ.pending(n_frames);
     return GR4HIP_OK;
 }
 
@@ -461,12 +362,12 @@ int gr4hip_xcorr_process(gr4hip_xcorr_t* x, const float* const* d_spectra, size_
     GR4_REQUIRE(n_out, "xcorr_process: null n_out");
     if (n_frames == 0) { *n_out = 0; return GR4HIP_OK; }
     GR4_REQUIRE(d_spectra, "xcorr_process: null array of inputs");
-    GR4_REQUIRE(n_frames <= (size_t(1) << 40) / x->N, "xcorr_process: %zu frames of %zu bins in one call", n_frames, x->N);
-    const size_t n = (x->pos + n_frames) / x->A;
+    GR4_REQUIRE(n_frames <= kLeafMaxFrames / x->N, "xcorr_process: %zu frames of %zu bins in one call", n_frames, x->N);
+    const size_t n = x->integ.pending(n_frames);
     GR4_REQUIRE(d_out || n == 0, "xcorr_process: null output in a call that completes %zu integrations", n);
     GR4_REQUIRE((uintptr_t)d_out % 8 == 0, "xcorr_process: the output must be aligned to 8 bytes");
     XcorrIn         in{};
-    const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + n * x->P * x->N * 2 * sizeof(float);
+    const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + n * x->integ.M * sizeof(float);
     for (size_t s = 0; s < x->S; ++s) {
         GR4_REQUIRE(d_spectra[s], "xcorr_process: null input %zu", s);
         GR4_REQUIRE((uintptr_t)d_spectra[s] % 8 == 0, "xcorr_process: input %zu must be aligned to 8 bytes", s);
@@ -475,14 +376,13 @@ int gr4hip_xcorr_process(gr4hip_xcorr_t* x, const float* const* d_spectra, size_
         in.s[s] = d_spectra[s];
     }
     const hipStream_t st    = as_stream(stream);
-    const size_t      piece = std::max<size_t>(1, kXcorrPieceValues / (x->N * x->S)); // (a cut like any other: the values do not depend on it)
-    for (size_t f = 0; f < n_frames; f += piece) {
-        const size_t m = std::min(piece, n_frames - f), done = (x->pos + m) / x->A;
-        XcorrIn      at{};
+    const size_t      piece = std::max<size_t>(1, kXcorrPieceValues / (x->N * x->S));
+    const int         rc    = x->integ.for_each_piece(n_frames, piece, d_out, [&](size_t f, size_t m, float* out) {
+        XcorrIn at{};
         for (size_t s = 0; s < x->S; ++s) at.s[s] = in.s[s] + f * x->N * 2;
-        if (const int rc = xcorr_fold(x, at, m, d_out, st)) return rc;
-        if (d_out) d_out += done * x->P * x->N * 2;
-    }
+        return xcorr_fold(x, at, m, out, st);
+    });
+    if (rc) return rc;
     *n_out = n;
     return GR4HIP_OK;
 }

@@ -288,12 +288,7 @@ int gr4hip_cfir_band_table(const float* h_taps, size_t ntaps, size_t decim, floa
 int gr4hip_cfir_create(gr4hip_cfir_t** out, const float* h_taps, size_t ntaps, size_t decim) {
     GR4_REQUIRE(out, "cfir: null output handle");
     if (const int rc = cf_check_taps("cfir", h_taps, ntaps, decim)) return rc;
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
-        (void)hipGetLastError();
-        set_error("cfir: no HIP device visible");
-        return GR4HIP_NO_DEVICE;
-    }
+    if (const int rc = have_device("cfir")) return rc;
     auto* f = new (std::nothrow) gr4hip_cfir();
     GR4_REQUIRE(f, "out of host memory");
     f->D     = decim;

@@ -300,12 +300,7 @@ int gr4hip_resamp_create(gr4hip_resamp_t** out, int dtype, const float* h_taps, 
     if (dtype != GR4HIP_F32 && dtype != GR4HIP_C32) { set_error("resamp: dtype must be F32 or C32 (got %d)", dtype); return GR4HIP_UNSUPPORTED; }
     if (interp > kRsMaxRate || decim > kRsMaxRate) { set_error("resamp: interp %zu, decim %zu (supported: 1 .. %zu)", interp, decim, kRsMaxRate); return GR4HIP_UNSUPPORTED; }
     if (const int rc = rs_check_taps("resamp", h_taps, ntaps)) return rc;
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
-        (void)hipGetLastError();
-        set_error("resamp: no HIP device visible");
-        return GR4HIP_NO_DEVICE;
-    }
+    if (const int rc = have_device("resamp")) return rc;
     auto* f = new (std::nothrow) gr4hip_resamp();
     GR4_REQUIRE(f, "out of host memory");
     f->dtype = dtype;

@@ -137,16 +137,6 @@ static int ifft_check_size(const char* who, size_t N) {
     return GR4HIP_OK;
 }
 
-static int ifft_have_device(const char* who) {
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
-        (void)hipGetLastError();
-        set_error("%s: no HIP device visible", who);
-        return GR4HIP_NO_DEVICE;
-    }
-    return GR4HIP_OK;
-}
-
 static int synth_check_taps(const char* who, const float* h, size_t count) {
     for (size_t i = 0; i < count; ++i) GR4_REQUIRE(std::isfinite(h[i]), "%s: tap %zu is not finite", who, i);
     return GR4HIP_OK;
@@ -173,7 +163,7 @@ int gr4hip_ifft_create(gr4hip_ifft_t** out, int out_dtype, size_t fft_size, int 
     GR4_REQUIRE((flags & ~GR4HIP_IFFT_SCALE) == 0, "ifft: unknown flags %d", flags);
     GR4_REQUIRE(window >= GR4HIP_WIN_NONE && window <= GR4HIP_WIN_KAISER, "ifft: unknown window %d", window);
     if (const int rc = ifft_check_size("ifft", fft_size)) return rc;
-    if (const int rc = ifft_have_device("ifft")) return rc;
+    if (const int rc = have_device("ifft")) return rc;
     auto* f = new (std::nothrow) gr4hip_ifft();
     GR4_REQUIRE(f, "out of host memory");
     f->N     = fft_size;
@@ -215,7 +205,7 @@ int gr4hip_pfb_synth_create(gr4hip_pfb_synth_t** out, size_t n_channels, size_t 
     const size_t L = n_channels * taps_per_channel;
     if (h_taps)
         if (const int rc = synth_check_taps("pfb_synth", h_taps, L)) return rc;
-    if (const int rc = ifft_have_device("pfb_synth")) return rc;
+    if (const int rc = have_device("pfb_synth")) return rc;
     auto* f = new (std::nothrow) gr4hip_pfb_synth();
     GR4_REQUIRE(f, "out of host memory");
     f->N     = n_channels;

@@ -118,12 +118,7 @@ int gr4hip_pfb_create(gr4hip_pfb_t** out, int in_dtype, size_t n_channels, size_
     const size_t L = n_channels * taps_per_channel;
     if (h_taps)
         if (const int rc = pfb_check_taps("pfb", h_taps, L)) return rc;
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
-        (void)hipGetLastError();
-        set_error("pfb: no HIP device visible");
-        return GR4HIP_NO_DEVICE;
-    }
+    if (const int rc = have_device("pfb")) return rc;
     auto* f = new (std::nothrow) gr4hip_pfb();
     GR4_REQUIRE(f, "out of host memory");
     f->N = n_channels;

@@ -36,6 +36,16 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
+int have_device(const char* who) {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
+        (void)hipGetLastError();
+        set_error("%s: no HIP device visible", who);
+        return GR4HIP_NO_DEVICE;
+    }
+    return GR4HIP_OK;
+}
+
 template <typename T>
 static T bessel_i0f(T x) { // window.hpp:42-56
     T       sum = 1, term = 1;

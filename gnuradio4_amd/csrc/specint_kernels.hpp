@@ -1,45 +1,15 @@
-// specint_kernels.hpp -- the spectrum integrator (SPECTRUM_INTEGRATOR.md) as seen by the transforms: the geometry of one call, the handle's begin / finish
-// steps, and the kernels that run the FFT block's frame loop (fft_fast_frames.inc) with the |X|^2 store replaced by per-lane leaf sums (the fused sink).
-//
-//   leaf_l[c] = (((0 + m[f0][c]) + m[f0 + 1][c]) + ...)   float32, the frames of integration q's leaf l = q A + [32 l, min(32 (l + 1), A)) ascending
-//   acc[c]    = ((0 + (double)leaf_0[c]) + ...)           float64, leaves ascending;  y_q[c] = (float)acc[c]  or  (float)(acc[c] / (double)A)
-//
-// A call of n frames that starts `pos` frames into an integration touches the leaves K = k0 .. k0 + nl - 1, counted from that integration's first leaf; every
-// producer (the stand-alone leaf kernel, the sinks) writes the float32 sum of call-leaf k = K - k0 to leaves[k][n_bins], the emit kernel folds them.
+// specint_kernels.hpp -- the spectrum integrator (SPECTRUM_INTEGRATOR.md) as seen by the transforms: its handle, the begin / finish steps of a call, and the
+// kernels that run the FFT block's frame loop (fft_fast_frames.inc) with the |X|^2 store replaced by per-lane leaf sums (the fused sink).  The scheme itself
+// -- leaves of 32 frames in float32, folded in float64 -- is leaf_integrator.hpp's: every producer (the stand-alone leaf kernel, the sinks, the beamformer)
+// writes the float32 sum of call-leaf k to leaves[k][n_bins], the emit kernel folds them.
 #pragma once
+#include "leaf_integrator.hpp"
 #include "pfb_kernels.hpp"
 
 namespace gr4 {
 
 constexpr int kSpecintLeaf = 32;
-
-struct SpecintGeom {
-    long pos; // frames of the integration in progress that earlier calls took (< A)
-    long n;   // frames of this call
-    long A;   // frames per integration
-    long lpi; // leaves per integration: ceil(A / 32)
-    long k0;  // pos / 32: the call's first leaf
-    long nl;  // leaves the call touches
-    long nq;  // integrations the call touches: ceil((pos + n) / A)
-};
-
-inline SpecintGeom specint_geom(long pos, long n, long A) {
-    SpecintGeom g{pos, n, A, (A + kSpecintLeaf - 1) / kSpecintLeaf, pos / kSpecintLeaf, 0, (pos + n + A - 1) / A};
-    const long  last = pos + n - 1; // n >= 1
-    g.nl             = (last / A) * g.lpi + (last % A) / kSpecintLeaf - g.k0 + 1;
-    return g;
-}
-
-// call-leaf k: its first frame in the call, the frames of it the call holds, and whether the call holds its end
-__host__ __device__ __forceinline__ void specint_leaf_range(const SpecintGeom& g, long k, long* first, int* count, bool* complete) {
-    const long K = g.k0 + k, q = K / g.lpi, l = K - q * g.lpi;
-    const long s = q * g.A + l * kSpecintLeaf;
-    const long e = s + kSpecintLeaf < (q + 1) * g.A ? s + kSpecintLeaf : (q + 1) * g.A;
-    const long a = s > g.pos ? s : g.pos, b = e < g.pos + g.n ? e : g.pos + g.n;
-    *first    = a - g.pos;
-    *count    = (int)(b - a);
-    *complete = e <= g.pos + g.n;
-}
+using SpecintGeom          = LeafGeom<kSpecintLeaf>;
 
 // what a producer of leaf sums is given for one call
 struct SpecintLaunch {
@@ -70,14 +40,14 @@ __device__ __forceinline__ SinkLane sink_begin(const SpecintGeom& g, const float
     long          f;
     int           c;
     bool          done;
-    specint_leaf_range(g, ku, unit_first, &c, &done);
+    leaf_range(g, ku, unit_first, &c, &done);
     const long room = g.n - *unit_first;
     *unit_frames    = (unsigned)(room < FPB * kSpecintLeaf ? room : FPB * kSpecintLeaf);
     const int  fl = threadIdx.x / T, t = threadIdx.x % T;
     const long k  = ku + fl;
     SinkLane   ln{0, 0};
     if (k < g.nl) {
-        specint_leaf_range(g, k, &f, &c, &done);
+        leaf_range(g, k, &f, &c, &done);
         ln.first = (int)(f - *unit_first);
         ln.count = c;
     }
@@ -247,7 +217,18 @@ int pfb_sink_launch_256(const PfbFront& bank, const float2* tw, const SpecintLau
 int pfb_sink_launch_8192(const PfbFront& bank, const float2* tw, const SpecintLaunch& L, hipStream_t st);
 #endif // __HIPCC__
 
-// ---- the handle's side of a call (spectrum_integrator.hip), for the entries that live with their transform's handle (fft.hip, pfb.hip)
+} // namespace gr4
+
+struct gr4hip_specint {
+    gr4::LeafIntegrator<gr4::kSpecintLeaf, false> integ;  // M = n_bins; begin / finish through specint_begin / specint_finish: one instance of the emit kernel
+    gr4::DeviceBuffer                             d_mag2; // the composition's |X|^2 of one piece
+    int                                           last_path  = 0;
+    int                                           force_path = 0; // test hook: 1 = the sink wherever a kernel exists, 2 = the composition, 0 = the measured default
+};
+
+namespace gr4 {
+
+// ---- the handle's side of a call (spectrum_integrator.hip), for the entries that live with their transform's handle (fft.hip, pfb.hip, beamformer.hip)
 // argument checks shared by the three entries, before any device work: *n_out = spectra the call completes
 int specint_check(const gr4hip_specint* si, const char* who, size_t n_bins, const void* d_in, size_t in_frame_bytes, size_t in_align, size_t n_frames, const float* d_out, size_t* n_out);
 int specint_begin(gr4hip_specint* si, size_t n_frames, hipStream_t st, SpecintLaunch* L); // applies a pending reset, sizes the leaf scratch

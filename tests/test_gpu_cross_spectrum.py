@@ -163,6 +163,44 @@ def test_reset_and_set_length_clear_the_carry(G):
     assert np.array_equal(u32(blk.process_bulk(torch.from_numpy(np.array(X2)).cuda()).cpu().numpy()), u32(want2))
 
 
+@pytest.mark.parametrize("mean", [False, True])
+@pytest.mark.parametrize("path", [1, 2])
+def test_the_carried_state_through_cuts_set_length_and_reset(G, path, mean):
+    """the state the integrating blocks share (csrc/leaf_integrator.hpp) behind the public entries alone, at S = 3, N = 7 (rows of 84 floats) and A = 65: calls of
+    1, 63, 1, 0, 65, 2 frames, set_length(2) in mid-integration, 3 frames, one more, reset(), 4 frames -- every call returns what pending said, the rows are the
+    ordered definition of the segments between the drops, bit for bit, and the diagonal's imaginary parts are +0"""
+    S, N, A = 3, 7, 65
+    X = XO.streams(S, 140, N, 77)
+    d = torch.from_numpy(X).cuda()
+    blk, at, got = G.CrossSpectrum(S, N, A, mean), 0, []
+    set_path(G, blk, path)
+
+    def feed(n):
+        nonlocal at
+        want = blk.pending(n)
+        out = blk.process_bulk([d[s, at:at + n].contiguous() for s in range(S)])
+        assert out.shape == (want, 6, N) and (n == 0 or last_path(G, blk) == path)
+        got.append(out.cpu().numpy())
+        at += n
+
+    for n in (1, 63, 1, 0, 65, 2):
+        feed(n)
+    assert at == 132 and blk.pending(A - 2) == 1
+    blk.set_length(2)  # frames 130, 131 are dropped
+    assert blk.pending(1) == 0 and blk.pending(2) == 1
+    feed(3)
+    feed(1)
+    blk.reset()
+    assert blk.pending(1) == 0
+    feed(4)
+    assert at == 140
+    want = np.concatenate([XO.cross_ordered(X[:, :132], A, mean), XO.cross_ordered(X[:, 132:136], 2, mean), XO.cross_ordered(X[:, 136:], 2, mean)])
+    got = np.concatenate(got)
+    assert got.shape == want.shape == (6, 6, N) and np.array_equal(u32(got), u32(want))
+    diag = [XO.baseline(i, i) for i in range(S)]
+    assert not u32(got.imag[:, diag]).any() and u32(got.imag[:, [XO.baseline(1, 0), XO.baseline(2, 0), XO.baseline(2, 1)]]).all()
+
+
 @pytest.mark.parametrize("path", [1, 2])
 def test_mean_mode(G, path):
     X, want = case(4, 64, 130, mean=True)

@@ -283,6 +283,39 @@ def test_identity_and_state(G, N, path):
         assert same(run(si, 7, 7 + A), want)
 
 
+@pytest.mark.parametrize("mean", [False, True])
+def test_the_carried_state_through_cuts_set_length_and_reset(G, mean):
+    """the state the integrating blocks share (csrc/leaf_integrator.hpp) behind the public entries alone, at N = 7 (the scalar leaf kernel, a carry that is no
+    multiple of four floats) and A = 33: calls of 1, 31, 1, 0, 33, 2 frames, set_length(2) in mid-integration, 3 frames, one more, reset(), 4 frames -- every
+    call returns what pending said, and the rows are the ordered definition of the segments between the drops, bit for bit"""
+    N, A = 7, 33
+    m = np.abs(SO.signal(76 * N, 11)).astype(np.float32).reshape(76, N) ** 2
+    md = dev(m)
+    si, at, got = G.SpectrumIntegrator(N, A, mean), 0, []
+
+    def feed(n):
+        nonlocal at
+        want = si.pending(n)
+        out = si.process_bulk(md[at:at + n])
+        assert out.shape == (want, N)
+        got.append(out)
+        at += n
+
+    for n in (1, 31, 1, 0, 33, 2):
+        feed(n)
+    assert at == 68 and si.pending(A - 2) == 1
+    si.set_length(2)  # frames 66, 67 are dropped
+    assert si.pending(1) == 0 and si.pending(2) == 1
+    feed(3)
+    feed(1)
+    si.reset()
+    assert si.pending(1) == 0
+    feed(4)
+    assert at == 76
+    want = np.concatenate([SO.integrate_ordered(m[:68], A, mean), SO.integrate_ordered(m[68:72], 2, mean), SO.integrate_ordered(m[72:], 2, mean)])
+    assert want.shape == (6, N) and same(torch.cat(got), torch.from_numpy(want))
+
+
 @pytest.mark.parametrize("path", PATHS)
 @pytest.mark.parametrize("N", [64, 1024, 8192])
 def test_non_finite_values_reach_exactly_their_integration(G, N, path):
