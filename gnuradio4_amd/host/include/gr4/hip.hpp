@@ -60,6 +60,32 @@ struct Options {
 };
 inline Options& options() { static Options o; return o; }
 
+// An owning library handle: gr4hip_X_t* with gr4hip_X_destroy as its deleter.  It converts to the raw pointer, so the C-ABI calls take it as it is, and
+// out() is the slot of gr4hip_X_create: what the handle held is released first, what the call leaves there is taken over.  A constructor that throws
+// after its create has succeeded releases the handle with the members already built.
+// The slot hands over when it dies, at the END of the full expression that holds out(): give the create call a statement (or an if-init) of its own, as in
+// check(gr4hip_X_create(h.out(), ...), "..."), and use h from the next statement on -- within the same expression the handle is still empty.
+template <typename T, auto Destroy>
+class Handle {
+    struct Release { void operator()(T* p) const noexcept { Destroy(p); } };
+    std::unique_ptr<T, Release> _p;
+    struct Slot {
+        Handle& owner;
+        T*      raw = nullptr;
+        operator T**() { return &raw; }
+        ~Slot() { owner._p.reset(raw); }
+    };
+
+public:
+    Handle() = default;
+    explicit Handle(T* p) : _p(p) {}
+    [[nodiscard]] T* get() const noexcept { return _p.get(); }
+    operator T*() const noexcept { return _p.get(); }
+    void reset(T* p = nullptr) noexcept { _p.reset(p); }
+    [[nodiscard]] Slot out() { _p.reset(); return Slot{*this}; }
+};
+using EwiseHandle = Handle<gr4hip_ewise_t, gr4hip_ewise_destroy>;
+
 // A run of per-sample blocks -- MathOpImpl<T, op> (Math.hpp:38-56), Rotator<complex<float>> (Rotator.hpp:51-61) -- as data: what Merge<A, "out", B, "in">
 // (BlockMerging.hpp:126-240) is at compile time upstream.  One program = one launch (gr4hip_ewise_*), or no launch at all when a neighbouring filter takes it
 // as its load / store hook (Stage::absorb).
@@ -82,13 +108,14 @@ struct EwiseProgram {
         for (const auto& o : ops) d += std::string(d.empty() ? "" : ",") + names[std::clamp(o.kind, 0, 4)];
         return d;
     }
-    // a fresh library handle (the caller destroys it; a filter that takes the program as a hook copies it)
-    [[nodiscard]] gr4hip_ewise_t* make() const {
-        gr4hip_ewise_t* h = nullptr;
-        if (const int rc = gr4hip_ewise_create(&h, dtype); rc < 0) throw std::runtime_error(std::string("gr4hip_ewise_create: ") + gr4hip_last_error());
+    // a fresh library handle (a filter that takes the program as a hook copies it); none for an empty program where `or_none` says so: the hooks' "no program"
+    [[nodiscard]] EwiseHandle make(bool or_none = false) const {
+        EwiseHandle h;
+        if (or_none && empty()) return h;
+        if (const int rc = gr4hip_ewise_create(h.out(), dtype); rc < 0) throw std::runtime_error(std::string("gr4hip_ewise_create: ") + gr4hip_last_error());
         for (const auto& o : ops) {
             const int rc = o.kind == kRotator ? gr4hip_ewise_append_rotator(h, o.inc, o.ph0) : gr4hip_ewise_append_const(h, o.kind, o.value.data());
-            if (rc < 0) { gr4hip_ewise_destroy(h); throw std::runtime_error(std::string("gr4hip_ewise_append: ") + gr4hip_last_error()); }
+            if (rc < 0) throw std::runtime_error(std::string("gr4hip_ewise_append: ") + gr4hip_last_error());
         }
         return h;
     }
@@ -265,17 +292,14 @@ public:
 // the hooks of a gr4hip_fir handle follow `ab` (gr4hip_fir_set_prologue / _epilogue: the library copies the programs)
 inline void apply_fir_hooks(gr4hip_fir_t* h, const AbsorbedPrograms& ab) {
     for (int pro = 1; pro >= 0; --pro) {
-        const EwiseProgram& p    = pro ? ab.pre : ab.post;
-        gr4hip_ewise_t*     prog = p.empty() ? nullptr : p.make();
-        const int           rc   = pro ? gr4hip_fir_set_prologue(h, prog) : gr4hip_fir_set_epilogue(h, prog);
-        if (prog) gr4hip_ewise_destroy(prog);
-        check(rc, pro ? "gr4hip_fir_set_prologue" : "gr4hip_fir_set_epilogue");
+        const EwiseHandle prog = (pro ? ab.pre : ab.post).make(true);
+        check(pro ? gr4hip_fir_set_prologue(h, prog) : gr4hip_fir_set_epilogue(h, prog), pro ? "gr4hip_fir_set_prologue" : "gr4hip_fir_set_epilogue");
     }
 }
 
 template <typename T>
 struct FirStage final : Stage {
-    gr4hip_fir_t* h = nullptr;
+    Handle<gr4hip_fir_t, gr4hip_fir_destroy> h;
     std::vector<float> taps;
     std::size_t        decim = 1;
     AbsorbedPrograms   absorbed;
@@ -285,11 +309,10 @@ struct FirStage final : Stage {
     explicit FirStage(const Taps& b, std::size_t decimate = 1) : taps(b.begin(), b.end()), decim(std::max<std::size_t>(1, decimate)) {
         in_bytes = out_bytes = sizeof(T);
         in_chunk = decim;
-        check(gr4hip_fir_create(&h, kDtype, taps.data(), taps.size(), decim), "gr4hip_fir_create");
+        check(gr4hip_fir_create(h.out(), kDtype, taps.data(), taps.size(), decim), "gr4hip_fir_create");
         check(gr4hip_fir_set_guard_mode(h, options().guard_mode), "gr4hip_fir_set_guard_mode");
         name();
     }
-    ~FirStage() override { gr4hip_fir_destroy(h); }
     void name() { _kind = std::string(gr::detail::is_complex<T>::value ? "fir_c32" : "fir_f32") + (decim > 1 ? "/" + std::to_string(decim) : std::string()) + absorbed.suffix(); }
     // the neighbours' per-sample ops in this filter's launch: gains fold into the taps, the rest are load / store hooks (include/gr4hip.h)
     bool absorb(const EwiseProgram& p, bool before) override {
@@ -314,7 +337,7 @@ struct FirStage final : Stage {
 };
 
 struct PowerSpectrumStage final : Stage {
-    gr4hip_fft_t* h = nullptr;
+    Handle<gr4hip_fft_t, gr4hip_fft_destroy> h;
     std::size_t   N;
     int           window;
     EwiseProgram  post; // float blocks behind |X|^2 (normalisation, an offset): in the transform's launch (gr4hip_fft_set_epilogue)
@@ -322,15 +345,11 @@ struct PowerSpectrumStage final : Stage {
     PowerSpectrumStage(std::size_t fftSize, int win) : N(fftSize), window(win) {
         in_bytes = 8; out_bytes = 4; in_chunk = out_chunk = fftSize;
         post.dtype = GR4HIP_F32;
-        check(gr4hip_fft_create(&h, GR4HIP_C32, fftSize, win, 0), "gr4hip_fft_create");
+        check(gr4hip_fft_create(h.out(), GR4HIP_C32, fftSize, win, 0), "gr4hip_fft_create");
     }
-    ~PowerSpectrumStage() override { gr4hip_fft_destroy(h); }
     std::string_view kind() const override { return _kind; }
     void apply() {
-        gr4hip_ewise_t* prog = post.empty() ? nullptr : post.make();
-        const int       rc   = gr4hip_fft_set_epilogue(h, prog);
-        if (prog) gr4hip_ewise_destroy(prog);
-        check(rc, "gr4hip_fft_set_epilogue");
+        check(gr4hip_fft_set_epilogue(h, post.make(true)), "gr4hip_fft_set_epilogue");
         _kind = post.empty() ? "power_spectrum_c32" : "power_spectrum_c32[post: " + post.describe() + "]";
     }
     bool absorb(const EwiseProgram& p, bool before) override {
@@ -348,16 +367,15 @@ struct PowerSpectrumStage final : Stage {
 
 // polyphase filter bank (gr4hip_pfb_*): PfbPowerSpectrum (|X|^2, float out) and PfbChannelizer (the spectrum, complex out); whole frames of N samples
 struct PfbStage final : Stage {
-    gr4hip_pfb_t*      h = nullptr;
+    Handle<gr4hip_pfb_t, gr4hip_pfb_destroy> h;
     std::size_t        N, P;
     bool               power;
     std::vector<float> taps;
     PfbStage(std::size_t fftSize, std::size_t tapsPerChannel, const std::vector<float>& prototype, bool mag2) : N(fftSize), P(tapsPerChannel), power(mag2), taps(prototype) {
         in_bytes = 8; out_bytes = power ? 4 : 8; in_chunk = out_chunk = fftSize;
         if (taps.size() != N * P) throw std::invalid_argument("pfb: need taps_per_channel * fftSize taps");
-        check(gr4hip_pfb_create(&h, GR4HIP_C32, N, P, taps.data(), 0), "gr4hip_pfb_create");
+        check(gr4hip_pfb_create(h.out(), GR4HIP_C32, N, P, taps.data(), 0), "gr4hip_pfb_create");
     }
-    ~PfbStage() override { gr4hip_pfb_destroy(h); }
     void set_taps(const std::vector<float>& prototype) {
         taps = prototype;
         check(gr4hip_pfb_set_taps(h, taps.data(), taps.size()), "gr4hip_pfb_set_taps"); // (the history is kept)
@@ -371,15 +389,14 @@ struct PfbStage final : Stage {
 
 // inverse transform (gr4hip_ifft_*): whole frames of N complex bins in, N complex (ifft_c32) or real (ifft_f32) samples out
 struct InverseFftStage final : Stage {
-    gr4hip_ifft_t* h = nullptr;
+    Handle<gr4hip_ifft_t, gr4hip_ifft_destroy> h;
     std::size_t    N;
     int            window;
     bool           real_out, scale;
     InverseFftStage(std::size_t fftSize, int window_, bool realOut, bool scale_) : N(fftSize), window(window_), real_out(realOut), scale(scale_) {
         in_bytes = 8; out_bytes = real_out ? 4 : 8; in_chunk = out_chunk = fftSize;
-        check(gr4hip_ifft_create(&h, real_out ? GR4HIP_F32 : GR4HIP_C32, N, window, scale ? GR4HIP_IFFT_SCALE : 0), "gr4hip_ifft_create");
+        check(gr4hip_ifft_create(h.out(), real_out ? GR4HIP_F32 : GR4HIP_C32, N, window, scale ? GR4HIP_IFFT_SCALE : 0), "gr4hip_ifft_create");
     }
-    ~InverseFftStage() override { gr4hip_ifft_destroy(h); }
     std::string_view kind() const override { return real_out ? "ifft_f32" : "ifft_c32"; }
     int enqueue(const void* in, std::size_t n, void* out, std::size_t* n_out, gr4hip_stream_t s) override {
         *n_out = (n / N) * N;
@@ -389,16 +406,15 @@ struct InverseFftStage final : Stage {
 
 // polyphase synthesis bank (gr4hip_pfb_synth_*): whole frames of N channel values in, N samples out
 struct PfbSynthStage final : Stage {
-    gr4hip_pfb_synth_t* h = nullptr;
+    Handle<gr4hip_pfb_synth_t, gr4hip_pfb_synth_destroy> h;
     std::size_t         N, P;
     bool                scale;
     std::vector<float>  taps;
     PfbSynthStage(std::size_t fftSize, std::size_t tapsPerChannel, const std::vector<float>& prototype, bool scale_) : N(fftSize), P(tapsPerChannel), scale(scale_), taps(prototype) {
         in_bytes = out_bytes = 8; in_chunk = out_chunk = fftSize;
         if (taps.size() != N * P) throw std::invalid_argument("pfb_synth: need taps_per_channel * fftSize taps");
-        check(gr4hip_pfb_synth_create(&h, N, P, taps.data(), scale ? GR4HIP_IFFT_SCALE : 0), "gr4hip_pfb_synth_create");
+        check(gr4hip_pfb_synth_create(h.out(), N, P, taps.data(), scale ? GR4HIP_IFFT_SCALE : 0), "gr4hip_pfb_synth_create");
     }
-    ~PfbSynthStage() override { gr4hip_pfb_synth_destroy(h); }
     void set_taps(const std::vector<float>& prototype) {
         taps = prototype;
         check(gr4hip_pfb_synth_set_taps(h, taps.data(), taps.size()), "gr4hip_pfb_synth_set_taps"); // (the history is kept)
@@ -414,15 +430,14 @@ struct PfbSynthStage final : Stage {
 // PowerSpectrum or PfbPowerSpectrum stage with the integrator behind it -- complex samples in, the transform's |X|^2 summed in its own launch
 // (gr4hip_fft_mag2_integrate / gr4hip_pfb_power_integrate: the values of the two stages in a row, bit for bit)
 struct IntegratorStage final : Stage {
-    gr4hip_specint_t*      h = nullptr;
+    Handle<gr4hip_specint_t, gr4hip_specint_destroy> h;
     std::size_t            N, A;
     bool                   mean;
     std::unique_ptr<Stage> front; // PowerSpectrumStage or PfbStage (|X|^2), or none
     IntegratorStage(std::size_t n_bins, std::size_t n_integrate, bool mean_, std::unique_ptr<Stage> front_ = nullptr) : N(n_bins), A(n_integrate), mean(mean_), front(std::move(front_)) {
         in_bytes = front ? 8 : 4; out_bytes = 4; in_chunk = A * N; out_chunk = N;
-        check(gr4hip_specint_create(&h, N, A, mean ? GR4HIP_SPECINT_MEAN : 0), "gr4hip_specint_create");
+        check(gr4hip_specint_create(h.out(), N, A, mean ? GR4HIP_SPECINT_MEAN : 0), "gr4hip_specint_create");
     }
-    ~IntegratorStage() override { gr4hip_specint_destroy(h); }
     std::string_view kind() const override { return !front ? "spectrum_integrator" : dynamic_cast<PfbStage*>(front.get()) ? "pfb_mag2_integrated_c32" : "power_spectrum_integrated_c32"; }
     int enqueue(const void* in, std::size_t n, void* out, std::size_t* n_out, gr4hip_stream_t s) override {
         std::size_t spectra = 0;
@@ -437,14 +452,13 @@ struct IntegratorStage final : Stage {
 
 // fir_filter<complex<float>> -> PowerSpectrum fused into one launch
 struct ChainStage final : Stage {
-    gr4hip_chain_t* h = nullptr;
+    Handle<gr4hip_chain_t, gr4hip_chain_destroy> h;
     std::size_t     N;
     ChainStage(const std::vector<float>& taps, std::size_t fftSize, int window) : N(fftSize) {
         in_bytes = 8; out_bytes = 4; in_chunk = out_chunk = fftSize;
-        check(gr4hip_chain_create(&h, taps.data(), taps.size(), fftSize, window, GR4HIP_CHAIN_AUTO), "gr4hip_chain_create");
+        check(gr4hip_chain_create(h.out(), taps.data(), taps.size(), fftSize, window, GR4HIP_CHAIN_AUTO), "gr4hip_chain_create");
         check(gr4hip_chain_set_guard_mode(h, options().guard_mode), "gr4hip_chain_set_guard_mode");
     }
-    ~ChainStage() override { gr4hip_chain_destroy(h); }
     std::string_view kind() const override { return "chain_fir_fft_mag2"; }
     int algo() const { int a = 0; gr4hip_chain_get_algo(h, &a); return a; }
     int enqueue(const void* in, std::size_t n, void* out, std::size_t* n_out, gr4hip_stream_t s) override {
@@ -492,19 +506,16 @@ struct MathConstStage final : Stage {
 
 // a run of per-sample blocks: ONE launch, the values in registers between the ops (gr4hip_ewise_process)
 struct EwiseStage final : Stage {
-    EwiseProgram    prog;
-    gr4hip_ewise_t* h = nullptr;
-    std::string     _kind;
+    EwiseProgram prog;
+    EwiseHandle  h;
+    std::string  _kind;
     explicit EwiseStage(EwiseProgram p) : prog(std::move(p)) {
         static constexpr std::size_t bytes[12] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 8, 16};
         in_bytes = out_bytes = bytes[std::clamp(prog.dtype, 0, 11)];
         rebuild();
     }
-    ~EwiseStage() override { if (h) gr4hip_ewise_destroy(h); }
     void rebuild() {
-        gr4hip_ewise_t* fresh = prog.make();
-        if (h) gr4hip_ewise_destroy(h);
-        h     = fresh;
+        h     = prog.make(); // (the old handle goes once the new one stands)
         _kind = "ewise[" + prog.describe() + "]";
     }
     std::string_view    kind() const override { return _kind; }
@@ -525,7 +536,7 @@ struct EwiseStage final : Stage {
 // neighbouring run of per-sample blocks rides in its launch: as prologue where the program's dtype is the input's, as epilogue where it is the output's.
 struct ConverterStage final : Stage {
     gr4hip_convert_params p;
-    gr4hip_convert_t*     h = nullptr;
+    Handle<gr4hip_convert_t, gr4hip_convert_destroy> h;
     EwiseProgram          pre, post;
     std::string           _kind;
     static constexpr const char* kKinds[14] = {"Convert", "ScalingConvert", "Abs", "Real", "Imag", "Arg", "RadiansToDegree", "DegreeToRadians", "ToRealImag", "RealImagToComplex",
@@ -533,17 +544,16 @@ struct ConverterStage final : Stage {
     static constexpr const char* kTypes[12] = {"u8", "u16", "u32", "u64", "i8", "i16", "i32", "i64", "f32", "f64", "c32", "c64"};
     explicit ConverterStage(const gr4hip_convert_params& params) : p(params) {
         static constexpr std::size_t bytes[12] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 8, 16};
-        check(gr4hip_convert_create(&h, &p), "gr4hip_convert_create");
+        check(gr4hip_convert_create(h.out(), &p), "gr4hip_convert_create");
         std::size_t n_in = 0, n_out = 0;
         check(gr4hip_convert_ports(h, &n_in, &n_out, &in_chunk, &out_chunk), "gr4hip_convert_ports");
-        if (n_in != 1 || n_out != 1) { gr4hip_convert_destroy(h); throw std::invalid_argument("ConverterStage: one input and one output (the two-port kinds go through the seam)"); }
+        if (n_in != 1 || n_out != 1) throw std::invalid_argument("ConverterStage: one input and one output (the two-port kinds go through the seam)");
         in_bytes  = bytes[std::clamp(p.in_dtype, 0, 11)];
         out_bytes = bytes[std::clamp(p.out_dtype, 0, 11)];
         pre.dtype  = p.in_dtype;
         post.dtype = p.out_dtype;
         name();
     }
-    ~ConverterStage() override { gr4hip_convert_destroy(h); }
     void name() {
         _kind = std::string("convert_") + kKinds[std::clamp(p.kind, 0, 13)] + "_" + kTypes[std::clamp(p.in_dtype, 0, 11)] + "_" + kTypes[std::clamp(p.out_dtype, 0, 11)];
         std::string s;
@@ -552,11 +562,8 @@ struct ConverterStage final : Stage {
         if (!s.empty()) _kind += "[" + s + "]";
     }
     void apply() { // the handle copies the programs
-        gr4hip_ewise_t* a = pre.empty() ? nullptr : pre.make();
-        gr4hip_ewise_t* b = post.empty() ? nullptr : post.make();
-        const int       ra = gr4hip_convert_set_prologue(h, a), rb = gr4hip_convert_set_epilogue(h, b);
-        if (a) gr4hip_ewise_destroy(a);
-        if (b) gr4hip_ewise_destroy(b);
+        const EwiseHandle a = pre.make(true), b = post.make(true);
+        const int         ra = gr4hip_convert_set_prologue(h, a), rb = gr4hip_convert_set_epilogue(h, b);
         check(ra, "gr4hip_convert_set_prologue");
         check(rb, "gr4hip_convert_set_epilogue");
         name();
@@ -584,7 +591,7 @@ struct ConverterStage final : Stage {
 
 // iir_filter<float, form> (one section with the user's b, a) and designed cascades
 struct IirStage final : Stage {
-    gr4hip_iir_t*      h = nullptr;
+    Handle<gr4hip_iir_t, gr4hip_iir_destroy> h;
     int                form;
     std::size_t        nsections, nb, na;
     std::vector<float> b, a;
@@ -592,16 +599,14 @@ struct IirStage final : Stage {
     std::string        _kind = "iir_f32";
     IirStage(int form_, std::size_t nsections_, const std::vector<float>& b_, std::size_t nb_, const std::vector<float>& a_, std::size_t na_)
         : form(form_), nsections(nsections_), nb(nb_), na(na_), b(b_), a(a_) {
-        check(gr4hip_iir_create(&h, form, nsections, b.data(), nb, a.data(), na), "gr4hip_iir_create");
+        check(gr4hip_iir_create(h.out(), form, nsections, b.data(), nb, a.data(), na), "gr4hip_iir_create");
     }
-    ~IirStage() override { gr4hip_iir_destroy(h); }
     void regain(double g) { // a new handle with the first section's numerator scaled (plan time: no state yet; a live stage restarts from zero state)
         std::vector<float> bs = b;
         for (std::size_t k = 0; k < nb; ++k) bs[k] = static_cast<float>(g * double(b[k]));
-        gr4hip_iir_t* fresh = nullptr;
-        check(gr4hip_iir_create(&fresh, form, nsections, bs.data(), nb, a.data(), na), "gr4hip_iir_create");
-        gr4hip_iir_destroy(h);
-        h     = fresh;
+        decltype(h) fresh;
+        check(gr4hip_iir_create(fresh.out(), form, nsections, bs.data(), nb, a.data(), na), "gr4hip_iir_create");
+        h     = std::move(fresh);
         gain  = g;
         _kind = g == 1.0 ? "iir_f32" : "iir_f32[gain folded]";
     }
@@ -623,14 +628,12 @@ template <typename T>
 struct DecimatorStage final : Stage {
     std::size_t      decim;
     EwiseProgram     absorbed; // per-sample blocks around the decimator, all applied BEHIND it (memoryless blocks commute with dropping samples): one launch
-    gr4hip_ewise_t*  h = nullptr;
+    EwiseHandle      h;
     std::string      _kind = "decimator";
     explicit DecimatorStage(std::size_t d) : decim(std::max<std::size_t>(1, d)) { in_bytes = out_bytes = sizeof(T); in_chunk = decim; out_chunk = 1; absorbed.dtype = dtype_of<T>(); }
-    ~DecimatorStage() override { if (h) gr4hip_ewise_destroy(h); }
     std::string_view kind() const override { return _kind; }
     void refresh() {
-        if (h) gr4hip_ewise_destroy(h);
-        h     = absorbed.empty() ? nullptr : absorbed.make();
+        h     = absorbed.make(true);
         _kind = absorbed.empty() ? "decimator" : "decimator[post: " + absorbed.describe() + "]";
     }
     bool absorb(const EwiseProgram& p, bool before) override {
@@ -651,15 +654,14 @@ struct DecimatorStage final : Stage {
 // interpolating FIR: polyphase kernel, n_out = n L
 template <typename T>
 struct InterpStage final : Stage {
-    gr4hip_fir_interp_t* h = nullptr;
+    Handle<gr4hip_fir_interp_t, gr4hip_fir_interp_destroy> h;
     std::size_t          L;
     std::vector<float>   taps;
     double               gain = 1.0; // neighbouring gains folded into the taps (linear)
     InterpStage(const std::vector<float>& b, std::size_t interp) : L(std::max<std::size_t>(1, interp)), taps(b) {
         in_bytes = out_bytes = sizeof(T); in_chunk = 1; out_chunk = L;
-        check(gr4hip_fir_interp_create(&h, dtype_of<T>(), b.data(), b.size(), L), "gr4hip_fir_interp_create");
+        check(gr4hip_fir_interp_create(h.out(), dtype_of<T>(), b.data(), b.size(), L), "gr4hip_fir_interp_create");
     }
-    ~InterpStage() override { gr4hip_fir_interp_destroy(h); }
     void regain(double g) {
         std::vector<float> bs(taps.size());
         for (std::size_t k = 0; k < taps.size(); ++k) bs[k] = static_cast<float>(g * double(taps[k]));
@@ -680,14 +682,13 @@ struct InterpStage final : Stage {
 // rational resampler: polyphase kernel, n_out = n / M * L
 template <typename T>
 struct ResampStage final : Stage {
-    gr4hip_resamp_t*   h = nullptr;
+    Handle<gr4hip_resamp_t, gr4hip_resamp_destroy> h;
     std::size_t        L, M;
     std::vector<float> taps;
     ResampStage(const std::vector<float>& b, std::size_t interp, std::size_t decim) : L(std::max<std::size_t>(1, interp)), M(std::max<std::size_t>(1, decim)), taps(b) {
         in_bytes = out_bytes = sizeof(T); in_chunk = M; out_chunk = L;
-        check(gr4hip_resamp_create(&h, dtype_of<T>(), taps.data(), taps.size(), L, M), "gr4hip_resamp_create");
+        check(gr4hip_resamp_create(h.out(), dtype_of<T>(), taps.data(), taps.size(), L, M), "gr4hip_resamp_create");
     }
-    ~ResampStage() override { gr4hip_resamp_destroy(h); }
     void set_taps(const std::vector<float>& b) {
         taps = b;
         check(gr4hip_resamp_set_taps(h, taps.data(), taps.size()), "gr4hip_resamp_set_taps"); // (the history is kept)
@@ -698,14 +699,13 @@ struct ResampStage final : Stage {
 
 // complex-tap FIR (complex data, direct and decimating): gr4hip_cfir_*, n_out = n / decim
 struct CfirStage final : Stage {
-    gr4hip_cfir_t*     h = nullptr;
+    Handle<gr4hip_cfir_t, gr4hip_cfir_destroy> h;
     std::size_t        decim;
     std::vector<float> taps; // interleaved {re, im}
     CfirStage(const std::vector<float>& interleaved, std::size_t decimate) : decim(std::max<std::size_t>(1, decimate)), taps(interleaved) {
         in_bytes = out_bytes = 8; in_chunk = decim; out_chunk = 1;
-        check(gr4hip_cfir_create(&h, taps.data(), taps.size() / 2, decim), "gr4hip_cfir_create");
+        check(gr4hip_cfir_create(h.out(), taps.data(), taps.size() / 2, decim), "gr4hip_cfir_create");
     }
-    ~CfirStage() override { gr4hip_cfir_destroy(h); }
     void set_taps(const std::vector<float>& interleaved) {
         taps = interleaved;
         check(gr4hip_cfir_set_taps(h, taps.data(), taps.size() / 2), "gr4hip_cfir_set_taps"); // (the history is kept)
@@ -715,11 +715,11 @@ struct CfirStage final : Stage {
 };
 
 struct RotatorStage final : Stage {
-    gr4hip_rotator_t* h = nullptr;
+    Handle<gr4hip_rotator_t, gr4hip_rotator_destroy> h;
     EwiseProgram      prog; // the closed-form rotator as a per-sample op (empty with the reference's recurrence: that one is sequential and stays a stage of its own)
     RotatorStage(float phase_increment, float initial_phase) {
         in_bytes = out_bytes = 8;
-        check(gr4hip_rotator_create(&h, phase_increment, initial_phase), "gr4hip_rotator_create");
+        check(gr4hip_rotator_create(h.out(), phase_increment, initial_phase), "gr4hip_rotator_create");
         if (options().rotator_reference_recurrence) check(gr4hip_rotator_set_algo(h, GR4HIP_ROTATOR_RECURRENCE), "gr4hip_rotator_set_algo");
         else if (std::isfinite(phase_increment) && std::isfinite(initial_phase)) {
             prog.dtype = GR4HIP_C32;
@@ -730,7 +730,6 @@ struct RotatorStage final : Stage {
             prog.ops.push_back(op);
         }
     }
-    ~RotatorStage() override { gr4hip_rotator_destroy(h); }
     const EwiseProgram* program() const override { return prog.empty() ? nullptr : &prog; }
     std::string_view kind() const override { return "rotator_c32"; }
     int enqueue(const void* in, std::size_t n, void* out, std::size_t* n_out, gr4hip_stream_t s) override {
@@ -741,12 +740,11 @@ struct RotatorStage final : Stage {
 
 // FrequencyEstimator{TimeDomain,FrequencyDomain}<float>: one estimate per chunk; a settings change keeps the last estimate (gr4hip_freqest_set_params)
 struct FreqEstStage final : Stage {
-    gr4hip_freqest_t* h = nullptr;
+    Handle<gr4hip_freqest_t, gr4hip_freqest_destroy> h;
     FreqEstStage(int method, const gr4hip_freqest_params& p) {
         in_bytes = out_bytes = 4; in_chunk = p.chunk; out_chunk = 1;
-        check(gr4hip_freqest_create(&h, method, &p), "gr4hip_freqest_create");
+        check(gr4hip_freqest_create(h.out(), method, &p), "gr4hip_freqest_create");
     }
-    ~FreqEstStage() override { gr4hip_freqest_destroy(h); }
     bool set_params(const gr4hip_freqest_params& p) {
         if (p.chunk != in_chunk) return false;
         check(gr4hip_freqest_set_params(h, &p), "gr4hip_freqest_set_params");
@@ -760,12 +758,11 @@ struct FreqEstStage final : Stage {
 
 // ---- the float64 instantiations the reference registers (time_domain_filter.hpp:20, 57-60; Rotator.hpp:15; fourier/fft.hpp:29): plain FP64 kernels
 struct Fir64Stage final : Stage {
-    gr4hip_fir64_t* h = nullptr;
+    Handle<gr4hip_fir64_t, gr4hip_fir64_destroy> h;
     explicit Fir64Stage(const std::vector<double>& b) {
         in_bytes = out_bytes = sizeof(double);
-        check(gr4hip_fir64_create(&h, b.data(), b.size(), 1), "gr4hip_fir64_create");
+        check(gr4hip_fir64_create(h.out(), b.data(), b.size(), 1), "gr4hip_fir64_create");
     }
-    ~Fir64Stage() override { gr4hip_fir64_destroy(h); }
     void set_taps(const std::vector<double>& b) { check(gr4hip_fir64_set_taps(h, b.data(), b.size()), "gr4hip_fir64_set_taps"); }
     std::string_view kind() const override { return "fir_f64"; }
     int enqueue(const void* in, std::size_t n, void* out, std::size_t* n_out, gr4hip_stream_t s) override {
@@ -773,12 +770,11 @@ struct Fir64Stage final : Stage {
     }
 };
 struct Iir64Stage final : Stage {
-    gr4hip_iir64_t* h = nullptr;
+    Handle<gr4hip_iir64_t, gr4hip_iir64_destroy> h;
     Iir64Stage(int form, const std::vector<double>& b, const std::vector<double>& a) {
         in_bytes = out_bytes = sizeof(double);
-        check(gr4hip_iir64_create(&h, form, 1, b.data(), b.size(), a.data(), a.size()), "gr4hip_iir64_create");
+        check(gr4hip_iir64_create(h.out(), form, 1, b.data(), b.size(), a.data(), a.size()), "gr4hip_iir64_create");
     }
-    ~Iir64Stage() override { gr4hip_iir64_destroy(h); }
     std::string_view kind() const override { return "iir_f64"; }
     int enqueue(const void* in, std::size_t n, void* out, std::size_t* n_out, gr4hip_stream_t s) override {
         *n_out = n;
@@ -786,12 +782,11 @@ struct Iir64Stage final : Stage {
     }
 };
 struct Rotator64Stage final : Stage {
-    gr4hip_rotator64_t* h = nullptr;
+    Handle<gr4hip_rotator64_t, gr4hip_rotator64_destroy> h;
     Rotator64Stage(double phase_increment, double initial_phase) {
         in_bytes = out_bytes = 16;
-        check(gr4hip_rotator64_create(&h, phase_increment, initial_phase), "gr4hip_rotator64_create");
+        check(gr4hip_rotator64_create(h.out(), phase_increment, initial_phase), "gr4hip_rotator64_create");
     }
-    ~Rotator64Stage() override { gr4hip_rotator64_destroy(h); }
     std::string_view kind() const override { return "rotator_c64"; }
     int enqueue(const void* in, std::size_t n, void* out, std::size_t* n_out, gr4hip_stream_t s) override {
         *n_out = n;
@@ -802,8 +797,8 @@ struct Rotator64Stage final : Stage {
 // BasicFilterProto<float, ...>: designed FIR (polyphase when decimating: only the kept outputs are computed) or designed IIR cascade at the
 // full rate followed by the keep-every-D-th step (time_domain_filter.hpp:190-204)
 struct BasicFilterStage final : Stage {
-    gr4hip_fir_t*    fir = nullptr;
-    gr4hip_iir_t*    iir = nullptr;
+    Handle<gr4hip_fir_t, gr4hip_fir_destroy> fir;
+    Handle<gr4hip_iir_t, gr4hip_iir_destroy> iir;
     std::size_t      decim;
     int              dtype; // GR4HIP_F32 as registered upstream, or GR4HIP_C32 (complex data, the designed real taps: FIR designs only)
     DevBuf           tmp;
@@ -813,16 +808,15 @@ struct BasicFilterStage final : Stage {
         in_chunk = decim; out_chunk = 1;
         in_bytes = out_bytes = dtype == GR4HIP_C32 ? 8 : 4;
         if (d.fir) {
-            check(gr4hip_fir_create(&fir, dtype, d.taps.data(), d.taps.size(), decim), "gr4hip_fir_create");
+            check(gr4hip_fir_create(fir.out(), dtype, d.taps.data(), d.taps.size(), decim), "gr4hip_fir_create");
         } else {
             if (dtype != GR4HIP_F32) throw std::invalid_argument("BasicFilter<complex<float>> on the device: FIR designs only");
             std::vector<float> b, a;
             for (std::size_t s = 0; s < d.b.size(); ++s) { b.insert(b.end(), d.b[s].begin(), d.b[s].end()); a.insert(a.end(), d.a[s].begin(), d.a[s].end()); }
-            check(gr4hip_iir_create(&iir, GR4HIP_DF_II, d.b.size(), b.data(), 3, a.data(), 3), "gr4hip_iir_create");
+            check(gr4hip_iir_create(iir.out(), GR4HIP_DF_II, d.b.size(), b.data(), 3, a.data(), 3), "gr4hip_iir_create");
         }
         name();
     }
-    ~BasicFilterStage() override { if (fir) gr4hip_fir_destroy(fir); if (iir) gr4hip_iir_destroy(iir); }
     void name() { _kind = std::string(fir ? (decim > 1 ? "basic_fir_decim" : "basic_fir") : (decim > 1 ? "basic_iir_decim" : "basic_iir")) + absorbed.suffix(); }
     bool absorb(const EwiseProgram& p, bool before) override { // designed FIR: the neighbours ride in the filter's launch (gains in the taps, the rest as hooks)
         if (!fir || !absorbed.take(p, before, dtype)) return false;
@@ -862,21 +856,79 @@ inline int window_id(const std::string& w) { // gr::algorithm::window::TypeNames
 }
 
 // ---------------------------------------------------------------------------------------------- per-block offload at the seam
+// Where the rows of one transfer lie (no HIP in here): `rows` rows of `bytes` bytes, each starting at a multiple of `align` bytes -- 1: packed tightly; 256: the
+// converter seam, whose every port region starts 256-byte aligned.  One copy moves the rows with the gaps between them, not the gap behind the last.
+struct RowLayout {
+    std::size_t rows, bytes, stride;
+    constexpr RowLayout(std::size_t rows_, std::size_t bytes_, std::size_t align = 1) : rows(rows_), bytes(bytes_), stride((bytes_ + align - 1) / align * align) {}
+    [[nodiscard]] constexpr std::size_t offset(std::size_t k) const { return k * stride; }
+    [[nodiscard]] constexpr std::size_t copy_bytes() const { return rows ? (rows - 1) * stride + bytes : 0; }
+    [[nodiscard]] constexpr std::size_t alloc_bytes() const { return rows * stride; }
+};
+
 struct Offload { // state behind Block::_device_state (owned by the block through a shared_ptr<void> with this type's deleter)
     virtual ~Offload() = default;
     std::unique_ptr<Stage> stage;
     DevBuf                 d_in, d_out, h_in{true}, h_out{true};
     int                    device = 0;
     std::size_t            settings_generation = 0; // Block::_settings_generation the stage was built (or refreshed) for
+
+    // ---- the transfers of the hand-written seams: host spans -> h_in -> d_in in ONE copy, the launch writes into d_out, the wanted rows -> h_out and one sync
+    template <typename RowSource> // row(k): where row k's bytes are on the host
+    char* upload(const RowLayout& in, RowSource&& row) {
+        char* hin = static_cast<char*>(h_in.ensure(in.alloc_bytes()));
+        for (std::size_t k = 0; k < in.rows; ++k) std::memcpy(hin + in.offset(k), row(k), in.bytes);
+        char* din = static_cast<char*>(d_in.ensure(in.alloc_bytes()));
+        check(gr4hip_memcpy_h2d(din, hin, in.copy_bytes(), nullptr), "h2d");
+        return din;
+    }
+    char* upload(const void* span, std::size_t bytes) { return upload(RowLayout(1, bytes), [span](std::size_t) { return span; }); }
+    char* output(const RowLayout& out) { return static_cast<char*>(d_out.ensure(out.alloc_bytes())); }
+    char* output(std::size_t bytes) { return output(RowLayout(1, bytes)); }
+    template <typename Wanted> // wanted(k): is row k copied back?  (a row nobody reads was a NULL pointer in the launch)
+    const char* download(const RowLayout& out, Wanted&& wanted) {
+        char* hout = static_cast<char*>(h_out.ensure(out.alloc_bytes()));
+        for (std::size_t k = 0; k < out.rows; ++k)
+            if (wanted(k)) check(gr4hip_memcpy_d2h(hout + out.offset(k), static_cast<const char*>(d_out.p) + out.offset(k), out.bytes, nullptr), "d2h");
+        check(gr4hip_stream_synchronize(nullptr), "sync");
+        return hout;
+    }
+    const char* download(std::size_t bytes) { return download(RowLayout(1, bytes), [](std::size_t) { return true; }); }
 };
+// the state of a seam that owns a library handle `h`, with the block's own extras beside it (the key its handle was made for, further buffers)
+struct NoExtras {};
+template <typename T, auto Destroy, typename Extras = NoExtras>
+struct SeamState final : Offload, Extras {
+    Handle<T, Destroy> h;
+};
+// into a port's write span, if anybody reads it
+template <typename Port>
+void to_port(Port& port, std::size_t nOut, const void* src, std::size_t bytes) {
+    if (port.connected()) std::memcpy(port.buffer->write_span(nOut).data(), src, bytes);
+}
+template <typename Ports>
+[[nodiscard]] bool any_connected(Ports& ports) {
+    return std::any_of(ports.begin(), ports.end(), [](auto& port) { return port.connected(); });
+}
+// the frame of every seam: what the body throws becomes the block's log line and work::Status::ERROR -- never a silent host fallback
+template <typename BlockT, typename Body>
+work::Status seam(BlockT& blk, Body&& body) {
+    try {
+        body();
+        return work::Status::OK;
+    } catch (const std::exception& e) {
+        blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
+        return work::Status::ERROR;
+    }
+}
 // the block's Offload (created on first use, on the block's device); every call makes the block's device the calling thread's current device:
 // one scheduler thread drives blocks of several "gpu:hip:<i>" domains, and allocations, attributes and launches follow the CURRENT device
-template <typename State = Offload, typename BlockT>
-State* offload_state(BlockT& blk) {
-    auto* st = static_cast<State*>(static_cast<Offload*>(blk._device_state.get()));
+template <typename St = Offload, typename BlockT>
+St* offload_state(BlockT& blk) {
+    auto* st = static_cast<St*>(static_cast<Offload*>(blk._device_state.get()));
     if (!st) {
         check(gr4hip_set_device(blk._domain.index), "gr4hip_set_device");
-        st         = new State();
+        st         = new St();
         st->device = blk._domain.index;
         blk._device_state = std::shared_ptr<void>(static_cast<Offload*>(st), [](void* p) { delete static_cast<Offload*>(p); });
     }
@@ -889,7 +941,7 @@ State* offload_state(BlockT& blk) {
 // through Block::_settings_generation (applySettings and settings-by-tag bump it): a stage is never used with stale taps or constants.
 template <typename BlockT, typename MakeStage, typename UpdateStage = std::nullptr_t>
 work::Status offload_work(BlockT& blk, std::size_t nIn, std::size_t nOut, MakeStage&& make, UpdateStage&& update = nullptr) {
-    try {
+    return seam(blk, [&] {
         Offload* st = offload_state(blk);
         if (!st->stage) {
             st->stage               = make(blk);
@@ -920,11 +972,7 @@ work::Status offload_work(BlockT& blk, std::size_t nIn, std::size_t nOut, MakeSt
         check(gr4hip_memcpy_d2h(dst, st->d_out.p, nOut * sizeof(TOut), nullptr), "d2h");
         check(gr4hip_stream_synchronize(nullptr), "sync");
         if (!out_locked) CopyPool::instance().copy(os.data(), st->h_out.p, nOut * sizeof(TOut));
-        return work::Status::OK;
-    } catch (const std::exception& e) {
-        blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
-        return work::Status::ERROR; // never a silent host fallback
-    }
+    });
 }
 
 template <typename BlockT>
@@ -1108,21 +1156,18 @@ struct Kernel<gr::filter::FrequencyEstimatorFrequencyDomain<float, Args...>> {
 // spans go to HBM, one gr4hip_iqdemod_process, three spans back.  A settings change that named a filter key re-initialises the handle's filters; any other keeps them.
 template <typename T, typename... Args>
 struct Kernel<gr::filter::IQDemodulator<T, Args...>> {
-    using B = gr::filter::IQDemodulator<T, Args...>;
-    struct State final : Offload {
-        gr4hip_iqdemod_t* h = nullptr;
-        ~State() override { if (h) gr4hip_iqdemod_destroy(h); }
-    };
+    using B     = gr::filter::IQDemodulator<T, Args...>;
+    using State = SeamState<gr4hip_iqdemod_t, gr4hip_iqdemod_destroy>;
     static gr4hip_iqdemod_params params(B& b) {
         return {b.sample_rate, b.f_high_pass, b.f_low_pass, static_cast<int>(b.phase_unit), b.invert_phase ? 1 : 0, static_cast<int>(b.derivative_method),
                 static_cast<double>(b.epsilon), b.chunk()};
     }
     static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
-        try {
+        return seam(blk, [&] {
             State*     st = offload_state<State>(blk);
             const auto p  = params(blk);
             if (!st->h) {
-                check(gr4hip_iqdemod_create(&st->h, dtype_of<T>(), &p), "gr4hip_iqdemod_create");
+                check(gr4hip_iqdemod_create(st->h.out(), dtype_of<T>(), &p), "gr4hip_iqdemod_create");
                 st->settings_generation = blk._settings_generation;
                 blk._filters_changed    = false;
             } else if (st->settings_generation != blk._settings_generation) {
@@ -1131,28 +1176,16 @@ struct Kernel<gr::filter::IQDemodulator<T, Args...>> {
                 blk._filters_changed    = false;
             }
             const std::size_t bi = nIn * sizeof(T), bo = nOut * sizeof(T);
-            char*             hin = static_cast<char*>(st->h_in.ensure(2 * bi));
-            std::memcpy(hin, blk.ref.buffer->read_span(nIn).data(), bi);
-            std::memcpy(hin + bi, blk.resp.buffer->read_span(nIn).data(), bi);
-            char* din = static_cast<char*>(st->d_in.ensure(2 * bi));
-            check(gr4hip_memcpy_h2d(din, hin, 2 * bi, nullptr), "h2d");
-            char*       dout     = static_cast<char*>(st->d_out.ensure(3 * bo));
-            std::size_t produced = 0;
+            const void*       rows[2] = {blk.ref.buffer->read_span(nIn).data(), blk.resp.buffer->read_span(nIn).data()};
+            char*             din     = st->upload(RowLayout(2, bi), [&](std::size_t k) { return rows[k]; });
+            char*             dout    = st->output(3 * bo);
+            std::size_t       produced = 0;
             check(gr4hip_iqdemod_process(st->h, din, din + bi, nIn, dout, dout + bo, dout + 2 * bo, &produced, nullptr), "gr4hip_iqdemod_process");
             if (produced != nOut) throw std::runtime_error("IQDemodulator: the work loop must hand over whole chunks");
-            const char* hout = static_cast<const char*>(st->h_out.ensure(3 * bo));
-            check(gr4hip_memcpy_d2h(const_cast<char*>(hout), dout, 3 * bo, nullptr), "d2h");
-            check(gr4hip_stream_synchronize(nullptr), "sync");
-            std::size_t k = 0;
-            for (auto* port : {&blk.amplitude, &blk.phase, &blk.frequency}) {
-                if (port->connected()) std::memcpy(port->buffer->write_span(nOut).data(), hout + k * bo, bo);
-                ++k;
-            }
-            return work::Status::OK;
-        } catch (const std::exception& e) {
-            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
-            return work::Status::ERROR; // never a silent host fallback
-        }
+            const char* hout = st->download(3 * bo);
+            std::size_t k    = 0;
+            for (auto* port : {&blk.amplitude, &blk.phase, &blk.frequency}) to_port(*port, nOut, hout + k++ * bo, bo);
+        });
     }
 };
 
@@ -1167,10 +1200,7 @@ struct Kernel<B> {
     static constexpr std::size_t NI = std::tuple_size_v<InTuple>, NO = std::tuple_size_v<OutTuple>;
     using TI = typename std::decay_t<std::tuple_element_t<0, InTuple>>::value_type;
     using TO = typename std::decay_t<std::tuple_element_t<0, OutTuple>>::value_type;
-    struct State final : Offload {
-        gr4hip_convert_t* h = nullptr;
-        ~State() override { if (h) gr4hip_convert_destroy(h); }
-    };
+    using State = SeamState<gr4hip_convert_t, gr4hip_convert_destroy>;
     static gr4hip_convert_params params(B& b) {
         gr4hip_convert_params p{B::kConvertKind, dtype_of<TI>(), dtype_of<TO>(), 1.0};
         if constexpr (requires { b.scale; }) p.scale = static_cast<double>(b.scale);
@@ -1178,180 +1208,127 @@ struct Kernel<B> {
     }
     static std::unique_ptr<Stage> make_stage(B& b) requires(NI == 1 && NO == 1) { return std::make_unique<ConverterStage>(params(b)); }
     static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
-        try {
+        return seam(blk, [&] {
             State*     st = offload_state<State>(blk);
             const auto p  = params(blk);
             if (!st->h) {
-                check(gr4hip_convert_create(&st->h, &p), "gr4hip_convert_create");
+                check(gr4hip_convert_create(st->h.out(), &p), "gr4hip_convert_create");
                 st->settings_generation = blk._settings_generation;
             } else if (st->settings_generation != blk._settings_generation) {
                 if (p.kind == GR4HIP_SCALING_CONVERT) check(gr4hip_convert_set_scale(st->h, p.scale), "gr4hip_convert_set_scale");
                 st->settings_generation = blk._settings_generation;
             }
-            const std::size_t bi = nIn * sizeof(TI), bo = nOut * sizeof(TO);
-            const auto        up = [](std::size_t b) { return (b + 255) / 256 * 256; }; // every port's region starts 256-byte aligned
-            char*             hin = static_cast<char*>(st->h_in.ensure(NI * up(bi)));
-            char*             din = static_cast<char*>(st->d_in.ensure(NI * up(bi)));
-            char*             dout = static_cast<char*>(st->d_out.ensure(NO * up(bo)));
-            char*             hout = static_cast<char*>(st->h_out.ensure(NO * up(bo)));
-            const void*       ins[NI];
-            void*             outs[NO];
-            bool              wired[NO];
-            std::size_t       k = 0;
-            std::apply([&](auto&... port) { ((std::memcpy(hin + k * up(bi), port.buffer->read_span(nIn).data(), bi), ins[k] = din + k * up(bi), ++k), ...); }, blk.inPorts());
-            check(gr4hip_memcpy_h2d(din, hin, (NI - 1) * up(bi) + bi, nullptr), "h2d");
-            k = 0;
-            std::apply([&](auto&... port) { ((wired[k] = port.connected(), outs[k] = wired[k] ? dout + k * up(bo) : nullptr, ++k), ...); }, blk.outPorts());
+            const RowLayout in(NI, nIn * sizeof(TI), 256), out(NO, nOut * sizeof(TO), 256); // every port's region starts 256-byte aligned
+            const void*     rows[NI];
+            const void*     ins[NI];
+            void*           outs[NO];
+            bool            wired[NO];
+            std::size_t     k = 0;
+            std::apply([&](auto&... port) { ((rows[k++] = port.buffer->read_span(nIn).data()), ...); }, blk.inPorts());
+            char* din = st->upload(in, [&](std::size_t r) { return rows[r]; });
+            for (k = 0; k < NI; ++k) ins[k] = din + in.offset(k);
+            char* dout = st->output(out);
+            k          = 0;
+            std::apply([&](auto&... port) { ((wired[k] = port.connected(), outs[k] = wired[k] ? dout + out.offset(k) : nullptr, ++k), ...); }, blk.outPorts());
             std::size_t produced = 0;
             check(gr4hip_convert_process(st->h, ins, outs, nIn, &produced, nullptr), "gr4hip_convert_process");
             if (produced != nOut) throw std::runtime_error("converter: the work loop must hand over whole chunks");
-            for (k = 0; k < NO; ++k)
-                if (wired[k]) check(gr4hip_memcpy_d2h(hout + k * up(bo), dout + k * up(bo), bo, nullptr), "d2h");
-            check(gr4hip_stream_synchronize(nullptr), "sync");
-            k = 0;
-            std::apply([&](auto&... port) { ((wired[k] ? (void)std::memcpy(port.buffer->write_span(nOut).data(), hout + k * up(bo), bo) : (void)0, ++k), ...); }, blk.outPorts());
-            return work::Status::OK;
-        } catch (const std::exception& e) {
-            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
-            return work::Status::ERROR; // never a silent host fallback
-        }
+            const char* hout = st->download(out, [&](std::size_t r) { return wired[r]; });
+            k                = 0;
+            std::apply([&](auto&... port) { ((to_port(port, nOut, hout + out.offset(k), out.bytes), ++k), ...); }, blk.outPorts());
+        });
     }
 };
 
+namespace detail {
+// the electrical blocks' ports come as vectors of N phases.  In: G such vectors are G * N rows of d_in, group after group
+template <typename T, std::size_t G>
+char* phase_rows(Offload* st, const std::array<std::vector<gr::PortIn<T>>*, G>& groups, std::size_t N, std::size_t nIn) {
+    return st->upload(RowLayout(G * N, nIn * sizeof(T)), [&](std::size_t r) { return static_cast<const void*>((*groups[r / N])[r % N].buffer->read_span(nIn).data()); });
+}
+// Out: quantity q's N phases are row q of d_out -- d[q] in the launch, NULL when none of its ports is connected, and then neither computed nor copied back
+template <typename T, std::size_t Q>
+struct PhaseOutputs {
+    std::array<std::vector<gr::PortOut<T>>*, Q> ports;
+    RowLayout                                   rows;
+    std::array<T*, Q>                           d{};
+    PhaseOutputs(Offload* st, const std::array<std::vector<gr::PortOut<T>>*, Q>& ports_, std::size_t N, std::size_t nOut) : ports(ports_), rows(Q, N * nOut * sizeof(T)) {
+        char* dout = st->output(rows);
+        for (std::size_t q = 0; q < Q; ++q) d[q] = any_connected(*ports[q]) ? reinterpret_cast<T*>(dout + rows.offset(q)) : nullptr;
+    }
+    void deliver(Offload* st, std::size_t nOut) {
+        const std::size_t bo   = nOut * sizeof(T);
+        const char*       hout = st->download(rows, [&](std::size_t q) { return d[q] != nullptr; });
+        for (std::size_t q = 0; q < Q; ++q)
+            for (std::size_t k = 0; d[q] && k < ports[q]->size(); ++k) to_port((*ports[q])[k], nOut, hout + rows.offset(q) + k * bo, bo);
+    }
+};
+} // namespace detail
 // PowerMetrics<float, N>: 2 N inputs, 5 N outputs at the seam, like IQDemodulator: the N voltage and N current spans go to HBM as rows of one buffer in one copy,
 // one gr4hip_powermetrics_process, one copy back per output; an output no port of which is connected has a NULL pointer in the call and is not copied.  Every settings generation rebuilds
 // the handle's filters (settingsChanged, PowerEstimators.hpp:95).
 template <std::size_t N>
 struct Kernel<gr::electrical::PowerMetrics<float, N>> {
-    using B = gr::electrical::PowerMetrics<float, N>;
-    struct State final : Offload {
-        gr4hip_powermetrics_t* h = nullptr;
-        ~State() override { if (h) gr4hip_powermetrics_destroy(h); }
-    };
+    using B     = gr::electrical::PowerMetrics<float, N>;
+    using State = SeamState<gr4hip_powermetrics_t, gr4hip_powermetrics_destroy>;
     static gr4hip_powermetrics_params params(B& b) { return {b.sample_rate, b.high_pass, b.low_pass, static_cast<std::size_t>(b.decimate), N}; }
     static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
-        try {
+        return seam(blk, [&] {
             State*     st = offload_state<State>(blk);
             const auto p  = params(blk);
             if (!st->h) {
-                check(gr4hip_powermetrics_create(&st->h, &p), "gr4hip_powermetrics_create");
+                check(gr4hip_powermetrics_create(st->h.out(), &p), "gr4hip_powermetrics_create");
                 st->settings_generation = blk._settings_generation;
             } else if (st->settings_generation != blk._settings_generation) {
                 check(gr4hip_powermetrics_set_params(st->h, &p), "gr4hip_powermetrics_set_params");
                 st->settings_generation = blk._settings_generation;
             }
-            const std::size_t bi = nIn * sizeof(float), bo = nOut * sizeof(float);
-            char*             hin = static_cast<char*>(st->h_in.ensure(2 * N * bi));
-            for (std::size_t k = 0; k < N; ++k) {
-                std::memcpy(hin + k * bi, blk.U[k].buffer->read_span(nIn).data(), bi);
-                std::memcpy(hin + (N + k) * bi, blk.I[k].buffer->read_span(nIn).data(), bi);
-            }
-            char* din = static_cast<char*>(st->d_in.ensure(2 * N * bi));
-            check(gr4hip_memcpy_h2d(din, hin, 2 * N * bi, nullptr), "h2d");
-            std::vector<gr::PortOut<float>>* ports[5] = {&blk.P, &blk.Q, &blk.S, &blk.U_rms, &blk.I_rms};
-            float*                           dptr[5];
-            char*                            dout = static_cast<char*>(st->d_out.ensure(5 * N * bo));
-            for (std::size_t q = 0; q < 5; ++q) { // an output with no connected port of any phase is skipped
-                bool any = false;
-                for (auto& port : *ports[q]) any = any || port.connected();
-                dptr[q] = any ? reinterpret_cast<float*>(dout + q * N * bo) : nullptr;
-            }
-            std::size_t produced = 0;
-            check(gr4hip_powermetrics_process(st->h, reinterpret_cast<const float*>(din), reinterpret_cast<const float*>(din + N * bi), nIn, nIn, dptr[0], dptr[1], dptr[2],
-                                              dptr[3], dptr[4], nOut, &produced, nullptr),
+            const float*                    din = reinterpret_cast<const float*>(detail::phase_rows<float, 2>(st, {&blk.U, &blk.I}, N, nIn));
+            detail::PhaseOutputs<float, 5> out(st, {&blk.P, &blk.Q, &blk.S, &blk.U_rms, &blk.I_rms}, N, nOut);
+            std::size_t                     produced = 0;
+            check(gr4hip_powermetrics_process(st->h, din, din + N * nIn, nIn, nIn, out.d[0], out.d[1], out.d[2], out.d[3], out.d[4], nOut, &produced, nullptr),
                   "gr4hip_powermetrics_process");
             if (produced != nOut) throw std::runtime_error("PowerMetrics: the work loop must hand over whole chunks");
-            char* hout = static_cast<char*>(st->h_out.ensure(5 * N * bo));
-            for (std::size_t q = 0; q < 5; ++q)
-                if (dptr[q]) check(gr4hip_memcpy_d2h(hout + q * N * bo, dout + q * N * bo, N * bo, nullptr), "d2h");
-            check(gr4hip_stream_synchronize(nullptr), "sync");
-            for (std::size_t q = 0; q < 5; ++q) {
-                if (!dptr[q]) continue;
-                for (std::size_t k = 0; k < N; ++k)
-                    if ((*ports[q])[k].connected()) std::memcpy((*ports[q])[k].buffer->write_span(nOut).data(), hout + (q * N + k) * bo, bo);
-            }
-            return work::Status::OK;
-        } catch (const std::exception& e) {
-            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
-            return work::Status::ERROR; // never a silent host fallback
-        }
+            out.deliver(st, nOut);
+        });
     }
 };
 
 // PowerFactor<T, N> and SystemUnbalance<T, N> (PowerEstimators.hpp:144-257), after the pattern of PowerMetrics: the input spans go to HBM as rows of one buffer
 // in one copy, ONE stateless launch (gr4hip_powerfactor_process / gr4hip_unbalance_process), one copy back per output that has a connected port (the others are
 // NULL pointers in the call and are not computed).  Multi-port blocks stay outside hip::plan runs: the edges between PowerMetrics and these two are host spans.
-namespace detail {
-template <typename T, std::size_t R>
-char* electrical_rows_to_device(Offload* st, const std::array<std::vector<gr::PortIn<T>>*, R>& groups, std::size_t N, std::size_t nIn) {
-    const std::size_t b   = nIn * sizeof(T);
-    char*             hin = static_cast<char*>(st->h_in.ensure(R * N * b));
-    for (std::size_t g = 0; g < R; ++g)
-        for (std::size_t k = 0; k < N; ++k) std::memcpy(hin + (g * N + k) * b, (*groups[g])[k].buffer->read_span(nIn).data(), b);
-    char* din = static_cast<char*>(st->d_in.ensure(R * N * b));
-    check(gr4hip_memcpy_h2d(din, hin, R * N * b, nullptr), "h2d");
-    return din;
-}
-} // namespace detail
 template <typename T, std::size_t N>
 struct Kernel<gr::electrical::PowerFactor<T, N>> {
     using B = gr::electrical::PowerFactor<T, N>;
     static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
-        try {
-            Offload*          st = offload_state<Offload>(blk);
-            const std::size_t bi = nIn * sizeof(T), bo = nOut * sizeof(T);
+        return seam(blk, [&] {
+            Offload* st = offload_state<Offload>(blk);
             if (nOut != nIn) throw std::runtime_error("PowerFactor: one output per input");
-            char* din  = detail::electrical_rows_to_device<T, 2>(st, {&blk.P, &blk.S}, N, nIn);
-            char* dout = static_cast<char*>(st->d_out.ensure(2 * N * bo));
-            std::vector<gr::PortOut<T>>* ports[2] = {&blk.power_factor, &blk.phase};
-            void*                        dptr[2];
-            for (std::size_t q = 0; q < 2; ++q) {
-                bool any = false;
-                for (auto& port : *ports[q]) any = any || port.connected();
-                dptr[q] = any ? dout + q * N * bo : nullptr;
-            }
-            check(gr4hip_powerfactor_process(dtype_of<T>(), N, din, din + N * bi, nIn, dptr[0], dptr[1], nOut, nIn, nullptr), "gr4hip_powerfactor_process");
-            char* hout = static_cast<char*>(st->h_out.ensure(2 * N * bo));
-            for (std::size_t q = 0; q < 2; ++q)
-                if (dptr[q]) check(gr4hip_memcpy_d2h(hout + q * N * bo, dout + q * N * bo, N * bo, nullptr), "d2h");
-            check(gr4hip_stream_synchronize(nullptr), "sync");
-            for (std::size_t q = 0; q < 2; ++q) {
-                if (!dptr[q]) continue;
-                for (std::size_t k = 0; k < N; ++k)
-                    if ((*ports[q])[k].connected()) std::memcpy((*ports[q])[k].buffer->write_span(nOut).data(), hout + (q * N + k) * bo, bo);
-            }
-            return work::Status::OK;
-        } catch (const std::exception& e) {
-            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
-            return work::Status::ERROR; // never a silent host fallback
-        }
+            char*                      din = detail::phase_rows<T, 2>(st, {&blk.P, &blk.S}, N, nIn);
+            detail::PhaseOutputs<T, 2> out(st, {&blk.power_factor, &blk.phase}, N, nOut);
+            check(gr4hip_powerfactor_process(dtype_of<T>(), N, din, din + N * nIn * sizeof(T), nIn, out.d[0], out.d[1], nOut, nIn, nullptr), "gr4hip_powerfactor_process");
+            out.deliver(st, nOut);
+        });
     }
 };
 template <typename T, std::size_t N>
 struct Kernel<gr::electrical::SystemUnbalance<T, N>> {
     using B = gr::electrical::SystemUnbalance<T, N>;
     static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
-        try {
+        return seam(blk, [&] {
             Offload*          st = offload_state<Offload>(blk);
             const std::size_t bi = nIn * sizeof(T), bo = nOut * sizeof(T);
             if (nOut != nIn) throw std::runtime_error("SystemUnbalance: one output per input");
-            char* din  = detail::electrical_rows_to_device<T, 3>(st, {&blk.voltage_rms_inputs, &blk.current_rms_inputs, &blk.active_power_inputs}, N, nIn);
-            char* dout = static_cast<char*>(st->d_out.ensure(3 * bo));
+            char*           din = detail::phase_rows<T, 3>(st, {&blk.voltage_rms_inputs, &blk.current_rms_inputs, &blk.active_power_inputs}, N, nIn);
+            const RowLayout out(3, bo);
+            char*           dout     = st->output(out);
             gr::PortOut<T>* ports[3] = {&blk.total_active_power_output, &blk.voltage_unbalance_output, &blk.current_unbalance_output};
             void*           dptr[3];
-            for (std::size_t q = 0; q < 3; ++q) dptr[q] = ports[q]->connected() ? dout + q * bo : nullptr;
+            for (std::size_t q = 0; q < 3; ++q) dptr[q] = ports[q]->connected() ? dout + out.offset(q) : nullptr;
             check(gr4hip_unbalance_process(dtype_of<T>(), N, din, din + N * bi, din + 2 * N * bi, nIn, dptr[0], dptr[1], dptr[2], nIn, nullptr), "gr4hip_unbalance_process");
-            char* hout = static_cast<char*>(st->h_out.ensure(3 * bo));
-            for (std::size_t q = 0; q < 3; ++q)
-                if (dptr[q]) check(gr4hip_memcpy_d2h(hout + q * bo, dout + q * bo, bo, nullptr), "d2h");
-            check(gr4hip_stream_synchronize(nullptr), "sync");
-            for (std::size_t q = 0; q < 3; ++q)
-                if (dptr[q]) std::memcpy(ports[q]->buffer->write_span(nOut).data(), hout + q * bo, bo);
-            return work::Status::OK;
-        } catch (const std::exception& e) {
-            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
-            return work::Status::ERROR; // never a silent host fallback
-        }
+            const char* hout = st->download(out, [&](std::size_t q) { return dptr[q] != nullptr; });
+            for (std::size_t q = 0; q < 3; ++q) to_port(*ports[q], nOut, hout + out.offset(q), bo);
+        });
     }
 };
 
@@ -1361,16 +1338,13 @@ struct Kernel<gr::electrical::SystemUnbalance<T, N>> {
 template <typename T, gr::trigger::InterpolationMethod Method>
 struct Kernel<gr::blocks::basic::SchmittTrigger<T, Method>> {
     using B = gr::blocks::basic::SchmittTrigger<T, Method>;
-    struct State final : Offload {
-        gr4hip_schmitt_t* h = nullptr;
-        ~State() override { if (h) gr4hip_schmitt_destroy(h); }
-    };
+    using State = SeamState<gr4hip_schmitt_t, gr4hip_schmitt_destroy>;
     static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
-        try {
+        return seam(blk, [&] {
             State*     st = offload_state<State>(blk);
             const auto p  = blk.params();
             if (!st->h) {
-                check(gr4hip_schmitt_create(&st->h, &p), "gr4hip_schmitt_create");
+                check(gr4hip_schmitt_create(st->h.out(), &p), "gr4hip_schmitt_create");
                 blk._detector_changed = false;
             } else if (blk._detector_changed) {
                 check(gr4hip_schmitt_set_params(st->h, &p), "gr4hip_schmitt_set_params");
@@ -1379,12 +1353,9 @@ struct Kernel<gr::blocks::basic::SchmittTrigger<T, Method>> {
             ++blk._device_calls;
             const std::size_t bi  = nIn * sizeof(T);
             const auto        is  = blk.in.buffer->read_span(nIn);
-            char*             hin = static_cast<char*>(st->h_in.ensure(bi));
-            std::memcpy(hin, is.data(), bi);
-            char* din = static_cast<char*>(st->d_in.ensure(bi));
-            check(gr4hip_memcpy_h2d(din, hin, bi, nullptr), "h2d");
+            char*             din = st->upload(is.data(), bi);
             constexpr std::size_t head = 16; // the counter, then the edges
-            char*                 dout = static_cast<char*>(st->d_out.ensure(head + nIn * sizeof(gr4hip_schmitt_edge)));
+            char*                 dout = st->output(head + nIn * sizeof(gr4hip_schmitt_edge));
             check(gr4hip_schmitt_process(st->h, din, nIn, reinterpret_cast<gr4hip_schmitt_edge*>(dout + head), nIn, reinterpret_cast<unsigned long long*>(dout), nullptr),
                   "gr4hip_schmitt_process");
             char* hout = static_cast<char*>(st->h_out.ensure(head + nIn * sizeof(gr4hip_schmitt_edge)));
@@ -1423,11 +1394,7 @@ struct Kernel<gr::blocks::basic::SchmittTrigger<T, Method>> {
                                                static_cast<std::size_t>(pos));
             }
             blk._now += static_cast<std::uint64_t>(nIn) * blk._period;
-            return work::Status::OK;
-        } catch (const std::exception& e) {
-            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
-            return work::Status::ERROR; // never a silent host fallback
-        }
+        });
     }
 };
 
@@ -1437,16 +1404,13 @@ struct Kernel<gr::blocks::basic::SchmittTrigger<T, Method>> {
 template <typename T>
 struct Kernel<gr::filter::SvdDenoiser<T>> {
     using B = gr::filter::SvdDenoiser<T>;
-    struct State final : Offload {
-        gr4hip_svddenoise_t* h = nullptr;
-        ~State() override { if (h) gr4hip_svddenoise_destroy(h); }
-    };
+    using State = SeamState<gr4hip_svddenoise_t, gr4hip_svddenoise_destroy>;
     static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
-        try {
+        return seam(blk, [&] {
             State*     st = offload_state<State>(blk);
             const auto p  = blk.params();
             if (!st->h) {
-                check(gr4hip_svddenoise_create(&st->h, &p), "gr4hip_svddenoise_create");
+                check(gr4hip_svddenoise_create(st->h.out(), &p), "gr4hip_svddenoise_create");
                 blk._parameters_changed = false;
             } else if (blk._parameters_changed) {
                 check(gr4hip_svddenoise_set_params(st->h, &p), "gr4hip_svddenoise_set_params");
@@ -1455,22 +1419,10 @@ struct Kernel<gr::filter::SvdDenoiser<T>> {
             if (nOut != nIn) throw std::runtime_error("SvdDenoiser: one output per input");
             ++blk._device_calls;
             const std::size_t bytes = nIn * sizeof(T);
-            const auto        is    = blk.in.buffer->read_span(nIn);
-            char*             hin   = static_cast<char*>(st->h_in.ensure(bytes));
-            std::memcpy(hin, is.data(), bytes);
-            char* din  = static_cast<char*>(st->d_in.ensure(bytes));
-            char* dout = static_cast<char*>(st->d_out.ensure(bytes));
-            check(gr4hip_memcpy_h2d(din, hin, bytes, nullptr), "h2d");
-            check(gr4hip_svddenoise_process(st->h, din, nIn, dout, nullptr), "gr4hip_svddenoise_process");
-            char* hout = static_cast<char*>(st->h_out.ensure(bytes));
-            check(gr4hip_memcpy_d2h(hout, dout, bytes, nullptr), "d2h");
-            check(gr4hip_stream_synchronize(nullptr), "sync");
-            if (blk.out.connected()) std::memcpy(blk.out.buffer->write_span(nOut).data(), hout, bytes);
-            return work::Status::OK;
-        } catch (const std::exception& e) {
-            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
-            return work::Status::ERROR; // never a silent host fallback
-        }
+            char*             din   = st->upload(blk.in.buffer->read_span(nIn).data(), bytes);
+            check(gr4hip_svddenoise_process(st->h, din, nIn, st->output(bytes), nullptr), "gr4hip_svddenoise_process");
+            to_port(blk.out, nOut, st->download(bytes), bytes);
+        });
     }
 };
 
@@ -1480,21 +1432,17 @@ struct Kernel<gr::filter::SvdDenoiser<T>> {
 // is setParameters (SavitzkyGolay.hpp:253-260), which clears the history, so the stage is made anew (gr4hip_fir_set_taps alone would keep it).
 template <typename T>
 struct SavgolStage final : Stage {
-    gr4hip_fir_t*   h32 = nullptr;
-    gr4hip_fir64_t* h64 = nullptr;
+    Handle<gr4hip_fir_t, gr4hip_fir_destroy> h32;
+    Handle<gr4hip_fir64_t, gr4hip_fir64_destroy> h64;
     explicit SavgolStage(const std::vector<T>& coeffs) {
         in_bytes = out_bytes = sizeof(T);
         const std::vector<T> b(coeffs.rbegin(), coeffs.rend());
         if constexpr (std::is_same_v<T, float>) {
-            check(gr4hip_fir_create(&h32, GR4HIP_F32, b.data(), b.size(), 1), "gr4hip_fir_create");
+            check(gr4hip_fir_create(h32.out(), GR4HIP_F32, b.data(), b.size(), 1), "gr4hip_fir_create");
             check(gr4hip_fir_set_algo(h32, GR4HIP_FIR_EXACT_F32), "gr4hip_fir_set_algo");
         } else {
-            check(gr4hip_fir64_create(&h64, b.data(), b.size(), 1), "gr4hip_fir64_create");
+            check(gr4hip_fir64_create(h64.out(), b.data(), b.size(), 1), "gr4hip_fir64_create");
         }
-    }
-    ~SavgolStage() override {
-        if (h32) gr4hip_fir_destroy(h32);
-        if (h64) gr4hip_fir64_destroy(h64);
     }
     std::string_view kind() const override { return std::is_same_v<T, float> ? "savgol_f32" : "savgol_f64"; }
     int enqueue(const void* in, std::size_t n, void* out, std::size_t* n_out, gr4hip_stream_t s) override {
@@ -1519,15 +1467,12 @@ struct Kernel<gr::filter::SavitzkyGolayFilter<T>> {
 template <typename T>
 struct Kernel<gr::filter::SavitzkyGolayDataSetFilter<T>> {
     using B = gr::filter::SavitzkyGolayDataSetFilter<T>;
-    struct State final : Offload {
-        gr4hip_savgol_zp_t* h = nullptr;
-        ~State() override { if (h) gr4hip_savgol_zp_destroy(h); }
-    };
+    using State = SeamState<gr4hip_savgol_zp_t, gr4hip_savgol_zp_destroy>;
     static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
-        try {
+        return seam(blk, [&] {
             State*     st = offload_state<State>(blk);
             const auto p  = blk.params();
-            if (!st->h) check(gr4hip_savgol_zp_create(&st->h, &p), "gr4hip_savgol_zp_create");
+            if (!st->h) check(gr4hip_savgol_zp_create(st->h.out(), &p), "gr4hip_savgol_zp_create");
             else if (blk._parameters_changed) check(gr4hip_savgol_zp_set_params(st->h, &p), "gr4hip_savgol_zp_set_params");
             blk._parameters_changed = false;
             if (nOut != nIn) throw std::runtime_error("SavitzkyGolayDataSetFilter: one DataSet out per DataSet in");
@@ -1538,24 +1483,13 @@ struct Kernel<gr::filter::SavitzkyGolayDataSetFilter<T>> {
                 const std::size_t n     = ds.signal_values.size();
                 const std::size_t bytes = n * sizeof(T);
                 if (n) {
-                    char* hin = static_cast<char*>(st->h_in.ensure(bytes));
-                    std::memcpy(hin, ds.signal_values.data(), bytes);
-                    char* din  = static_cast<char*>(st->d_in.ensure(bytes));
-                    char* dout = static_cast<char*>(st->d_out.ensure(bytes));
-                    check(gr4hip_memcpy_h2d(din, hin, bytes, nullptr), "h2d");
-                    check(gr4hip_savgol_zp_process(st->h, din, dout, n, 1, n, nullptr), "gr4hip_savgol_zp_process");
-                    char* hout = static_cast<char*>(st->h_out.ensure(bytes));
-                    check(gr4hip_memcpy_d2h(hout, dout, bytes, nullptr), "d2h");
-                    check(gr4hip_stream_synchronize(nullptr), "sync");
-                    std::memcpy(ds.signal_values.data(), hout, bytes);
+                    char* din = st->upload(ds.signal_values.data(), bytes);
+                    check(gr4hip_savgol_zp_process(st->h, din, st->output(bytes), n, 1, n, nullptr), "gr4hip_savgol_zp_process");
+                    std::memcpy(ds.signal_values.data(), st->download(bytes), bytes);
                 }
                 if (!os.empty()) os[f] = std::move(ds);
             }
-            return work::Status::OK;
-        } catch (const std::exception& e) {
-            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
-            return work::Status::ERROR; // never a silent host fallback
-        }
+        });
     }
 };
 
@@ -1565,16 +1499,13 @@ struct Kernel<gr::filter::SavitzkyGolayDataSetFilter<T>> {
 template <typename T>
 struct Kernel<gr::basic::SignalGenerator<T>> {
     using B = gr::basic::SignalGenerator<T>;
-    struct State final : Offload {
-        gr4hip_siggen_t* h = nullptr;
-        ~State() override { if (h) gr4hip_siggen_destroy(h); }
-    };
+    using State = SeamState<gr4hip_siggen_t, gr4hip_siggen_destroy>;
     static work::Status generate(B& blk, T* host, std::size_t n) {
-        try {
+        return seam(blk, [&] {
             State*     st = offload_state<State>(blk);
             const auto p  = blk.params();
             if (!st->h) {
-                check(gr4hip_siggen_create(&st->h, &p), "gr4hip_siggen_create");
+                check(gr4hip_siggen_create(st->h.out(), &p), "gr4hip_siggen_create");
             } else {
                 if (blk._device_configure) check(gr4hip_siggen_configure(st->h, &p), "gr4hip_siggen_configure");
                 if (blk._device_reset) check(gr4hip_siggen_reset(st->h), "gr4hip_siggen_reset");
@@ -1582,17 +1513,9 @@ struct Kernel<gr::basic::SignalGenerator<T>> {
             blk._device_configure = blk._device_reset = false;
             ++blk._device_calls;
             const std::size_t bytes = n * sizeof(T);
-            char*             dout  = static_cast<char*>(st->d_out.ensure(bytes));
-            check(gr4hip_siggen_process(st->h, dout, n, nullptr), "gr4hip_siggen_process");
-            char* hout = static_cast<char*>(st->h_out.ensure(bytes));
-            check(gr4hip_memcpy_d2h(hout, dout, bytes, nullptr), "d2h");
-            check(gr4hip_stream_synchronize(nullptr), "sync");
-            std::memcpy(host, hout, bytes);
-            return work::Status::OK;
-        } catch (const std::exception& e) {
-            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
-            return work::Status::ERROR; // never a silent host fallback
-        }
+            check(gr4hip_siggen_process(st->h, st->output(bytes), n, nullptr), "gr4hip_siggen_process");
+            std::memcpy(host, st->download(bytes), bytes);
+        });
     }
 };
 
@@ -1860,7 +1783,7 @@ struct Kernel<gr::blocks::math::MathOpMultiPortImpl<T, op>> {
         std::vector<std::unique_ptr<DevBuf>> d_ins;
     };
     static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
-        try {
+        return seam(blk, [&] {
             State* st = offload_state<State>(blk);
             while (st->d_ins.size() < blk.in.size()) st->d_ins.push_back(std::make_unique<DevBuf>());
             const std::size_t        bytes = nIn * sizeof(T);
@@ -1871,59 +1794,74 @@ struct Kernel<gr::blocks::math::MathOpMultiPortImpl<T, op>> {
                 check(gr4hip_memcpy_h2d(st->d_ins[i]->ensure(bytes), stage + i * bytes, bytes, nullptr), "h2d");
                 ptrs.push_back(st->d_ins[i]->p);
             }
-            check(gr4hip_math_nary(op_id<op, T>(), dtype_of<T>(), ptrs.data(), ptrs.size(), st->d_out.ensure(bytes), nIn, nullptr), "gr4hip_math_nary");
-            check(gr4hip_memcpy_d2h(st->h_out.ensure(bytes), st->d_out.p, bytes, nullptr), "d2h");
-            check(gr4hip_stream_synchronize(nullptr), "sync");
-            std::memcpy(blk.out.buffer->write_span(nOut).data(), st->h_out.p, nOut * sizeof(T));
-            return work::Status::OK;
-        } catch (const std::exception& e) {
-            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
-            return work::Status::ERROR;
-        }
+            check(gr4hip_math_nary(op_id<op, T>(), dtype_of<T>(), ptrs.data(), ptrs.size(), st->output(bytes), nIn, nullptr), "gr4hip_math_nary");
+            std::memcpy(blk.out.buffer->write_span(nOut).data(), st->download(bytes), nOut * sizeof(T));
+        });
     }
 };
+
+// The fan-in and chunk-shape blocks that follow keep no Stage: their handle's shape is part of the handle, so the state remembers the key it was made for and a
+// call with another key makes the handle anew (the old one is released first).
+template <typename... Ts>
+struct MadeFor {
+    std::tuple<Ts...> key{};
+};
+namespace detail {
+// the spectra of a fan-in (CrossSpectrum, Beamformer) as rows of one buffer in one copy; the row pointers that the launch takes
+template <typename Ports>
+std::vector<const float*> spectra_rows(Offload* st, Ports& in, std::size_t nIn) {
+    const RowLayout           rows(in.size(), nIn * sizeof(std::complex<float>));
+    char*                     din = st->upload(rows, [&](std::size_t s) { return static_cast<const void*>(in[s].buffer->read_span(nIn).data()); });
+    std::vector<const float*> ptrs(rows.rows);
+    for (std::size_t s = 0; s < rows.rows; ++s) ptrs[s] = reinterpret_cast<const float*>(din + rows.offset(s));
+    return ptrs;
+}
+// Beamformer's weights and AdaptiveWeights' steering vectors: value(beam, stream, bin) packed [beam][stream][bin] as {re, im} floats, to the device when the
+// handle is new and whenever the settings change (Block::_settings_generation); give(table) hands the device copy to the handle
+struct BeamTable : MadeFor<std::size_t, std::size_t, std::size_t> {
+    bool   loaded = false;
+    DevBuf d_table;
+};
+template <typename St, typename B, typename Value, typename Give>
+void beam_table(St* st, B& blk, Value&& value, Give&& give) {
+    if (st->loaded && st->settings_generation == blk._settings_generation) return;
+    const auto [S, NB, N] = st->key;
+    std::vector<float> t(2 * NB * S * N);
+    for (std::size_t b = 0, i = 0; b < NB; ++b)
+        for (std::size_t s = 0; s < S; ++s)
+            for (std::size_t c = 0; c < N; ++c, ++i) { const auto v = value(b, s, c); t[2 * i] = v.real(); t[2 * i + 1] = v.imag(); }
+    const std::size_t bytes = t.size() * sizeof(float);
+    check(gr4hip_memcpy_h2d(st->d_table.ensure(bytes), t.data(), bytes, nullptr), "h2d");
+    give(static_cast<const float*>(st->d_table.p));
+    check(gr4hip_stream_synchronize(nullptr), "sync"); // t leaves scope
+    st->loaded              = true;
+    st->settings_generation = blk._settings_generation;
+}
+} // namespace detail
 
 // CrossSpectrum<float>: n_inputs spectra -> one stream of cross-spectral matrices at the seam, like the N-input math blocks (no Stage: a fan-in is not part of a
 // linear device run).  The input spans go to HBM as rows of one buffer in one copy, one gr4hip_xcorr_process, the matrices back.  A work() call hands over whole
 // integrations, so the handle carries nothing between calls; other settings make a new handle.
 template <>
 struct Kernel<gr::blocks::fft::CrossSpectrum<float>> {
-    using B = gr::blocks::fft::CrossSpectrum<float>;
-    struct State final : Offload {
-        gr4hip_xcorr_t* h = nullptr;
-        std::size_t     S = 0, N = 0, A = 0;
-        bool            mean = false;
-        ~State() override { if (h) gr4hip_xcorr_destroy(h); }
-    };
+    using B     = gr::blocks::fft::CrossSpectrum<float>;
+    using State = SeamState<gr4hip_xcorr_t, gr4hip_xcorr_destroy, MadeFor<std::size_t, std::size_t, std::size_t, bool>>;
     static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
-        try {
+        return seam(blk, [&] {
             State*            st = offload_state<State>(blk);
             const std::size_t S = blk.in.size(), N = blk.vector_size, A = blk.n_integrate;
-            if (!st->h || st->S != S || st->N != N || st->A != A || st->mean != blk.mean) {
-                if (st->h) gr4hip_xcorr_destroy(st->h);
-                st->h = nullptr;
-                check(gr4hip_xcorr_create(&st->h, S, N, A, blk.mean ? GR4HIP_XCORR_MEAN : 0), "gr4hip_xcorr_create");
-                st->S = S; st->N = N; st->A = A; st->mean = blk.mean;
+            if (const std::tuple key{S, N, A, bool(blk.mean)}; !st->h || st->key != key) {
+                check(gr4hip_xcorr_create(st->h.out(), S, N, A, blk.mean ? GR4HIP_XCORR_MEAN : 0), "gr4hip_xcorr_create");
+                st->key = key;
             }
             if (nIn % (A * N) != 0 || nOut != nIn / (A * N) * blk.nBaselines() * N) throw std::runtime_error("CrossSpectrum: the work loop must hand over whole integrations");
-            const std::size_t bi = nIn * sizeof(std::complex<float>), bo = nOut * sizeof(std::complex<float>);
-            char*             hin = static_cast<char*>(st->h_in.ensure(S * bi));
-            for (std::size_t s = 0; s < S; ++s) std::memcpy(hin + s * bi, blk.in[s].buffer->read_span(nIn).data(), bi);
-            char* din = static_cast<char*>(st->d_in.ensure(S * bi));
-            check(gr4hip_memcpy_h2d(din, hin, S * bi, nullptr), "h2d");
-            std::vector<const float*> ptrs(S);
-            for (std::size_t s = 0; s < S; ++s) ptrs[s] = reinterpret_cast<const float*>(din + s * bi);
-            std::size_t produced = 0;
-            check(gr4hip_xcorr_process(st->h, ptrs.data(), nIn / N, static_cast<float*>(st->d_out.ensure(bo)), &produced, nullptr), "gr4hip_xcorr_process");
+            const std::size_t bo   = nOut * sizeof(std::complex<float>);
+            const auto        ptrs = detail::spectra_rows(st, blk.in, nIn);
+            std::size_t       produced = 0;
+            check(gr4hip_xcorr_process(st->h, ptrs.data(), nIn / N, reinterpret_cast<float*>(st->output(bo)), &produced, nullptr), "gr4hip_xcorr_process");
             if (produced * blk.nBaselines() * N != nOut) throw std::runtime_error("CrossSpectrum: the device wrote another number of matrices than the work loop expects");
-            check(gr4hip_memcpy_d2h(st->h_out.ensure(bo), st->d_out.p, bo, nullptr), "d2h");
-            check(gr4hip_stream_synchronize(nullptr), "sync");
-            if (blk.out.connected()) std::memcpy(blk.out.buffer->write_span(nOut).data(), st->h_out.p, bo);
-            return work::Status::OK;
-        } catch (const std::exception& e) {
-            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
-            return work::Status::ERROR; // never a silent host fallback
-        }
+            to_port(blk.out, nOut, st->download(bo), bo);
+        });
     }
 };
 
@@ -1932,57 +1870,28 @@ struct Kernel<gr::blocks::fft::CrossSpectrum<float>> {
 // weights go to the device when the handle is made and whenever the settings change (Block::_settings_generation).
 template <>
 struct Kernel<gr::blocks::fft::Beamformer<float>> {
-    using B = gr::blocks::fft::Beamformer<float>;
-    struct State final : Offload {
-        gr4hip_beamform_t* h = nullptr;
-        std::size_t        S = 0, NB = 0, N = 0;
-        bool               have_weights = false;
-        DevBuf             d_w;
-        ~State() override { if (h) gr4hip_beamform_destroy(h); }
-    };
+    using B     = gr::blocks::fft::Beamformer<float>;
+    using State = SeamState<gr4hip_beamform_t, gr4hip_beamform_destroy, detail::BeamTable>;
     static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
-        try {
+        return seam(blk, [&] {
             State*            st = offload_state<State>(blk);
             const std::size_t S = blk.in.size(), NB = blk.n_beams, N = blk.vector_size;
-            if (!st->h || st->S != S || st->NB != NB || st->N != N) {
-                if (st->h) gr4hip_beamform_destroy(st->h);
-                st->h = nullptr;
-                check(gr4hip_beamform_create(&st->h, S, NB, N), "gr4hip_beamform_create");
-                st->S = S; st->NB = NB; st->N = N;
-                st->have_weights = false;
+            if (const std::tuple key{S, NB, N}; !st->h || st->key != key) {
+                check(gr4hip_beamform_create(st->h.out(), S, NB, N), "gr4hip_beamform_create");
+                st->key    = key;
+                st->loaded = false;
             }
-            if (!st->have_weights || st->settings_generation != blk._settings_generation) {
-                std::vector<float> w(2 * NB * S * N);
-                for (std::size_t b = 0, i = 0; b < NB; ++b)
-                    for (std::size_t s = 0; s < S; ++s)
-                        for (std::size_t c = 0; c < N; ++c, ++i) { const auto v = blk.weight(b, s, c); w[2 * i] = v.real(); w[2 * i + 1] = v.imag(); }
-                const std::size_t bw = w.size() * sizeof(float);
-                check(gr4hip_memcpy_h2d(st->d_w.ensure(bw), w.data(), bw, nullptr), "h2d");
-                check(gr4hip_beamform_set_weights(st->h, static_cast<const float*>(st->d_w.p), nullptr), "gr4hip_beamform_set_weights");
-                check(gr4hip_stream_synchronize(nullptr), "sync"); // w leaves scope
-                st->have_weights        = true;
-                st->settings_generation = blk._settings_generation;
-            }
+            detail::beam_table(st, blk, [&](std::size_t b, std::size_t s, std::size_t c) { return blk.weight(b, s, c); },
+                               [&](const float* w) { check(gr4hip_beamform_set_weights(st->h, w, nullptr), "gr4hip_beamform_set_weights"); });
             if (nIn % N != 0 || nOut != nIn * NB) throw std::runtime_error("Beamformer: the work loop must hand over whole frames");
-            const std::size_t bi = nIn * sizeof(std::complex<float>), bo = nOut * sizeof(std::complex<float>);
-            char*             hin = static_cast<char*>(st->h_in.ensure(S * bi));
-            for (std::size_t s = 0; s < S; ++s) std::memcpy(hin + s * bi, blk.in[s].buffer->read_span(nIn).data(), bi);
-            char* din = static_cast<char*>(st->d_in.ensure(S * bi));
-            check(gr4hip_memcpy_h2d(din, hin, S * bi, nullptr), "h2d");
-            std::vector<const float*> ptrs(S);
-            for (std::size_t s = 0; s < S; ++s) ptrs[s] = reinterpret_cast<const float*>(din + s * bi);
-            float*              dout = static_cast<float*>(st->d_out.ensure(bo));
+            const std::size_t   bo   = nOut * sizeof(std::complex<float>);
+            const auto          ptrs = detail::spectra_rows(st, blk.in, nIn);
+            float*              dout = reinterpret_cast<float*>(st->output(bo));
             std::vector<float*> outs(NB);
             for (std::size_t b = 0; b < NB; ++b) outs[b] = dout + b * N * 2;
             check(gr4hip_beamform_process(st->h, ptrs.data(), nIn / N, outs.data(), NB * N, nullptr), "gr4hip_beamform_process");
-            check(gr4hip_memcpy_d2h(st->h_out.ensure(bo), st->d_out.p, bo, nullptr), "d2h");
-            check(gr4hip_stream_synchronize(nullptr), "sync");
-            if (blk.out.connected()) std::memcpy(blk.out.buffer->write_span(nOut).data(), st->h_out.p, bo);
-            return work::Status::OK;
-        } catch (const std::exception& e) {
-            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
-            return work::Status::ERROR; // never a silent host fallback
-        }
+            to_port(blk.out, nOut, st->download(bo), bo);
+        });
     }
 };
 
@@ -1991,158 +1900,96 @@ struct Kernel<gr::blocks::fft::Beamformer<float>> {
 // when it is made and whenever the settings change (Block::_settings_generation).
 template <>
 struct Kernel<gr::blocks::fft::AdaptiveWeights<float>> {
-    using B = gr::blocks::fft::AdaptiveWeights<float>;
-    struct State final : Offload {
-        gr4hip_mvdr_t* h = nullptr;
-        std::size_t    S = 0, NB = 0, N = 0;
-        bool           have_steering = false;
-        DevBuf         d_a;
-        ~State() override { if (h) gr4hip_mvdr_destroy(h); }
-    };
+    using B     = gr::blocks::fft::AdaptiveWeights<float>;
+    using State = SeamState<gr4hip_mvdr_t, gr4hip_mvdr_destroy, detail::BeamTable>;
     static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
-        try {
+        return seam(blk, [&] {
             State*            st = offload_state<State>(blk);
             const std::size_t S = blk.n_inputs, NB = blk.n_beams, N = blk.vector_size, P = blk.nBaselines();
-            if (!st->h || st->S != S || st->NB != NB || st->N != N) {
-                if (st->h) gr4hip_mvdr_destroy(st->h);
-                st->h = nullptr;
-                check(gr4hip_mvdr_create(&st->h, S, NB, N), "gr4hip_mvdr_create");
-                st->S = S; st->NB = NB; st->N = N;
-                st->have_steering = false;
+            if (const std::tuple key{S, NB, N}; !st->h || st->key != key) {
+                check(gr4hip_mvdr_create(st->h.out(), S, NB, N), "gr4hip_mvdr_create");
+                st->key    = key;
+                st->loaded = false;
             }
-            if (!st->have_steering || st->settings_generation != blk._settings_generation) {
-                std::vector<float> a(2 * NB * S * N);
-                for (std::size_t b = 0, i = 0; b < NB; ++b)
-                    for (std::size_t s = 0; s < S; ++s)
-                        for (std::size_t c = 0; c < N; ++c, ++i) { const auto v = blk.steer(b, s, c); a[2 * i] = v.real(); a[2 * i + 1] = v.imag(); }
-                const std::size_t ba = a.size() * sizeof(float);
-                check(gr4hip_memcpy_h2d(st->d_a.ensure(ba), a.data(), ba, nullptr), "h2d");
-                check(gr4hip_mvdr_set_steering(st->h, static_cast<const float*>(st->d_a.p), nullptr), "gr4hip_mvdr_set_steering");
+            detail::beam_table(st, blk, [&](std::size_t b, std::size_t s, std::size_t c) { return blk.steer(b, s, c); }, [&](const float* a) {
+                check(gr4hip_mvdr_set_steering(st->h, a, nullptr), "gr4hip_mvdr_set_steering");
                 check(gr4hip_mvdr_set_loading(st->h, blk.loading), "gr4hip_mvdr_set_loading");
-                check(gr4hip_stream_synchronize(nullptr), "sync"); // a leaves scope
-                st->have_steering       = true;
-                st->settings_generation = blk._settings_generation;
-            }
+            });
             if (nIn % (P * N) != 0 || nOut != nIn / (P * N) * NB * S * N) throw std::runtime_error("AdaptiveWeights: the work loop must hand over whole matrices");
             const std::size_t bi = nIn * sizeof(std::complex<float>), bo = nOut * sizeof(std::complex<float>);
-            std::memcpy(st->h_in.ensure(bi), blk.in.buffer->read_span(nIn).data(), bi);
-            check(gr4hip_memcpy_h2d(st->d_in.ensure(bi), st->h_in.p, bi, nullptr), "h2d");
-            check(gr4hip_mvdr_process(st->h, static_cast<const float*>(st->d_in.p), nIn / (P * N), static_cast<float*>(st->d_out.ensure(bo)), nullptr, nullptr), "gr4hip_mvdr_process");
-            check(gr4hip_memcpy_d2h(st->h_out.ensure(bo), st->d_out.p, bo, nullptr), "d2h");
-            check(gr4hip_stream_synchronize(nullptr), "sync");
-            if (blk.out.connected()) std::memcpy(blk.out.buffer->write_span(nOut).data(), st->h_out.p, bo);
-            return work::Status::OK;
-        } catch (const std::exception& e) {
-            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
-            return work::Status::ERROR; // never a silent host fallback
-        }
+            const float*      din = reinterpret_cast<const float*>(st->upload(blk.in.buffer->read_span(nIn).data(), bi));
+            check(gr4hip_mvdr_process(st->h, din, nIn / (P * N), reinterpret_cast<float*>(st->output(bo)), nullptr, nullptr), "gr4hip_mvdr_process");
+            to_port(blk.out, nOut, st->download(bo), bo);
+        });
     }
 };
 
-// FFT block: nOut frames of fftSize samples in, nOut DataSets out.  The four signals and their ranges are computed on the device
-// (gr4hip_fft_process); the host only assembles the descriptive part of the DataSet (axis, names, meta information).
+// FFT block: nOut frames of fftSize samples in, nOut DataSets out.  The four signals are computed on the device; the host only assembles the descriptive part of
+// the DataSet (axis, names, meta information).  One body for the two seams, which differ in where the per-signal ranges come from: FFT<float | complex<float>>
+// (gr4hip_fft_process) takes them from the device with a second copy, FFT<double> (gr4hip_fft64_process) on the host from the copied signals (fft.hpp:229-232).
+namespace detail {
+template <typename T, typename V, typename HandleT, auto Destroy>
+struct FftSeam {
+    using B = gr::blocks::fft::FFT<T, DataSet<V>>;
+    static constexpr bool kDeviceRanges = std::is_same_v<V, float>;
+    struct Ranges {
+        DevBuf d_rng, h_rng{true};
+    };
+    struct Extras : MadeFor<std::size_t, std::string, int>, std::conditional_t<kDeviceRanges, Ranges, NoExtras> {
+        DevBuf d_sig;
+    };
+    using State = SeamState<HandleT, Destroy, Extras>;
+    static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
+        return seam(blk, [&] {
+            State*    st    = offload_state<State>(blk);
+            const int flags = (blk.outputInDb ? GR4HIP_FFT_OUTPUT_IN_DB : 0) | (blk.outputInDeg ? GR4HIP_FFT_OUTPUT_IN_DEG : 0) | (blk.unwrapPhase ? GR4HIP_FFT_UNWRAP_PHASE : 0);
+            if (const std::tuple key{std::size_t(blk.fftSize), blk.window.value, flags}; !st->h || st->key != key) { // settings changed: new plan
+                if constexpr (kDeviceRanges) check(gr4hip_fft_create(st->h.out(), dtype_of<T>(), blk.fftSize, window_id(blk.window), flags), "gr4hip_fft_create");
+                else check(gr4hip_fft64_create(st->h.out(), blk.fftSize, window_id(blk.window), flags), "gr4hip_fft64_create");
+                st->key = key;
+            }
+            const std::size_t N = std::get<0>(st->key), M = blk.nBins(), frames = nOut, sig_bytes = 4 * frames * M * sizeof(V), rng_bytes = frames * 8 * sizeof(V);
+            if (nIn != frames * N) throw std::runtime_error("FFT: the work loop must hand over whole frames");
+            const char* din = st->upload(blk.in.buffer->read_span(nIn).data(), nIn * sizeof(T));
+            V*          sig = static_cast<V*>(st->d_sig.ensure(sig_bytes)); // [mag | phase | re | im], each frames x M
+            [[maybe_unused]] const V* hr = nullptr;
+            if constexpr (kDeviceRanges) {
+                V* rng = static_cast<V*>(st->d_rng.ensure(rng_bytes));
+                check(gr4hip_fft_process(st->h, din, frames, sig, sig + frames * M, sig + 2 * frames * M, sig + 3 * frames * M, rng, nullptr), "gr4hip_fft_process");
+                check(gr4hip_memcpy_d2h(st->h_out.ensure(sig_bytes), sig, sig_bytes, nullptr), "d2h");
+                check(gr4hip_memcpy_d2h(st->h_rng.ensure(rng_bytes), rng, rng_bytes, nullptr), "d2h");
+                hr = static_cast<const V*>(st->h_rng.p);
+            } else {
+                check(gr4hip_fft64_process(st->h, reinterpret_cast<const V*>(din), frames, sig, sig + frames * M, sig + 2 * frames * M, sig + 3 * frames * M, nullptr), "gr4hip_fft64_process");
+                check(gr4hip_memcpy_d2h(st->h_out.ensure(sig_bytes), sig, sig_bytes, nullptr), "d2h");
+            }
+            check(gr4hip_stream_synchronize(nullptr), "sync");
+            const V*   hs       = static_cast<const V*>(st->h_out.p);
+            auto       os       = blk.out.buffer->write_span(nOut);
+            const auto skeleton = blk.datasetSkeleton();
+            for (std::size_t f = 0; f < frames; ++f) {
+                DataSet<V> ds = skeleton;
+                for (std::size_t i = 0; i < 4; ++i) {
+                    const V* v = hs + (i * frames + f) * M;
+                    std::memcpy(ds.signalValues(i).data(), v, M * sizeof(V));
+                    if constexpr (kDeviceRanges) {
+                        ds.signal_ranges[i] = {hr[f * 8 + 2 * i], hr[f * 8 + 2 * i + 1]};
+                    } else {
+                        const auto [mn, mx] = std::minmax_element(v, v + M);
+                        ds.signal_ranges[i] = {*mn, *mx};
+                    }
+                }
+                os[f] = std::move(ds);
+            }
+        });
+    }
+};
+} // namespace detail
 template <typename T>
 requires(std::is_same_v<T, float> || std::is_same_v<T, std::complex<float>>)
-struct Kernel<gr::blocks::fft::FFT<T, DataSet<float>>> {
-    using B = gr::blocks::fft::FFT<T, DataSet<float>>;
-    struct State final : Offload {
-        gr4hip_fft_t* h = nullptr;
-        std::size_t   N = 0;
-        std::string   window;
-        int           flags = -1;
-        DevBuf        d_sig, d_rng, h_rng{true};
-        ~State() override { if (h) gr4hip_fft_destroy(h); }
-    };
-    static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
-        try {
-            State* st = offload_state<State>(blk);
-            const int flags = (blk.outputInDb ? GR4HIP_FFT_OUTPUT_IN_DB : 0) | (blk.outputInDeg ? GR4HIP_FFT_OUTPUT_IN_DEG : 0) | (blk.unwrapPhase ? GR4HIP_FFT_UNWRAP_PHASE : 0);
-            if (!st->h || st->N != blk.fftSize || st->window != blk.window.value || st->flags != flags) { // settings changed: new plan
-                if (st->h) gr4hip_fft_destroy(st->h);
-                st->h = nullptr;
-                check(gr4hip_fft_create(&st->h, dtype_of<T>(), blk.fftSize, window_id(blk.window), flags), "gr4hip_fft_create");
-                st->N = blk.fftSize; st->window = blk.window; st->flags = flags;
-            }
-            const std::size_t N = st->N, M = blk.nBins(), frames = nOut;
-            if (nIn != frames * N) throw std::runtime_error("FFT: the work loop must hand over whole frames");
-            std::memcpy(st->h_in.ensure(nIn * sizeof(T)), blk.in.buffer->read_span(nIn).data(), nIn * sizeof(T));
-            check(gr4hip_memcpy_h2d(st->d_in.ensure(nIn * sizeof(T)), st->h_in.p, nIn * sizeof(T), nullptr), "h2d");
-            float* sig = static_cast<float*>(st->d_sig.ensure(4 * frames * M * sizeof(float))); // [mag | phase | re | im], each frames x M
-            float* rng = static_cast<float*>(st->d_rng.ensure(frames * 8 * sizeof(float)));
-            check(gr4hip_fft_process(st->h, st->d_in.p, frames, sig, sig + frames * M, sig + 2 * frames * M, sig + 3 * frames * M, rng, nullptr), "gr4hip_fft_process");
-            check(gr4hip_memcpy_d2h(st->h_out.ensure(4 * frames * M * sizeof(float)), sig, 4 * frames * M * sizeof(float), nullptr), "d2h");
-            check(gr4hip_memcpy_d2h(st->h_rng.ensure(frames * 8 * sizeof(float)), rng, frames * 8 * sizeof(float), nullptr), "d2h");
-            check(gr4hip_stream_synchronize(nullptr), "sync");
-            const float* hs = static_cast<const float*>(st->h_out.p);
-            const float* hr = static_cast<const float*>(st->h_rng.p);
-            auto         os = blk.out.buffer->write_span(nOut);
-            const auto   skeleton = blk.datasetSkeleton();
-            for (std::size_t f = 0; f < frames; ++f) {
-                DataSet<float> ds = skeleton;
-                for (std::size_t i = 0; i < 4; ++i) {
-                    std::memcpy(ds.signalValues(i).data(), hs + (i * frames + f) * M, M * sizeof(float));
-                    ds.signal_ranges[i] = {hr[f * 8 + 2 * i], hr[f * 8 + 2 * i + 1]};
-                }
-                os[f] = std::move(ds);
-            }
-            return work::Status::OK;
-        } catch (const std::exception& e) {
-            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
-            return work::Status::ERROR;
-        }
-    }
-};
-
-// FFT<double>: real double frames -> DataSet<double> (gr4hip_fft64_process; the per-signal ranges of fft.hpp:229-232 are taken on the host from the copied signals)
+struct Kernel<gr::blocks::fft::FFT<T, DataSet<float>>> : detail::FftSeam<T, float, gr4hip_fft_t, gr4hip_fft_destroy> {};
 template <>
-struct Kernel<gr::blocks::fft::FFT<double, DataSet<double>>> {
-    using B = gr::blocks::fft::FFT<double, DataSet<double>>;
-    struct State final : Offload {
-        gr4hip_fft64_t* h = nullptr;
-        std::size_t     N = 0;
-        std::string     window;
-        int             flags = -1;
-        DevBuf          d_sig;
-        ~State() override { if (h) gr4hip_fft64_destroy(h); }
-    };
-    static work::Status work(B& blk, std::size_t nIn, std::size_t nOut) {
-        try {
-            State* st = offload_state<State>(blk);
-            const int flags = (blk.outputInDb ? GR4HIP_FFT_OUTPUT_IN_DB : 0) | (blk.outputInDeg ? GR4HIP_FFT_OUTPUT_IN_DEG : 0) | (blk.unwrapPhase ? GR4HIP_FFT_UNWRAP_PHASE : 0);
-            if (!st->h || st->N != blk.fftSize || st->window != blk.window.value || st->flags != flags) {
-                if (st->h) gr4hip_fft64_destroy(st->h);
-                st->h = nullptr;
-                check(gr4hip_fft64_create(&st->h, blk.fftSize, window_id(blk.window), flags), "gr4hip_fft64_create");
-                st->N = blk.fftSize; st->window = blk.window; st->flags = flags;
-            }
-            const std::size_t N = st->N, M = blk.nBins(), frames = nOut;
-            if (nIn != frames * N) throw std::runtime_error("FFT: the work loop must hand over whole frames");
-            std::memcpy(st->h_in.ensure(nIn * sizeof(double)), blk.in.buffer->read_span(nIn).data(), nIn * sizeof(double));
-            check(gr4hip_memcpy_h2d(st->d_in.ensure(nIn * sizeof(double)), st->h_in.p, nIn * sizeof(double), nullptr), "h2d");
-            double* sig = static_cast<double*>(st->d_sig.ensure(4 * frames * M * sizeof(double))); // [mag | phase | re | im], each frames x M
-            check(gr4hip_fft64_process(st->h, static_cast<const double*>(st->d_in.p), frames, sig, sig + frames * M, sig + 2 * frames * M, sig + 3 * frames * M, nullptr), "gr4hip_fft64_process");
-            check(gr4hip_memcpy_d2h(st->h_out.ensure(4 * frames * M * sizeof(double)), sig, 4 * frames * M * sizeof(double), nullptr), "d2h");
-            check(gr4hip_stream_synchronize(nullptr), "sync");
-            const double* hs = static_cast<const double*>(st->h_out.p);
-            auto          os = blk.out.buffer->write_span(nOut);
-            const auto    skeleton = blk.datasetSkeleton();
-            for (std::size_t f = 0; f < frames; ++f) {
-                DataSet<double> ds = skeleton;
-                for (std::size_t i = 0; i < 4; ++i) {
-                    const double* v = hs + (i * frames + f) * M;
-                    std::memcpy(ds.signalValues(i).data(), v, M * sizeof(double));
-                    const auto [mn, mx] = std::minmax_element(v, v + M);
-                    ds.signal_ranges[i] = {*mn, *mx};
-                }
-                os[f] = std::move(ds);
-            }
-            return work::Status::OK;
-        } catch (const std::exception& e) {
-            blk._log(std::string("device block '") + blk.name + "' failed: " + e.what());
-            return work::Status::ERROR;
-        }
-    }
-};
+struct Kernel<gr::blocks::fft::FFT<double, DataSet<double>>> : detail::FftSeam<double, double, gr4hip_fft64_t, gr4hip_fft64_destroy> {};
 
 // ---------------------------------------------------------------------------------------------- GPU-resident BufferLike ring
 // The device-side analogue of gr::CircularBuffer (core/include/gnuradio-4.0/CircularBuffer.hpp:191-236, BufferLike concept
@@ -2454,7 +2301,7 @@ struct OnDevice : Block<OnDevice<BlockT>, Resampling<1, 1, false>> {
         this->output_chunk_size = block.output_chunk_size;
     }
     work::Status processBulk(std::span<const TIn> dev_in, std::span<TOut> dev_out) {
-        try {
+        return seam(*this, [&] {
             check(gr4hip_set_device(static_cast<int>(device)), "gr4hip_set_device");
             if (!_stream) check(gr4hip_stream_create(&_stream), "gr4hip_stream_create");
             if (!_stage) _stage = Kernel<BlockT>::make_stage(block);
@@ -2463,11 +2310,7 @@ struct OnDevice : Block<OnDevice<BlockT>, Resampling<1, 1, false>> {
             if (produced != dev_out.size()) throw std::runtime_error("device stage produced an unexpected number of samples");
             check(gr4hip_stream_synchronize(_stream), "sync"); // cursors move only after completion (Block.hpp:1989-2026 ordering)
             ++_launches;
-            return work::Status::OK;
-        } catch (const std::exception& e) {
-            this->_log(std::string("device block '") + this->name + "' failed: " + e.what());
-            return work::Status::ERROR;
-        }
+        });
     }
 };
 

@@ -84,6 +84,66 @@ static int graph(const std::string& domain, std::size_t B, std::size_t N, std::s
     return 0;
 }
 
+// the matrices straight into the block (no CrossSpectrum in front: a settings tag reaches it with its sample index); a weight set depends on its own matrix and the
+// settings only, so with new steering vectors and loading by a tag in front of matrix 2 of 4 the first two sets are those of the old settings and the last two those
+// of the new ones, bit for bit -- on the device the steering table and the loading go to the live handle again
+static int direct(const std::string& domain, std::size_t S, std::size_t N, const std::vector<C32>& matrices, const std::vector<float>& ar, const std::vector<float>& ai, double loading,
+                  const std::vector<Tag>& tags, std::vector<C32>& y) {
+    Graph g;
+    auto& blk  = g.emplaceBlock<Mvdr>({{"n_inputs", std::int64_t(S)}, {"n_beams", std::int64_t(1)}, {"vector_size", std::int64_t(N)}, {"steering_real", ar}, {"steering_imag", ai}, {"loading", loading},
+                                       {"compute_domain", domain}});
+    auto& src  = g.emplaceBlock<testing::VectorSource<C32>>();
+    auto& sink = g.emplaceBlock<testing::VectorSink<C32>>();
+    blk._log   = [](std::string_view m) { std::cerr << "[log] " << m << "\n"; };
+    src.values = matrices;
+    src._tags  = tags;
+    if (!g.connect<"out", "in">(src, blk) || !g.connect<"out", "in">(blk, sink)) return 2;
+    scheduler::Simple sched;
+    sched.exchange(std::move(g));
+    if (const auto r = sched.runAndWait(); !r) {
+        std::fprintf(stderr, "graph: %s\n", r.error().message.c_str());
+        return 3;
+    }
+    EXPECT(blk._device_state != nullptr && blk._settings_by_tag == tags.size());
+    y = sink._samples;
+    return 0;
+}
+static int new_steering_case() {
+    const std::size_t S = 2, N = 16, A = 8, P = S * (S + 1) / 2;
+    std::vector<C32>  matrices;
+    { // four mean cross-spectral matrices from the host CrossSpectrum
+        Graph g;
+        auto& xc   = g.emplaceBlock<Cross>({{"n_inputs", std::int64_t(S)}, {"vector_size", std::int64_t(N)}, {"n_integrate", std::int64_t(A)}, {"mean", true}});
+        auto& sink = g.emplaceBlock<testing::VectorSink<C32>>();
+        const auto x = streams(S, N * A * 4, 57u);
+        for (std::size_t s = 0; s < S; ++s) {
+            auto& src  = g.emplaceBlock<testing::VectorSource<C32>>();
+            src.values = x[s];
+            if (!g.connect(src, "out"s, xc, "in#"s + std::to_string(s))) return 2;
+        }
+        if (!g.connect<"out", "in">(xc, sink)) return 2;
+        scheduler::Simple sched;
+        sched.exchange(std::move(g));
+        if (!sched.runAndWait()) return 3;
+        matrices = sink._samples;
+    }
+    EXPECT(matrices.size() == 4 * P * N);
+    const std::vector<float> ar1{1.f, 0.f}, ai1{0.f, 1.f}, ar2{0.6f, -0.8f}, ai2{0.8f, 0.6f};
+    const std::vector<Tag>   again{{2 * P * N, {{"steering_real", ar2}, {"steering_imag", ai2}, {"loading", 0.01}}}};
+    std::vector<C32>         changed, before, after;
+    if (int rc = direct("gpu:hip:0", S, N, matrices, ar1, ai1, 0.001, again, changed)) return rc;
+    if (int rc = direct("gpu:hip:0", S, N, matrices, ar1, ai1, 0.001, {}, before)) return rc;
+    if (int rc = direct("gpu:hip:0", S, N, matrices, ar2, ai2, 0.01, {}, after)) return rc;
+    const std::size_t half = 2 * S * N; // two weight sets [1 beam][S][N]
+    const bool sizes = changed.size() == 2 * half && before.size() == 2 * half && after.size() == 2 * half;
+    EXPECT(sizes);
+    if (!sizes) return 0;
+    EXPECT(std::memcmp(changed.data(), before.data(), half * sizeof(C32)) == 0 && std::memcmp(changed.data() + half, after.data() + half, half * sizeof(C32)) == 0);
+    EXPECT(std::memcmp(before.data() + half, after.data() + half, half * sizeof(C32)) != 0);
+    std::printf("steering and loading again on the live handle (by settings in front of matrix 2 of 4): %zu weights, old settings' then new settings'\n", changed.size());
+    return 0;
+}
+
 static int dumped_cases(const std::string& domain, const std::string& prefix) {
     struct Shape { std::size_t S, B, N, A; double loading; };
     for (const auto& [S, B, N, A, loading] : {Shape{2, 1, 8, 64, 0.0}, Shape{3, 5, 16, 19, 1e-3}, Shape{9, 2, 8, 40, 1e-2}}) {
@@ -184,6 +244,7 @@ int main(int argc, char** argv) {
     if (!ok) { std::fprintf(stderr, "%s\n", ok.error().message.c_str()); return 2; }
     try {
         if (int rc = mode == "device" ? dumped_cases("gpu:hip:0", argv[3]) : host_checks(loader, argv[3])) return rc;
+        if (int rc = mode == "device" ? new_steering_case() : 0) return rc;
     } catch (const std::exception& e) {
         std::fprintf(stderr, "graph: %s\n", e.what());
         return 3;

@@ -53,7 +53,7 @@ static bool throws(const property_map& settings) {
 }
 
 static int graph(const std::string& domain, std::size_t B, std::size_t N, const std::vector<float>& wr, const std::vector<float>& wi, const std::vector<std::vector<C32>>& x,
-                 std::vector<C32>& y, std::vector<Tag>* tags = nullptr) {
+                 std::vector<C32>& y, std::vector<Tag>* tags = nullptr, const std::vector<Tag>& settings_tags = {}) {
     Graph        g;
     property_map cfg{{"n_inputs", std::int64_t(x.size())}, {"n_beams", std::int64_t(B)}, {"vector_size", std::int64_t(N)}, {"weights_real", wr}, {"weights_imag", wi}};
     if (!domain.empty()) cfg["compute_domain"] = domain;
@@ -64,6 +64,7 @@ static int graph(const std::string& domain, std::size_t B, std::size_t N, const 
         auto& src  = g.emplaceBlock<testing::VectorSource<C32>>();
         src.values = x[s];
         if (tags) src._tags = {{0, {{"gr:sample_rate", 48000.f}}}};
+        if (s == 0 && !settings_tags.empty()) src._tags = settings_tags;
         if (!g.connect(src, "out"s, blk, "in#"s + std::to_string(s))) return 2;
     }
     if (!g.connect<"out", "in">(blk, sink)) return 2;
@@ -74,6 +75,7 @@ static int graph(const std::string& domain, std::size_t B, std::size_t N, const 
         return 3;
     }
     if (!domain.empty()) EXPECT(blk._device_state != nullptr); // the seam was taken
+    EXPECT(blk._settings_by_tag == settings_tags.size());
     y = sink._samples;
     if (tags) *tags = sink._tags;
     return 0;
@@ -98,6 +100,22 @@ static int dumped_cases(const std::string& domain, const std::string& prefix) {
             dump(tag + ".out", y);
         }
     }
+    return 0;
+}
+
+// S = 2, one beam, vector_size 16: two frames, then new weights by settings, then two frames.  The seam keeps its handle (the shape is the same) and sends the
+// weights to the device again.  Device against the host body: both are the ordered definition, bit for bit.
+static int new_weights_case() {
+    const std::size_t      N = 16;
+    const auto             x = streams(2, N * 4, 31u);
+    const std::vector<Tag> reweigh{{N * 2, {{"weights_real", std::vector<float>{-0.25f, 0.75f}}, {"weights_imag", std::vector<float>{0.5f, -1.f}}}}};
+    std::vector<C32>       dev, host, unchanged;
+    if (int rc = graph("gpu:hip:0", 1, N, {0.5f, 0.5f}, {0.f, 0.25f}, x, dev, nullptr, reweigh)) return rc;
+    if (int rc = graph("", 1, N, {0.5f, 0.5f}, {0.f, 0.25f}, x, host, nullptr, reweigh)) return rc;
+    if (int rc = graph("", 1, N, {0.5f, 0.5f}, {0.f, 0.25f}, x, unchanged)) return rc;
+    EXPECT(host.size() == 4 * N && dev.size() == host.size() && std::memcmp(dev.data(), host.data(), host.size() * sizeof(C32)) == 0);
+    EXPECT(unchanged.size() == host.size() && std::equal(host.begin(), host.begin() + 2 * N, unchanged.begin()) && !std::equal(host.begin() + 2 * N, host.end(), unchanged.begin() + 2 * N));
+    std::printf("weights again with the handle kept (new weights by settings): %zu values, device == host\n", dev.size());
     return 0;
 }
 
@@ -172,6 +190,7 @@ int main(int argc, char** argv) {
     if (!ok) { std::fprintf(stderr, "%s\n", ok.error().message.c_str()); return 2; }
     try {
         if (int rc = mode == "device" ? dumped_cases("gpu:hip:0", argv[3]) : host_checks(loader, argv[3])) return rc;
+        if (int rc = mode == "device" ? new_weights_case() : 0) return rc;
     } catch (const std::exception& e) {
         std::fprintf(stderr, "graph: %s\n", e.what());
         return 3;

@@ -222,6 +222,44 @@ static std::vector<std::int16_t> narrowing(const std::string& convert_domain) {
     return sink._samples;
 }
 
+// one block between a source and ONE sink on `out`; tags on the source (settings by tag)
+template <typename B, typename TI, typename TO>
+static std::vector<TO> one_sink(const std::string& domain, const char* in, const char* out, property_map settings, const std::vector<Tag>& tags, std::size_t* by_tag = nullptr) {
+    Graph g;
+    settings.insert_or_assign("compute_domain", domain);
+    auto& blk  = g.emplaceBlock<B>(settings);
+    blk._log   = [](std::string_view m) { std::cerr << "[log] " << m << "\n"; };
+    auto& src  = g.emplaceBlock<testing::VectorSource<TI>>();
+    src.values = load<TI>(0);
+    src._tags  = tags;
+    auto& sink = g.emplaceBlock<testing::VectorSink<TO>>();
+    if (!g.connect(src, "out", blk, in) || !g.connect(blk, out, sink, "in")) { ++g_errors; return {}; }
+    scheduler::Simple sched;
+    sched.exchange(std::move(g));
+    if (const auto r = sched.runAndWait(); !r) { std::cerr << "one_sink (" << domain << "): " << r.error().message << "\n"; ++g_errors; }
+    if (by_tag) *by_tag = blk._settings_by_tag;
+    return sink._samples;
+}
+// the seam's other two paths, device against the host block bit for bit (both kinds are exact arithmetic): ToRealImag with `imag` open -- a NULL pointer in the
+// call, not copied back --, and ScalingConvert's scale changed by a settings tag in mid-stream
+static void open_output_and_new_scale() {
+    using C = std::complex<float>;
+    const auto dr = one_sink<cv::ToRealImag<C>, C, float>("gpu:hip:0", "in", "real", {}, {}), hr = one_sink<cv::ToRealImag<C>, C, float>("host", "in", "real", {}, {});
+    const bool same_r = !dr.empty() && dr.size() == hr.size() && std::memcmp(dr.data(), hr.data(), dr.size() * sizeof(float)) == 0;
+    std::printf("ToRealImag with `imag` open: %zu samples, device == host: %s\n", dr.size(), same_r ? "bit for bit" : "FAILED");
+    EXPECT(same_r);
+    const std::size_t      n = load<std::uint8_t>(0).size(), at = n / 2;
+    const std::vector<Tag> rescale{{at, {{"scale", 0.25}}}};
+    std::size_t            by_tag[2] = {0, 0};
+    const auto ds = one_sink<cv::ScalingConvert<std::uint8_t, float>, std::uint8_t, float>("gpu:hip:0", "in", "out", {{"scale", g_scale}}, rescale, &by_tag[0]);
+    const auto hs = one_sink<cv::ScalingConvert<std::uint8_t, float>, std::uint8_t, float>("host", "in", "out", {{"scale", g_scale}}, rescale, &by_tag[1]);
+    const auto h0 = one_sink<cv::ScalingConvert<std::uint8_t, float>, std::uint8_t, float>("host", "in", "out", {{"scale", g_scale}}, {});
+    const bool same_s = ds.size() == n && hs.size() == n && std::memcmp(ds.data(), hs.data(), n * sizeof(float)) == 0;
+    const bool stepped = h0.size() == n && std::equal(hs.begin(), hs.begin() + static_cast<std::ptrdiff_t>(at), h0.begin()) && !std::equal(hs.begin() + static_cast<std::ptrdiff_t>(at), hs.end(), h0.begin() + static_cast<std::ptrdiff_t>(at));
+    std::printf("ScalingConvert scale by settings in mid-stream: %zu samples, device == host: %s\n", ds.size(), same_s && stepped ? "bit for bit" : "FAILED");
+    EXPECT(same_s && stepped && by_tag[0] == 1 && by_tag[1] == 1);
+}
+
 static void plugin_checks(const char* path) {
     using namespace std::string_literals;
     PluginLoader loader;
@@ -281,6 +319,7 @@ static int device_main(int argc, char** argv) {
     std::printf("narrowing graph: %zu samples, device Convert<float, int16> == host Convert: %s\n", nd.size(), same ? "bit for bit" : "FAILED");
     EXPECT(same);
     EXPECT(std::count(nd.begin(), nd.end(), std::int16_t(32767)) > 0 && std::count_if(nd.begin(), nd.end(), [](std::int16_t v) { return v > 0 && v < 32767; }) > 100);
+    open_output_and_new_scale();
     plugin_checks(argv[3]);
     if (g_errors) { std::printf("FAILED: %d graphs did not run\n", g_errors); return 3; }
     if (!g_failures) std::printf("all converter device checks passed\n");

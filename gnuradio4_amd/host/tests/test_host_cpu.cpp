@@ -1,13 +1,15 @@
 // Host-layer self test (no GPU): the kept gr::Block<>/Port<>/Graph::connect surface and scheduler::Simple, in the style of the
 // reference's own tests (blocks/math/test/qa_Math.cpp:16-41, blocks/filter/test/qa_filter.cpp:267-293, core/test/qa_Block.cpp:1315-1343).
 // Also BASELINE.json configs[0]: SignalSource -> 64-tap float FIR -> sink, 1 000 448 samples, CPU scheduler; the stream is dumped
-// for the python test to compare against the oracle.
+// for the python test to compare against the oracle.  Of the device seam (gr4/hip.hpp), the two parts that need no device: the owning library handle and the
+// row layout of the seams' transfers.
 #include <deque>
 #include <cstdio>
 #include <fstream>
 #include <iostream>
 
 #include <gr4/blocks.hpp>
+#include <gr4/hip.hpp>
 #include <gr4/merge.hpp>
 
 using namespace gr;
@@ -68,7 +70,95 @@ void uncertain_suite() {
     EXPECT(gr::value(U{3, 1}) == F(3) && gr::uncertainty(U{3, 1}) == F(1) && gr::uncertainty(F(42)) == F(0) && !gr::UncertainValueLike<F> && gr::UncertainValueLike<U>);
 }
 
+// filter::Decimator's body under a type of this program's own.  This program includes gr4/hip.hpp for the handle and row-layout checks below, and with that header
+// every hot-path block of the library has a device kernel; the reference's behaviour for a block that has none (warn once, run on the host: below) therefore needs
+// a block that has none whichever headers are included.  (No program checks that behaviour on a library block any more: it would have to leave gr4/hip.hpp out.)
+template <typename T>
+struct PlainDecimator : Block<PlainDecimator<T>, Resampling<1, 1, false>> {
+    PortIn<T>  in;
+    PortOut<T> out;
+    Size_t     decim = 1;
+    GR_MAKE_REFLECTABLE(PlainDecimator, in, out, decim);
+    void settingsChanged(const property_map&, const property_map&) { this->input_chunk_size = decim; }
+    [[nodiscard]] work::Status processBulk(std::span<const T> input, std::span<T> output) noexcept {
+        std::size_t o = 0;
+        for (std::size_t i = 0; i < input.size(); ++i)
+            if (i % decim == 0) output[o++] = input[i];
+        return work::Status::OK;
+    }
+};
+static_assert(!hip::HasKernel<PlainDecimator<float>> && hip::HasKernel<filter::Decimator<float>>);
+
+// a stand-in for a library handle type with its gr4hip_X_create / gr4hip_X_destroy: the destroy function counts
+struct FakeLibraryHandle { int id; };
+static int fake_released = 0;
+static int fake_create(FakeLibraryHandle** out, int id) { *out = new FakeLibraryHandle{id}; return 0; }
+static int fake_destroy(FakeLibraryHandle* h) { ++fake_released; delete h; return 0; }
+using FakeHandle = hip::Handle<FakeLibraryHandle, fake_destroy>;
+struct OwnerThatThrows { // a Stage's shape: create in the constructor, then a second call that fails
+    FakeHandle h;
+    explicit OwnerThatThrows(bool fail) {
+        fake_create(h.out(), 7);
+        if (fail) throw std::runtime_error("the call after create failed");
+    }
+};
+
 int main(int argc, char** argv) {
+    // ---- hip::Handle: whoever holds a library handle releases it exactly once -- at scope exit, on reset, when create fills it again, after a move, and when
+    //      the constructor of its owner throws after the handle was filled
+    {
+        { FakeHandle empty; EXPECT(!empty && empty.get() == nullptr); }
+        EXPECT(fake_released == 0); // nothing held, nothing released
+        {
+            FakeHandle h;
+            EXPECT(fake_create(h.out(), 1) == 0); // (the slot hands the handle over at the end of the statement that holds the create call)
+            EXPECT(h && h.get()->id == 1);
+            FakeLibraryHandle* raw = h; // what a C-ABI call receives
+            EXPECT(raw == h.get() && fake_released == 0);
+        }
+        EXPECT(fake_released == 1);
+        {
+            FakeHandle h;
+            fake_create(h.out(), 2);
+            h.reset();
+            EXPECT(fake_released == 2 && !h);
+            h.reset();
+            EXPECT(fake_released == 2);
+            fake_create(h.out(), 3);
+            fake_create(h.out(), 4); // a re-make: the old handle goes first
+            EXPECT(fake_released == 3 && h.get()->id == 4);
+        }
+        EXPECT(fake_released == 4);
+        {
+            FakeHandle a;
+            fake_create(a.out(), 5);
+            FakeHandle b = std::move(a);
+            EXPECT(!a && b && b.get()->id == 5 && fake_released == 4);
+            FakeHandle c;
+            fake_create(c.out(), 6);
+            c = std::move(b); // the handle that c held goes, b's lives on in c
+            EXPECT(fake_released == 5 && !b && c.get()->id == 5);
+        }
+        EXPECT(fake_released == 6);
+        { OwnerThatThrows kept(false); EXPECT(kept.h.get()->id == 7); }
+        EXPECT(fake_released == 7);
+        bool threw = false;
+        try { OwnerThatThrows lost(true); } catch (const std::runtime_error&) { threw = true; }
+        EXPECT(threw && fake_released == 8);
+    }
+    // ---- hip::RowLayout: where the rows of a seam's transfer lie.  The converter seam starts every row 256-byte aligned and copies up to the end of the last row;
+    //      every other seam packs its rows tightly
+    for (const std::size_t b : {std::size_t(1), std::size_t(255), std::size_t(256), std::size_t(257)}) {
+        for (const std::size_t R : {std::size_t(1), std::size_t(3)}) {
+            const std::size_t    up = (b + 255) / 256 * 256;
+            const hip::RowLayout aligned(R, b, 256), tight(R, b);
+            EXPECT(up % 256 == 0 && up >= b && up - b < 256);
+            for (std::size_t k = 0; k < R; ++k) EXPECT(aligned.offset(k) == k * up && tight.offset(k) == k * b);
+            EXPECT(aligned.copy_bytes() == (R - 1) * up + b && aligned.alloc_bytes() == R * up && aligned.bytes == b);
+            EXPECT(tight.copy_bytes() == R * b && tight.alloc_bytes() == R * b && tight.bytes == b);
+        }
+    }
+    EXPECT(hip::RowLayout(0, 64, 256).copy_bytes() == 0u);
     // ---- math blocks through Graph + Scheduler for the integer and float types
     math_suite<std::uint8_t>(); math_suite<std::int16_t>(); math_suite<std::int32_t>(); math_suite<std::uint64_t>(); math_suite<float>(); math_suite<double>();
     uncertain_suite<float>(); uncertain_suite<double>();
@@ -440,7 +530,7 @@ int main(int argc, char** argv) {
         Graph g;
         auto& src = g.emplaceBlock<testing::VectorSource<float>>({{"n_samples_max", std::int64_t(5000)}});
         src.values = {1.f};
-        auto& dec  = g.emplaceBlock<filter::Decimator<float>>({{"decim", std::int64_t(5)}, {"compute_domain", "gpu:hip:0"s}});
+        auto& dec  = g.emplaceBlock<PlainDecimator<float>>({{"decim", std::int64_t(5)}, {"compute_domain", "gpu:hip:0"s}});
         int   warnings = 0;
         dec._log = [&](std::string_view) { ++warnings; };
         auto& sink = g.emplaceBlock<testing::NullSink<float>>();

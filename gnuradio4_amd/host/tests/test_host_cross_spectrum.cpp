@@ -3,7 +3,8 @@
 //                                                                   tests/test_cross_spectrum_host.py (which compares them bit for bit with the oracle's ordered
 //                                                                   definition), the settings errors, the chunk sizes, gr:sample_rate, the plugin
 //   test_host_cross_spectrum device <libgr4hip_blocks.so> <prefix>   the same graph with the block on gpu:hip:0 (the seam onto gr4hip_xcorr_process); files for
-//                                                                   tests/test_gpu_cross_spectrum.py
+//                                                                   tests/test_gpu_cross_spectrum.py; and the seam's handle re-make: n_integrate changed by a
+//                                                                   settings tag between two work() calls, device against the host body bit for bit
 // Files: <prefix>.<name> = raw float32 {re, im} pairs; the input is [n_inputs][frames][vector_size].  Exit code 0: everything held; 1: a check failed; 3: a graph failed.
 #include <cstdio>
 #include <fstream>
@@ -45,7 +46,8 @@ static bool throws(const property_map& settings) {
     return false;
 }
 
-static int graph(const std::string& domain, std::size_t N, std::size_t A, bool mean, const std::vector<std::vector<C32>>& x, std::vector<C32>& y, std::vector<Tag>* tags = nullptr) {
+static int graph(const std::string& domain, std::size_t N, std::size_t A, bool mean, const std::vector<std::vector<C32>>& x, std::vector<C32>& y, std::vector<Tag>* tags = nullptr,
+                 const std::vector<Tag>& settings_tags = {}) {
     Graph        g;
     property_map cfg{{"n_inputs", std::int64_t(x.size())}, {"vector_size", std::int64_t(N)}, {"n_integrate", std::int64_t(A)}, {"mean", mean}};
     if (!domain.empty()) cfg["compute_domain"] = domain;
@@ -56,6 +58,7 @@ static int graph(const std::string& domain, std::size_t N, std::size_t A, bool m
         auto& src  = g.emplaceBlock<testing::VectorSource<C32>>();
         src.values = x[s];
         if (tags) src._tags = {{0, {{"gr:sample_rate", 48000.f}}}};
+        if (s == 0 && !settings_tags.empty()) src._tags = settings_tags;
         if (!g.connect(src, "out"s, blk, "in#"s + std::to_string(s))) return 2;
     }
     if (!g.connect<"out", "in">(blk, sink)) return 2;
@@ -66,6 +69,7 @@ static int graph(const std::string& domain, std::size_t N, std::size_t A, bool m
         return 3;
     }
     if (!domain.empty()) EXPECT(blk._device_state != nullptr); // the seam was taken
+    EXPECT(blk._settings_by_tag == settings_tags.size());
     y = sink._samples;
     if (tags) *tags = sink._tags;
     return 0;
@@ -86,6 +90,21 @@ static int dumped_cases(const std::string& domain, const std::string& prefix) {
             dump(tag + ".out", y);
         }
     }
+    return 0;
+}
+
+// S = 2, vector_size 16: one integration of two frames (one work() call: the chunk ends where the tag starts), then n_integrate 4 by settings, then one integration of
+// four frames.  The seam's handle was made for n_integrate 2 and has to be made anew.  Device against the host body: both are the ordered definition, bit for bit.
+static int remake_case() {
+    const std::size_t      N = 16;
+    const auto             x = streams(2, N * (2 + 4), 5u);
+    const std::vector<Tag> to_four{{N * 2, {{"n_integrate", std::int64_t(4)}}}};
+    std::vector<C32>       dev, host;
+    if (int rc = graph("gpu:hip:0", N, 2, false, x, dev, nullptr, to_four)) return rc;
+    if (int rc = graph("", N, 2, false, x, host, nullptr, to_four)) return rc;
+    EXPECT(host.size() == 2 * 3 * N && dev.size() == host.size() && std::memcmp(dev.data(), host.data(), host.size() * sizeof(C32)) == 0);
+    EXPECT(host[0] != host[3 * N]); // two frames summed, then four: not the same matrix twice
+    std::printf("handle re-make (n_integrate 2 -> 4 by settings): %zu values, device == host\n", dev.size());
     return 0;
 }
 
@@ -137,6 +156,7 @@ int main(int argc, char** argv) {
     if (!ok) { std::fprintf(stderr, "%s\n", ok.error().message.c_str()); return 2; }
     try {
         if (int rc = mode == "device" ? dumped_cases("gpu:hip:0", argv[3]) : host_checks(loader, argv[3])) return rc;
+        if (int rc = mode == "device" ? remake_case() : 0) return rc;
     } catch (const std::exception& e) {
         std::fprintf(stderr, "graph: %s\n", e.what());
         return 3;

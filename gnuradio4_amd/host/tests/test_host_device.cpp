@@ -44,6 +44,31 @@ std::vector<TOut> run_one(property_map settings, const std::vector<TIn>& input, 
     if (device && !blk._device_state) ++errors; // the seam must have been taken (the state goes with the block)
     return sink._samples;
 }
+// the same three blocks driven by hand: the first n_first samples, then `change` through applySettings, then the rest -- new settings between two work() calls
+template <typename BlockT, typename TIn, typename TOut>
+std::vector<TOut> run_in_two_parts(property_map settings, const property_map& change, const std::vector<TIn>& input, std::size_t n_first, bool device, int& errors) {
+    Graph g;
+    auto& src  = g.emplaceBlock<testing::VectorSource<TIn>>();
+    src.values = input;
+    if (device) settings["compute_domain"] = "gpu:hip:0"s;
+    auto& blk  = g.emplaceBlock<BlockT>(settings);
+    blk._log   = [](std::string_view m) { std::cerr << "[log] " << m << "\n"; };
+    auto& sink = g.emplaceBlock<testing::VectorSink<TOut>>();
+    if (!g.connect<"out", "in">(src, blk) || !g.connect<"out", "in">(blk, sink)) { ++errors; return {}; }
+    constexpr std::size_t all = std::numeric_limits<std::size_t>::max();
+    const auto            part = [&](std::size_t n) {
+        if (src.work(n).status != work::Status::OK) ++errors;
+        for (work::Status st; (st = blk.work(all).status) != work::Status::INSUFFICIENT_INPUT_ITEMS;) {
+            if (st != work::Status::OK) { ++errors; break; }
+            sink.work(all);
+        }
+    };
+    part(n_first);
+    blk.applySettings(change);
+    part(input.size() - n_first);
+    if (device && !blk._device_state) ++errors;
+    return sink._samples;
+}
 template <typename T>
 double max_rel(const std::vector<T>& got, const std::vector<T>& want) { // max |got - want| / max(|want|, rms(want))
     if (got.size() != want.size() || want.empty()) return 1e30;
@@ -397,6 +422,22 @@ int main(int argc, char** argv) {
                     worst = std::max(worst, max_rel(std::vector<double>(a.begin(), a.end()), std::vector<double>(b.begin(), b.end())));
                 }
             report("FFT<double> 1024 Hann -> DataSet<double>", worst, 1e-11);
+            // the double seam's handle re-make, as for FFT<complex<float>> below: two frames of 16, fftSize 32 through settings, two frames of 32; the same bound
+            const std::vector<double> x96(xd.begin(), xd.begin() + 2 * 16 + 2 * 32);
+            const property_map        cfg16{{"fftSize", std::int64_t(16)}, {"window", "Hann"s}}, to32{{"fftSize", std::int64_t(32)}};
+            const auto rd = run_in_two_parts<FF, double, DataSet<double>>(cfg16, to32, x96, 32, true, errors), rh = run_in_two_parts<FF, double, DataSet<double>>(cfg16, to32, x96, 32, false, errors);
+            double again = rd.size() == 4 && rh.size() == 4 && rh[1].extents == std::vector<std::int32_t>{8} && rh[2].extents == std::vector<std::int32_t>{16} ? 0.0 : 1e30;
+            for (std::size_t f = 0; f < 4 && again < 1e29; ++f) {
+                if (rd[f].extents != rh[f].extents || rd[f].axis_values != rh[f].axis_values) again = 1e30;
+                for (std::size_t i : {std::size_t(0), std::size_t(2), std::size_t(3)}) {
+                    if (again > 1e29) break;
+                    const auto a = rd[f].signalValues(i), b = rh[f].signalValues(i);
+                    again = std::max(again, max_rel(std::vector<double>(a.begin(), a.end()), std::vector<double>(b.begin(), b.end())));
+                    const auto [mn, mx] = std::minmax_element(a.begin(), a.end()); // the double seam's ranges are taken on the host from the copied signals
+                    if (rd[f].signal_ranges[i].min != *mn || rd[f].signal_ranges[i].max != *mx) again = 1e30;
+                }
+            }
+            report("FFT<double> 16 -> 32 by settings", again, 1e-11);
         }
         for (const char* kind : {"FIR", "IIR"}) {
             const property_map cfg{{"filter_type", std::string(kind)}, {"filter_response", "LOWPASS"s}, {"filter_order", std::int64_t(4)}, {"f_low", 100.0}, {"sample_rate", 1000.0},
@@ -513,6 +554,14 @@ int main(int argc, char** argv) {
                 const property_map cfg{{"fftSize", N}, {"window", N == 256 ? "Hann"s : "BlackmanHarris"s}, {"sample_rate", 1000.0}, {"signal_name", "ch0"s}};
                 compare(N == 256 ? "FFT<complex<float>> 256 Hann" : "FFT<complex<float>> 1000 B-Harris", run_one<B, std::complex<float>, DataSet<float>>(cfg, xc, true, errors),
                         run_one<B, std::complex<float>, DataSet<float>>(cfg, xc, false, errors), xc.size() / static_cast<std::size_t>(N));
+            }
+            { // the seam's handle re-make: two frames of 16, then fftSize 32 through settings, two frames of 32 -- a new plan between two work() calls
+                using B = blocks::fft::FFT<std::complex<float>>;
+                const property_map                     cfg16{{"fftSize", std::int64_t(16)}, {"window", "Hann"s}, {"sample_rate", 1000.0}}, to32{{"fftSize", std::int64_t(32)}};
+                const std::vector<std::complex<float>> x(xc.begin(), xc.begin() + 2 * 16 + 2 * 32);
+                const auto d = run_in_two_parts<B, std::complex<float>, DataSet<float>>(cfg16, to32, x, 32, true, errors), h = run_in_two_parts<B, std::complex<float>, DataSet<float>>(cfg16, to32, x, 32, false, errors);
+                if (!(h.size() == 4 && h[1].extents == std::vector<std::int32_t>{16} && h[2].extents == std::vector<std::int32_t>{32})) ++errors;
+                compare("FFT<complex<float>> 16 -> 32 by settings", d, h, 4);
             }
             using BR = blocks::fft::FFT<float>;
             const property_map cfg{{"fftSize", std::int64_t(512)}, {"window", "Hamming"s}, {"outputInDb", true}};

@@ -5,6 +5,7 @@
 // With dir, for T in {f32, f64} and X_<T>.bin holding three rows of one length for X in P, S, U, I: four graphs on compute_domain,
 //   pf3   ThreePhasePowerFactorCalculator<T>, every port connected         pf1   SinglePhasePowerFactorCalculator<T> on row 0, `phase` left unconnected
 //   ub3   ThreePhaseSystemUnbalanceCalculator<T>, every port connected     ub2   TwoPhaseSystemUnbalanceCalculator<T> on rows 0 and 1, the total power unconnected
+// and for float ub3t: ThreePhaseSystemUnbalanceCalculator<float> on the first 256 samples with the total power alone connected (both unbalance outputs unread),
 // whose sink contents go to dir/<graph>_<T>_<port>.bin (rows one after the other) and are compared with dir/want_<graph>_<T>_<port>.bin where that exists: the
 // phase within the given number of units in the last place (2 by default: CONVERTERS.md's host bound for the C library), everything else bit for bit with NaN
 // equal to NaN.  With dir/u.f32 and dir/i.f32 (three rows each) on a device domain: PowerMetrics<float, 3> (decimate 7) -> ThreePhasePowerFactorCalculator<float>
@@ -133,8 +134,8 @@ static int power_factor_graph(PluginLoader& loader, const std::string& domain, c
 }
 
 template <typename T>
-static int unbalance_graph(PluginLoader& loader, const std::string& domain, const std::string& dir, std::size_t phases, bool with_total) {
-    const std::string tag  = "ub" + std::to_string(phases) + "_" + tname<T>();
+static int unbalance_graph(PluginLoader& loader, const std::string& domain, const std::string& dir, std::size_t phases, bool with_total, bool total_alone = false) {
+    const std::string tag  = "ub" + std::to_string(phases) + (total_alone ? "t_" : "_") + tname<T>();
     const std::string type = (phases == 2 ? "gr::electrical::TwoPhaseSystemUnbalanceCalculator<"s : "gr::electrical::ThreePhaseSystemUnbalanceCalculator<"s) + portable<T>() + ">";
     const auto        U = read_bin<T>(dir + "/U_" + tname<T>() + ".bin"), I = read_bin<T>(dir + "/I_" + tname<T>() + ".bin"), P = read_bin<T>(dir + "/P_" + tname<T>() + ".bin");
     Graph             g;
@@ -145,18 +146,21 @@ static int unbalance_graph(PluginLoader& loader, const std::string& domain, cons
         su.values = row(U, k);
         si.values = row(I, k);
         sp.values = row(P, k);
+        if (total_alone)
+            for (auto* s : {&su, &si, &sp}) s->values.resize(256);
         EXPECT(g.connect(su, "out"s, blk, "voltage_rms_inputs" + sub).has_value() && g.connect(si, "out"s, blk, "current_rms_inputs" + sub).has_value() &&
                g.connect(sp, "out"s, blk, "active_power_inputs" + sub).has_value());
     }
-    auto &vu = g.emplaceBlock<testing::VectorSink<T>>(), &vi = g.emplaceBlock<testing::VectorSink<T>>();
+    testing::VectorSink<T>* vu = total_alone ? nullptr : &g.emplaceBlock<testing::VectorSink<T>>();
+    testing::VectorSink<T>* vi = total_alone ? nullptr : &g.emplaceBlock<testing::VectorSink<T>>();
     testing::VectorSink<T>* vt = with_total ? &g.emplaceBlock<testing::VectorSink<T>>() : nullptr;
-    EXPECT(g.connect(blk, "voltage_unbalance_output"s, vu, "in"s).has_value() && g.connect(blk, "current_unbalance_output"s, vi, "in"s).has_value());
+    if (vu) EXPECT(g.connect(blk, "voltage_unbalance_output"s, *vu, "in"s).has_value() && g.connect(blk, "current_unbalance_output"s, *vi, "in"s).has_value());
     if (vt) EXPECT(g.connect(blk, "total_active_power_output"s, *vt, "in"s).has_value());
     SchedulerPtr sched;
     if (const int rc = run(loader, std::move(g), tag, sched)) return rc;
     if (vt) deliver(dir, tag + "_P_total", vt->_samples, -1.0);
-    deliver(dir, tag + "_U_unbalance", vu._samples, -1.0);
-    deliver(dir, tag + "_I_unbalance", vi._samples, -1.0);
+    if (vu) deliver(dir, tag + "_U_unbalance", vu->_samples, -1.0);
+    if (vi) deliver(dir, tag + "_I_unbalance", vi->_samples, -1.0);
     return 0;
 }
 
@@ -286,7 +290,8 @@ int main(int argc, char** argv) {
         if ((rc = power_factor_graph<float>(loader, domain, dir, 3, true, b32)) || (rc = power_factor_graph<float>(loader, domain, dir, 1, false, b32)) ||
             (rc = power_factor_graph<double>(loader, domain, dir, 3, true, b64)) || (rc = power_factor_graph<double>(loader, domain, dir, 1, false, b64)) ||
             (rc = unbalance_graph<float>(loader, domain, dir, 3, true)) || (rc = unbalance_graph<float>(loader, domain, dir, 2, false)) ||
-            (rc = unbalance_graph<double>(loader, domain, dir, 3, true)) || (rc = unbalance_graph<double>(loader, domain, dir, 2, false)))
+            (rc = unbalance_graph<double>(loader, domain, dir, 3, true)) || (rc = unbalance_graph<double>(loader, domain, dir, 2, false)) ||
+            (rc = unbalance_graph<float>(loader, domain, dir, 3, true, true)))
             return rc;
         if (domain != "host" && exists(dir + "/u.f32")) {
             if ((rc = chain_graph(loader, domain, dir, false)) || (rc = chain_graph(loader, domain, dir, true))) return rc;

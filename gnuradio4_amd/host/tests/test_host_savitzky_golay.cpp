@@ -8,6 +8,9 @@
 //   stream_set   as stream_f32 but {5, 2, 0} at first and a tag at sample 2000 that sets window_size 11: the history starts again there
 //   dataset_f32  source -> FFT<float> {512, Hann} (host) -> SavitzkyGolayDataSetFilter<float>  {11, 4, 0, Reflect} -> sink
 //   dataset_f64  source -> FFT<double> {256, Hann} (host) -> SavitzkyGolayDataSetFilter<double> {8, 2, 1, Replicate} -> sink
+//   dataset_gap  source of three DataSet<float> with 32, 0 and 32 values -> SavitzkyGolayDataSetFilter<float> {11, 4, 0, Reflect} -> sink: the empty one is
+//                passed through between two that are filtered
+//   dataset_retune  three DataSet<float> of 32 values, {11, 4, 0, Reflect}, window_size 7 by a settings tag on the second: new coefficients on the live handle
 // The outputs go to dir/<graph>.<domain tag>.bin, the DataSet graphs' unfiltered signal_values to dir/<graph>.in.bin (the Python side compares them with the oracle,
 // and the device's with the host's).  Exit code 3: a graph failed (a device domain without a device fails loudly).
 #include <cstdio>
@@ -108,6 +111,92 @@ static int dataset_graph(const std::string& domain, const std::string& dir, cons
     return 0;
 }
 
+// hands out the DataSets it was given (VectorSource's `values` is a setting, and settings are compared: a DataSet is not)
+struct DataSetSource : Block<DataSetSource> {
+    PortOut<DataSet<float>> out;
+    GR_MAKE_REFLECTABLE(DataSetSource, out);
+    std::vector<DataSet<float>> values;
+    std::vector<Tag>            _tags; // as VectorSource's
+    std::size_t                 _produced = 0;
+    work::Result customWork(std::size_t requested) {
+        if (_produced >= values.size()) return {requested, 0, work::Status::DONE};
+        if (!out.connected()) return {requested, 0, work::Status::ERROR};
+        const std::size_t n = std::min({values.size() - _produced, out.buffer->free_space(), requested});
+        if (n == 0) return {requested, 0, work::Status::INSUFFICIENT_OUTPUT_ITEMS};
+        std::copy_n(values.begin() + static_cast<std::ptrdiff_t>(_produced), n, out.buffer->write_span(n).begin());
+        for (const Tag& t : _tags)
+            if (t.index >= _produced && t.index < _produced + n) out.buffer->publishTag(t.map, t.index - _produced);
+        out.buffer->publish(n);
+        _produced += n;
+        return {requested, n, work::Status::OK};
+    }
+};
+
+static int gap_graph(const std::string& domain, const std::string& dir) {
+    using B = filter::SavitzkyGolayDataSetFilter<float>;
+    const bool         dev = domain != "host";
+    const auto         x   = load<float>(dir + "/x.f32");
+    std::vector<float> filtered, unfiltered(x.begin(), x.begin() + 64);
+    Graph g;
+    auto& src = g.emplaceBlock<DataSetSource>();
+    src.values.resize(3);
+    src.values[0].signal_values.assign(x.begin(), x.begin() + 32);
+    src.values[2].signal_values.assign(x.begin() + 32, x.begin() + 64);
+    for (auto& ds : src.values) ds.signal_names = {"gap"};
+    auto& blk  = g.emplaceBlock<B>({{"window_size", std::int64_t(11)}, {"poly_order", std::int64_t(4)}, {"compute_domain", domain}});
+    auto& sink = g.emplaceBlock<testing::VectorSink<DataSet<float>>>();
+    blk._log   = [](std::string_view m) { std::cerr << "[log] " << m << "\n"; };
+    if (!g.connect<"out", "in">(src, blk) || !g.connect<"out", "in">(blk, sink)) return 2;
+    scheduler::Simple sched;
+    sched.exchange(std::move(g));
+    if (const auto r = sched.runAndWait(); !r) {
+        std::fprintf(stderr, "dataset_gap graph: %s\n", r.error().message.c_str());
+        return 3;
+    }
+    if (dev) EXPECT(blk._device_state != nullptr);
+    EXPECT(sink._samples.size() == 3);
+    if (sink._samples.size() != 3) return 0;
+    EXPECT(sink._samples[0].signal_values.size() == 32 && sink._samples[1].signal_values.empty() && sink._samples[2].signal_values.size() == 32);
+    for (const auto& ds : sink._samples) {
+        EXPECT(ds.signal_names == std::vector<std::string>{"gap"}); // everything else is passed through
+        filtered.insert(filtered.end(), ds.signal_values.begin(), ds.signal_values.end());
+    }
+    EXPECT(filtered != unfiltered);
+    dump(dir + "/dataset_gap.in.bin", unfiltered);
+    dump(dir + "/dataset_gap" + (dev ? ".device.bin" : ".host.bin"), filtered);
+    std::printf("dataset_gap: %zu values in 3 DataSets, the middle one empty\n", filtered.size());
+    return 0;
+}
+
+static int retune_graph(const std::string& domain, const std::string& dir) {
+    using B = filter::SavitzkyGolayDataSetFilter<float>;
+    const bool         dev = domain != "host";
+    const auto         x   = load<float>(dir + "/x.f32");
+    std::vector<float> filtered, unfiltered(x.begin() + 64, x.begin() + 160);
+    Graph g;
+    auto& src = g.emplaceBlock<DataSetSource>();
+    src.values.resize(3);
+    for (std::size_t f = 0; f < 3; ++f) src.values[f].signal_values.assign(unfiltered.begin() + static_cast<std::ptrdiff_t>(32 * f), unfiltered.begin() + static_cast<std::ptrdiff_t>(32 * (f + 1)));
+    src._tags  = {{1, {{"window_size", std::int64_t(7)}}}};
+    auto& blk  = g.emplaceBlock<B>({{"window_size", std::int64_t(11)}, {"poly_order", std::int64_t(4)}, {"compute_domain", domain}});
+    auto& sink = g.emplaceBlock<testing::VectorSink<DataSet<float>>>();
+    blk._log   = [](std::string_view m) { std::cerr << "[log] " << m << "\n"; };
+    if (!g.connect<"out", "in">(src, blk) || !g.connect<"out", "in">(blk, sink)) return 2;
+    scheduler::Simple sched;
+    sched.exchange(std::move(g));
+    if (const auto r = sched.runAndWait(); !r) {
+        std::fprintf(stderr, "dataset_retune graph: %s\n", r.error().message.c_str());
+        return 3;
+    }
+    EXPECT(sink._samples.size() == 3 && blk._settings_by_tag == 1 && blk.window_size.value == 7u);
+    for (const auto& ds : sink._samples) filtered.insert(filtered.end(), ds.signal_values.begin(), ds.signal_values.end());
+    EXPECT(filtered.size() == unfiltered.size());
+    dump(dir + "/dataset_retune.in.bin", unfiltered);
+    dump(dir + "/dataset_retune" + (dev ? ".device.bin" : ".host.bin"), filtered);
+    std::printf("dataset_retune: %zu values in 3 DataSets, window_size 11 then 7\n", filtered.size());
+    return 0;
+}
+
 template <typename T>
 static void check_blocks(PluginLoader& loader, const std::string& suffix) {
     using S = filter::SavitzkyGolayFilter<T>;
@@ -193,6 +282,8 @@ int main(int argc, char** argv) {
         if (int rc = stream_graph<float>(domain, dir, "stream_set", {{"window_size", std::int64_t(5)}, {"poly_order", std::int64_t(2)}}, true)) return rc;
         if (int rc = dataset_graph<float, blocks::fft::FFT<float>>(domain, dir, "dataset_f32", 512, {{"window_size", std::int64_t(11)}, {"poly_order", std::int64_t(4)}})) return rc;
         if (int rc = dataset_graph<double, blocks::fft::FFT<double, DataSet<double>>>(domain, dir, "dataset_f64", 256, {{"window_size", std::int64_t(8)}, {"poly_order", std::int64_t(2)}, {"deriv_order", std::int64_t(1)}, {"boundary_policy", "Replicate"s}})) return rc;
+        if (int rc = gap_graph(domain, dir)) return rc;
+        if (int rc = retune_graph(domain, dir)) return rc;
     } catch (const std::exception& e) { // (the planner makes its stages before anything runs: no device, no stage)
         std::fprintf(stderr, "graph: %s\n", e.what());
         return 3;

@@ -97,6 +97,49 @@ static int run_graph(PluginLoader& loader, const std::string& type, const std::s
     return 0;
 }
 
+// threshold by a settings tag at sample `at`: gr4hip_schmitt_set_params, which resets the detector.  From the tag on the edges are therefore those of a second
+// graph that starts at that sample with the new threshold: same names, same positions (moved by `at`), same trigger_offset.  `from` > 0: the stream from there on,
+// the new threshold from the start.  Returns (position in the whole stream, name, offset) of every edge at or behind `at`.
+using FoundEdge = std::tuple<std::size_t, std::string, float>;
+static int edges_behind(PluginLoader& loader, const std::string& domain, const std::string& dir, std::size_t at, bool by_tag, std::vector<FoundEdge>& edges, std::size_t& n_by_tag) {
+    using B = blocks::basic::SchmittTriggerLinear<float>;
+    Graph g;
+    auto& trg = g.addBlock(loader.instantiate("gr::blocks::basic::SchmittTrigger<float32>", {{"offset", 0.1f}, {"threshold", by_tag ? 0.3f : 0.15f}, {"sample_rate", 1000.f}, {"compute_domain", domain}}));
+    auto& src = g.addBlock(loader.instantiate("gr::testing::VectorSource<float32>"));
+    auto& snk = g.addBlock(loader.instantiate("gr::testing::VectorSink<float32>"));
+    auto* vs  = static_cast<testing::VectorSource<float>*>(src.raw());
+    vs->values = read_f32(dir + "/x.f32");
+    if (by_tag) vs->_tags.push_back(Tag{at, property_map{{"threshold", 0.15f}}});
+    else vs->values.erase(vs->values.begin(), vs->values.begin() + static_cast<std::ptrdiff_t>(at));
+    EXPECT(g.connect(src, "out"s, trg, "in"s).has_value() && g.connect(trg, "out"s, snk, "in"s).has_value());
+    auto sched = loader.instantiateScheduler("gr::scheduler::Simple");
+    if (!sched) return 1;
+    sched->exchange(std::move(g));
+    if (const auto r = sched->runAndWait(); !r) {
+        std::fprintf(stderr, "threshold graph: %s\n", r.error().message.c_str());
+        return 3;
+    }
+    n_by_tag = static_cast<B*>(trg.raw())->_settings_by_tag;
+    for (const Tag& t : static_cast<testing::VectorSink<float>*>(snk.raw())->_tags) {
+        const auto name = t.map.find(tag::wireKey(tag::TRIGGER_NAME));
+        const auto off  = t.map.find(tag::wireKey(tag::TRIGGER_OFFSET));
+        if (name == t.map.end() || off == t.map.end()) continue;
+        const std::size_t pos = by_tag ? t.index : t.index + at;
+        if (pos >= at) edges.emplace_back(pos, std::get<std::string>(static_cast<const pmt_base&>(name->second)), std::get<float>(static_cast<const pmt_base&>(off->second)));
+    }
+    return 0;
+}
+static int new_threshold_case(PluginLoader& loader, const std::string& domain, const std::string& dir) {
+    const std::size_t at = read_f32(dir + "/x.f32").size() / 2;
+    std::vector<FoundEdge> changed, fresh;
+    std::size_t       n1 = 0, n2 = 0;
+    if (int rc = edges_behind(loader, domain, dir, at, true, changed, n1)) return rc;
+    if (int rc = edges_behind(loader, domain, dir, at, false, fresh, n2)) return rc;
+    EXPECT(n1 == 1 && n2 == 0 && !fresh.empty() && changed == fresh);
+    std::printf("threshold by settings in mid-stream: %zu edges behind the tag, those of a detector started there: %s\n", changed.size(), changed == fresh ? "yes" : "NO");
+    return 0;
+}
+
 template <typename T>
 static void check_members(PluginLoader& loader, const std::string& suffix, const std::string& domain) {
     using namespace blocks::basic;
@@ -148,6 +191,7 @@ int main(int argc, char** argv) {
         if (int rc = run_graph<SchmittTriggerLinear<float>>(loader, "gr::blocks::basic::SchmittTrigger<float32>", domain, dir, "nofall", 0, false)) return rc;
         if (int rc = run_graph<SchmittTriggerLinear<float>>(loader, "gr::blocks::basic::SchmittTrigger<float32>", domain, dir, "nofwd", 0, true, false)) return rc;
         if (int rc = run_graph<SchmittTriggerLinear<float>>(loader, "gr::blocks::basic::SchmittTrigger<float32>", domain, dir, "cut", 2, true)) return rc;
+        if (int rc = new_threshold_case(loader, domain, dir)) return rc;
     }
     if (failures) std::printf("host-schmitt-trigger: %d FAILURES\n", failures);
     else std::printf("host-schmitt-trigger: all checks passed (compute_domain %s)\n", domain.c_str());

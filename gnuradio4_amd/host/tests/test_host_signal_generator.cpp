@@ -36,6 +36,28 @@ static std::vector<T> run_generator(const std::string& type, const std::string& 
     return sink._samples;
 }
 
+// the source driven by hand: n samples, new amplitude and seed through applySettings (the handle's configure), n samples, reset() (the handle's reset), n samples
+template <typename T>
+static std::vector<T> run_generator_in_parts(const std::string& domain, std::size_t n, int& errors, std::size_t* device_calls = nullptr) {
+    Graph g;
+    auto& src  = g.emplaceBlock<basic::SignalGenerator<T>>({{"signal_type", "UniformNoise"s}, {"sample_rate", 1000.0}, {"amplitude", 1.5}, {"offset", 0.25}, {"seed", std::int64_t(12345)},
+                                                            {"n_samples_max", std::int64_t(3 * n)}, {"compute_domain", domain}});
+    src._log   = [](std::string_view m) { std::cerr << "[log] " << m << "\n"; };
+    auto& sink = g.emplaceBlock<testing::VectorSink<T>>();
+    if (!g.connect<"out", "in">(src, sink)) { ++errors; return {}; }
+    const auto part = [&] {
+        if (const auto r = src.work(n); r.status != work::Status::OK || r.performed_work != n) ++errors;
+        sink.work(std::numeric_limits<std::size_t>::max());
+    };
+    part();
+    src.applySettings({{"amplitude", 0.5}, {"seed", std::int64_t(99)}});
+    part();
+    src.reset();
+    part();
+    if (device_calls) *device_calls = src._device_calls;
+    return sink._samples;
+}
+
 static std::vector<std::complex<float>> run_filtered(bool device_source, std::size_t n, const std::vector<double>& taps, int& errors) {
     using T = std::complex<float>;
     const property_map settings{{"signal_type", "TriangularNoise"s}, {"amplitude", 1.5}, {"offset", 0.25}, {"seed", std::int64_t(777)}, {"n_samples_max", std::int64_t(n)}};
@@ -96,6 +118,16 @@ int main(int argc, char** argv) {
     std::printf("SignalGenerator<complex<float>> Saw gpu:hip:0 == host domain: %s\n", ok_c ? "bit for bit" : "FAILED");
     if (!ok_c) ++failures;
 
+    {
+        const std::size_t m = 4096;
+        std::size_t       part_calls = 0;
+        const auto        dev_p  = run_generator_in_parts<float>("gpu:hip:0", m, errors, &part_calls);
+        const auto        host_p = run_generator_in_parts<float>("host", m, errors);
+        const bool        differ = host_p.size() == 3 * m && !std::equal(host_p.begin(), host_p.begin() + static_cast<std::ptrdiff_t>(m), host_p.begin() + static_cast<std::ptrdiff_t>(m));
+        const bool        ok_p   = dev_p.size() == 3 * m && part_calls == 3 && differ && same_bits(dev_p, host_p);
+        std::printf("SignalGenerator<float> new settings, then reset, between chunks, gpu:hip:0 == host domain: %s (%zu samples, %zu device calls)\n", ok_p ? "bit for bit" : "FAILED", dev_p.size(), part_calls);
+        if (!ok_p) ++failures;
+    }
     std::vector<double> taps(31); // (float32 products in a fixed order per output: the same bits however the two graphs cut the stream into chunks)
     for (std::size_t k = 0; k < taps.size(); ++k) taps[k] = (0.54 - 0.46 * std::cos(2.0 * 3.14159265358979323846 * double(k) / 30.0)) / 16.0;
     const auto from_device = run_filtered(true, n, taps, errors);

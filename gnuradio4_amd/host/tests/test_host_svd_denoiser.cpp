@@ -62,6 +62,42 @@ static int run_graph(PluginLoader& loader, const std::string& domain, const std:
     return 0;
 }
 
+// max_rank by a settings tag at sample `at`: gr4hip_svddenoise_set_params, which resets.  From the tag on the output is therefore that of a second graph that
+// starts at that sample with the new rank, bit for bit (the handle's outputs do not depend on how the stream is cut).  by_tag false: that second graph.
+static int tail_from(PluginLoader& loader, const std::string& domain, const std::string& dir, std::size_t at, bool by_tag, std::vector<float>& tail, std::size_t& n_by_tag) {
+    Graph g;
+    auto& den = g.addBlock(loader.instantiate("gr::filter::SvdDenoiser<float32>", {{"window_size", std::int64_t(64)}, {"max_rank", std::int64_t(by_tag ? 3 : 1)}, {"energy_fraction", 0.95f}, {"compute_domain", domain}}));
+    auto& src = g.addBlock(loader.instantiate("gr::testing::VectorSource<float32>"));
+    auto& snk = g.addBlock(loader.instantiate("gr::testing::VectorSink<float32>"));
+    auto* vs  = static_cast<testing::VectorSource<float>*>(src.raw());
+    vs->values = read_f32(dir + "/x.f32");
+    if (by_tag) vs->_tags.push_back(Tag{at, property_map{{"max_rank", std::int64_t(1)}}});
+    else vs->values.erase(vs->values.begin(), vs->values.begin() + static_cast<std::ptrdiff_t>(at));
+    EXPECT(g.connect(src, "out"s, den, "in"s).has_value() && g.connect(den, "out"s, snk, "in"s).has_value());
+    auto sched = loader.instantiateScheduler("gr::scheduler::Simple");
+    if (!sched) return 1;
+    sched->exchange(std::move(g));
+    if (const auto r = sched->runAndWait(); !r) {
+        std::fprintf(stderr, "rank graph: %s\n", r.error().message.c_str());
+        return 3;
+    }
+    n_by_tag      = static_cast<filter::SvdDenoiser<float>*>(den.raw())->_settings_by_tag;
+    const auto& y = static_cast<testing::VectorSink<float>*>(snk.raw())->_samples;
+    tail.assign(y.begin() + static_cast<std::ptrdiff_t>(by_tag ? std::min(at, y.size()) : 0), y.end());
+    return 0;
+}
+static int new_rank_case(PluginLoader& loader, const std::string& domain, const std::string& dir) {
+    const std::size_t  at = read_f32(dir + "/x.f32").size() / 2;
+    std::vector<float> changed, fresh;
+    std::size_t        n1 = 0, n2 = 0;
+    if (int rc = tail_from(loader, domain, dir, at, true, changed, n1)) return rc;
+    if (int rc = tail_from(loader, domain, dir, at, false, fresh, n2)) return rc;
+    const bool same = !fresh.empty() && changed.size() == fresh.size() && std::memcmp(changed.data(), fresh.data(), fresh.size() * sizeof(float)) == 0;
+    EXPECT(n1 == 1 && n2 == 0 && same);
+    std::printf("max_rank by settings in mid-stream: %zu samples behind the tag, those of a denoiser started there: %s\n", changed.size(), same ? "bit for bit" : "NO");
+    return 0;
+}
+
 template <typename T>
 static void check_members(PluginLoader& loader, const std::string& suffix, const std::string& domain) {
     using B     = filter::SvdDenoiser<T>;
@@ -105,6 +141,7 @@ int main(int argc, char** argv) {
         const std::string dir = argv[3];
         if (int rc = run_graph(loader, domain, dir, "whole", 0)) return rc;
         if (int rc = run_graph(loader, domain, dir, "small", 50)) return rc;
+        if (int rc = new_rank_case(loader, domain, dir)) return rc;
     }
     if (failures) std::printf("host-svd-denoiser: %d FAILURES\n", failures);
     else std::printf("host-svd-denoiser: all checks passed (compute_domain %s)\n", domain.c_str());

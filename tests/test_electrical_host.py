@@ -127,6 +127,8 @@ def write_graph_files(d, seed=5):
         want[f"pf3_{t}_power_factor"], want[f"pf3_{t}_phase"], want[f"pf1_{t}_power_factor"] = pf.ravel(), ph.ravel(), pf[0]
         want[f"ub3_{t}_P_total"], want[f"ub3_{t}_U_unbalance"], want[f"ub3_{t}_I_unbalance"] = EO.system_unbalance(x["U"], x["I"], x["P"])
         _, want[f"ub2_{t}_U_unbalance"], want[f"ub2_{t}_I_unbalance"] = EO.system_unbalance(x["U"][:2], x["I"][:2], x["P"][:2])
+        if t == "f32":  # ub3t: the total power alone connected, the first 256 samples
+            want["ub3t_f32_P_total"] = np.ascontiguousarray(want["ub3_f32_P_total"][:256])
     for k, v in want.items():
         v.setflags(write=False)
         v.tofile(d / f"want_{k}.bin")

@@ -271,6 +271,7 @@ def test_the_host_block_on_the_device_is_the_c_abi(G, device_run, S, B, N, A_, l
     """CrossSpectrum (host) -> AdaptiveWeights on gpu:hip:0 -> sink: what the seam writes is what gr4hip_mvdr_process writes for the same matrices, bit for bit"""
     r, prefix = device_run
     assert r.returncode == 0 and "adaptive weights device: ok" in r.stdout and "FAIL" not in r.stdout
+    assert "steering and loading again on the live handle (by settings in front of matrix 2 of 4): 128 weights" in r.stdout
     tag = f"{prefix}.S{S}.B{B}.N{N}.{form}"
     X = np.fromfile(tag + ".in", np.complex64).reshape(S, 2 * A_, N)
     a = np.fromfile(tag + ".a", np.complex64).reshape((B, S, N) if form == "full" else (B, S))

@@ -350,6 +350,7 @@ def test_the_host_block_on_the_device_is_the_definition(tmp_path):
     r = subprocess.run([HOST_BIN, "device", PLUGIN, prefix], capture_output=True, text=True, timeout=120)
     print(r.stdout[-3000:], r.stderr[-2000:])
     assert r.returncode == 0 and "beamformer device: ok" in r.stdout
+    assert "weights again with the handle kept (new weights by settings): 64 values, device == host" in r.stdout  # new weights between two work() calls
     for S, B, N in ((1, 1, 8), (3, 5, 16), (9, 2, 8)):
         for form in ("full", "short"):
             tag = f"{prefix}.S{S}.B{B}.N{N}.{form}"

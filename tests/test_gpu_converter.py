@@ -376,6 +376,7 @@ def test_graphs_on_the_device(tmp_path):
     print(r.stdout)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "all converter device checks passed" in r.stdout
+    assert "ToRealImag with `imag` open:" in r.stdout and "ScalingConvert scale by settings in mid-stream:" in r.stdout  # (a FAILED line fails the program)
     assert "ingest run: convert_InterleavedToComplex_i16_c32[post: mul,rot] -> fir_c32" in r.stdout
     for kind, t, o in GRAPH_CASES:
         t, o = np.dtype(t), np.dtype(o)

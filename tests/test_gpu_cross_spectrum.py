@@ -290,6 +290,7 @@ def test_the_host_block_on_the_device_is_the_definition(tmp_path):
     r = subprocess.run([HOST_BIN, "device", PLUGIN, prefix], capture_output=True, text=True, timeout=120)
     print(r.stdout[-3000:], r.stderr[-2000:])
     assert r.returncode == 0 and "cross spectrum device: ok" in r.stdout
+    assert "handle re-make (n_integrate 2 -> 4 by settings): 96 values, device == host" in r.stdout  # the seam makes the handle anew between two work() calls
     for S, N, A in ((2, 8, 1), (3, 16, 63), (5, 8, 65), (4, 8, 130)):
         for mean in (False, True):
             tag = f"{prefix}.S{S}.N{N}.A{A}.{'mean' if mean else 'sum'}"

@@ -211,5 +211,6 @@ def test_blocks_in_a_graph(host_bins):  # noqa: F811
     r = subprocess.run([os.path.join(host_bins, "test_host_signal_generator"), "200000"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "SignalGenerator<float> UniformNoise gpu:hip:0 == host domain: bit for bit" in r.stdout
+    assert "SignalGenerator<float> new settings, then reset, between chunks, gpu:hip:0 == host domain: bit for bit" in r.stdout  # configure and reset on the live handle
     assert "hip::SignalSource<complex<float>> -> OnDevice<fir_filter> -> D2H == host SignalGenerator -> H2D -> OnDevice<fir_filter> -> D2H: bit for bit" in r.stdout
     assert "FAILED" not in r.stdout and "all signal generator graph checks passed" in r.stdout

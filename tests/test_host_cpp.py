@@ -151,6 +151,8 @@ def test_device_graphs_match_oracle(host_bins, tmp_path, N, ntaps):
     assert len(got) == frames * N and rel(got, t) <= 1e-5
     # merge API: the reference benchmark's FeedbackMerge IIR collapses into one first-order section of the scan kernel
     assert "merge IIR low-pass (FeedbackMerge) on the device: stage 'iir_f32'" in r.stdout
+    assert "seam FFT<double> 16 -> 32 by settings" in r.stdout
+    assert "seam FFT<complex<float>> 16 -> 32 by settings" in r.stdout  # the FFT seam makes a new plan between two work() calls (a FAILED line fails the program)
     assert "merge MultiplyConst -> fir_filter on the device: stage 'fir_f32[pre: mul]'" in r.stdout
     # kernel-level fusion (the run-time Merge<>): the reference's merged benchmark chains are ONE program each, bit-identical to the merged block on the host ...
     for value in (2, 3):

@@ -117,6 +117,8 @@ def test_device_graph_matches_the_oracle(prog, tmp_path):
     r = subprocess.run([prog, PLUGIN, "gpu:hip:0", str(tmp_path / "ref.f32"), str(tmp_path / "resp.f32"), str(tmp_path / "y")], capture_output=True, text=True,
                        timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
+    assert "invert_phase by settings after two chunks: amplitude unchanged, phase turned from the third chunk on" in r.stdout  # set_params on the live handle
+    assert "phase alone: 1 output, the all-connected graph's bit for bit" in r.stdout  # two outputs without a reader: not copied to a port, the third unchanged
     got = [np.fromfile(tmp_path / f"y_{k}.f32", np.float32).astype(np.float64) for k in ("amp", "phase", "freq")]
     amp, ph, fr, m = IQ.truth(IQ.Params(derivative_method=1, chunk=1024), ref, resp)
     ok = m["decided"]

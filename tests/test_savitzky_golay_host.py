@@ -254,6 +254,26 @@ def check_graph_outputs(tmp_path, tag):
             bar = 2 * (W + 1) * float(np.finfo(dtype).eps) * S * S * float(np.max(np.abs(xin[f])))
             assert np.max(np.abs(got[f].astype(np.float64) - want.astype(np.float64))) <= bar, (name, f)
         out[name] = got
+    # dataset_gap: DataSets of 32, 0 and 32 values through {11, 4, 0, Reflect}; the empty one is passed through, the other two are under the same bar
+    xin = np.fromfile(tmp_path / "dataset_gap.in.bin", np.float32).reshape(2, 32)
+    got = np.fromfile(tmp_path / f"dataset_gap.{tag}.bin", np.float32).reshape(2, 32)
+    c, _ = SG.design(np.float32, 11, 4, 0)
+    S = float(np.abs(c.astype(np.float64)).sum())
+    for f in range(2):
+        want, _ = SG.zero_phase(c, xin[f], "Reflect")
+        bar = 2 * (11 + 1) * float(np.finfo(np.float32).eps) * S * S * float(np.max(np.abs(xin[f])))
+        assert np.max(np.abs(got[f].astype(np.float64) - want.astype(np.float64))) <= bar, ("dataset_gap", f)
+    out["dataset_gap"] = got
+    # dataset_retune: three DataSets of 32 values, {11, 4, 0, Reflect} for the first, window_size 7 by settings from the second on; the same bar per window
+    xin = np.fromfile(tmp_path / "dataset_retune.in.bin", np.float32).reshape(3, 32)
+    got = np.fromfile(tmp_path / f"dataset_retune.{tag}.bin", np.float32).reshape(3, 32)
+    for f, W in enumerate((11, 7, 7)):
+        c, _ = SG.design(np.float32, W, 4, 0)
+        S = float(np.abs(c.astype(np.float64)).sum())
+        want, _ = SG.zero_phase(c, xin[f], "Reflect")
+        bar = 2 * (W + 1) * float(np.finfo(np.float32).eps) * S * S * float(np.max(np.abs(xin[f])))
+        assert np.max(np.abs(got[f].astype(np.float64) - want.astype(np.float64))) <= bar, ("dataset_retune", f)
+    out["dataset_retune"] = got
     return out
 
 

@@ -169,6 +169,7 @@ def test_graphs_on_the_device(prog, tmp_path):
     r = subprocess.run([prog, PLUGIN, "gpu:hip:0", str(tmp_path)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     print(r.stdout)
+    assert "threshold by settings in mid-stream:" in r.stdout and "those of a detector started there: yes" in r.stdout  # set_params on the live handle resets it
     calls = {line.split(":")[0]: int(line.split(" tags, ")[1].split(" device calls")[0]) for line in r.stdout.splitlines() if " device calls" in line}
     drops = {line.split(":")[0]: int(line.split(" device calls, ")[1].split(" dropped edges")[0]) for line in r.stdout.splitlines() if " dropped edges" in line}
     for graph, method, kw in (("no", ST.NO_INTERPOLATION, {}), ("basic", ST.BASIC_LINEAR_INTERPOLATION, {}), ("linear", ST.LINEAR_INTERPOLATION, {}),

@@ -135,6 +135,7 @@ def test_graphs_on_the_device(prog, tmp_path):
     r = subprocess.run([prog, PLUGIN, "gpu:hip:0", str(tmp_path)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     print(r.stdout)
+    assert "max_rank by settings in mid-stream:" in r.stdout and "those of a denoiser started there: bit for bit" in r.stdout  # set_params on the live handle resets it
     calls = {line.split(":")[0]: int(line.split(" samples, ")[1].split(" device calls")[0]) for line in r.stdout.splitlines() if " device calls" in line}
     whole, small = (np.fromfile(tmp_path / f"{g}.f32", np.float32) for g in ("whole", "small"))
     assert whole.size == small.size == x.size
