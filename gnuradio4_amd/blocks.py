@@ -436,6 +436,7 @@ class FFT(_Handle):
                                              _stream()), "FFT.process")
             if ranges:  # fft.hpp:229-232: min / max of the four signals per frame (host-side glue for the float64 corner)
                 out["ranges"] = torch.stack([torch.stack([out[k].amin(dim=1), out[k].amax(dim=1)], dim=1) for k in ("magnitude", "phase", "re", "im")], dim=1)
+            out["frequency"] = np.arange(self.n_out) * (self.sample_rate / self.fftSize)  # frequency axis (fft.hpp:187-193), as for float32 real input
             return out
         mk = lambda: torch.empty((frames, self.n_out), dtype=torch.float32, device=x.device)
         out = {"magnitude": mk(), "phase": mk(), "re": mk(), "im": mk()}

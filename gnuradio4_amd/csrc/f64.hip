@@ -13,6 +13,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 namespace gr4 {
@@ -574,6 +575,10 @@ struct gr4hip_fir64 {
     // the stream rule (common.hpp): create / reset / set_taps only note what the device state has to become; fir64_state_on() enqueues it on the stream of the next call
     std::vector<double> row_host;
     bool                taps_dirty = false;
+    int                 Kp = 64; // taps rounded up to the matrix-pipe kernel's row (fir64_kp)
+    // what the last gr4hip_fir64_process call enqueued (gr4hip_internal_fir64_last_path): {kernel (0 nothing, 1 direct, 2 matrix pipe), R of the direct kernel /
+    // KSC of the matrix-pipe one (0: run-time K-loop), Kp, grid, dynamic LDS bytes, hcap, who wrote the next history (0 the carry launch, 1 the kernel), 0}
+    int                 last_path[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 struct gr4hip_iir64 {
     Iir64Desc    d{};
@@ -587,24 +592,33 @@ struct gr4hip_fft64 {
     int          log2n = 0, flags = 0;
     DeviceBuffer d_win, d_tw;
     bool         windowed = false;
+    // what the last gr4hip_fft64_process call enqueued (gr4hip_internal_fft64_last_path): {kernel (0 nothing, 1 per-frame radix-2, 2 half-size Stockham), grid,
+    // frames per workgroup, dynamic LDS bytes}
+    int          last_path[4] = {0, 0, 0, 0};
 };
 struct gr4hip_rotator64 {
     double inc = 0.0, phase = 0.0, initial = 0.0;
 };
 
+// the matrix-pipe kernel's row: the taps rounded up to 64 / 128 / 256 (compile-time K-loop) or to the next multiple of 64 (run-time K-loop)
+static int fir64_kp(size_t ntaps) { return (int)(ntaps <= 64 ? 64 : ntaps <= 128 ? 128 : ntaps <= 256 ? 256 : (ntaps + 63) / 64 * 64); }
+
 static int fir64_upload(gr4hip_fir64* f, const double* taps, size_t ntaps, bool keep_history) {
-    const size_t hcap = std::max<size_t>(32, bit_ceil(ntaps)); // HistoryBuffer{32}, grown by settingsChanged (time_domain_filter.hpp:36-42)
+    // HistoryBuffer{32}, replaced by settingsChanged only when b.size() > capacity (time_domain_filter.hpp:36-42): the capacity only grows, like gr4hip_fir's
+    const size_t hcap = ntaps > f->hcap ? bit_ceil(ntaps) : f->hcap;
     int          rc   = f->d_taps.ensure(ntaps * sizeof(double)); // (growing frees the old table: hipFree waits for the device)
     if (rc) return rc;
     { // fir64_mfma_kernel: row[16 + q] = b[q], zero elsewhere
-        const size_t         Kp = ntaps <= 64 ? 64 : ntaps <= 128 ? 128 : ntaps <= 256 ? 256 : (ntaps + 63) / 64 * 64;
+        const size_t         Kp = (size_t)fir64_kp(ntaps);
         std::vector<double>& row = f->row_host;
+        f->Kp                    = (int)Kp;
         row.assign(Kp + 32, 0.0);
         for (size_t q = 0; q < ntaps; ++q) row[16 + q] = taps[q];
         rc = f->d_trow.ensure(row.size() * sizeof(double));
         if (rc) return rc;
     }
-    if (!keep_history || hcap != f->hcap || !f->hist.current()) { // a history that has to grow starts empty, as upstream's replaced HistoryBuffer does
+    // a history that has to grow starts empty, as upstream's replaced HistoryBuffer does; shorter taps keep the capacity and with it the stream's history
+    if (!keep_history || hcap != f->hcap || !f->hist.current()) {
         rc = f->hist.resize(hcap * sizeof(double));
         if (rc) return rc;
     }
@@ -650,6 +664,8 @@ int gr4hip_fir64_reset(gr4hip_fir64_t* f) {
 }
 int gr4hip_fir64_process(gr4hip_fir64_t* f, const double* d_in, size_t n_in, double* d_out, size_t* n_out_p, gr4hip_stream_t stream) {
     GR4_REQUIRE(f, "fir64_process: null handle");
+    std::memset(f->last_path, 0, sizeof(f->last_path)); // a call that enqueues nothing says so, with the handle's Kp and hcap
+    f->last_path[2] = f->Kp, f->last_path[5] = (int)f->hcap;
     GR4_REQUIRE(n_in % f->decim == 0, "fir64_process: n_in=%zu is not a multiple of decim=%zu", n_in, f->decim);
     const size_t n_out = n_in / f->decim;
     if (n_out_p) *n_out_p = n_out;
@@ -659,7 +675,7 @@ int gr4hip_fir64_process(gr4hip_fir64_t* f, const double* d_in, size_t n_in, dou
     if (const int rc = fir64_state_on(f, st)) return rc;
     const int   K = (int)f->taps.size(), D = (int)f->decim;
     if (D == 1 && K > 16 && n_in >= 32768 && (uintptr_t)d_out % 16 == 0 && f->d_trow.ptr) { // matrix-pipe form; writes the next history itself
-        const int    Kp = K <= 64 ? 64 : K <= 128 ? 128 : K <= 256 ? 256 : (K + 63) / 64 * 64, NPAD = (kF64Seg + Kp) / 16 * 18;
+        const int    Kp = f->Kp, NPAD = (kF64Seg + Kp) / 16 * 18;
         const size_t lds = ((size_t)NPAD + Kp + 32) * sizeof(double);
         const dim3   grid((unsigned)ceil_div(ceil_div((long)n_in, (long)kF64Seg), (long)kF64SegPerWg));
         const auto   hp = (const double*)f->hist.current();
@@ -675,6 +691,7 @@ int gr4hip_fir64_process(gr4hip_fir64_t* f, const double* d_in, size_t n_in, dou
 #undef GR4_F64_MFMA
         GR4_LAUNCH_CHECK();
         f->hist.flip();
+        f->last_path[0] = 2, f->last_path[1] = Kp <= 256 ? (Kp + 16) / 4 : 0, f->last_path[3] = (int)grid.x, f->last_path[4] = (int)lds, f->last_path[6] = 1;
         return GR4HIP_OK;
     }
     const int   R = D <= 8 ? 4 : D <= 16 ? 2 : 1;
@@ -684,7 +701,15 @@ int gr4hip_fir64_process(gr4hip_fir64_t* f, const double* d_in, size_t n_in, dou
     const unsigned grid = (unsigned)ceil_div(n_out, (size_t)kF64BS * R);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kF64BS), lds, st, d_in, (const double*)f->hist.current(), (int)f->hcap, (const double*)f->d_taps.ptr, K, D, d_out, (long)n_out, (long)n_in);
     GR4_LAUNCH_CHECK();
+    f->last_path[0] = 1, f->last_path[1] = R, f->last_path[3] = (int)grid, f->last_path[4] = (int)lds;
     return f->hist.advance(d_in, n_in, f->hcap, sizeof(double), st);
+}
+// test hook (not in include/gr4hip.h; tests/test_gpu_float64_paths.py): what the last gr4hip_fir64_process call of this handle enqueued -- the fields of
+// gr4hip_fir64::last_path.  Kp and hcap are the handle's at that call, also where it enqueued nothing (n_in == 0, or a refused call).
+int gr4hip_internal_fir64_last_path(const gr4hip_fir64_t* f, int* rec /*[8]*/) {
+    GR4_REQUIRE(f && rec, "fir64_last_path: bad argument");
+    std::memcpy(rec, f->last_path, sizeof(f->last_path));
+    return GR4HIP_OK;
 }
 int gr4hip_fir64_destroy(gr4hip_fir64_t* f) { delete f; return GR4HIP_OK; }
 
@@ -846,6 +871,7 @@ int gr4hip_fft64_create(gr4hip_fft64_t** out, size_t fft_size, int window, int f
 }
 int gr4hip_fft64_process(gr4hip_fft64_t* f, const double* d_in, size_t n_frames, double* d_mag, double* d_phase, double* d_re, double* d_im, gr4hip_stream_t stream) {
     GR4_REQUIRE(f, "fft64_process: null handle");
+    std::memset(f->last_path, 0, sizeof(f->last_path));
     if (n_frames == 0) return GR4HIP_OK;
     GR4_REQUIRE(d_in, "fft64_process: null input");
     hipStream_t  st  = as_stream(stream);
@@ -857,6 +883,7 @@ int gr4hip_fft64_process(gr4hip_fft64_t* f, const double* d_in, size_t n_frames,
         hipLaunchKernelGGL(fft64_r2c_kernel, dim3((unsigned)ceil_div(n_frames, fpb)), dim3(256), lds, st, d_in, f->windowed ? (const double*)f->d_win.ptr : nullptr, (const double2*)f->d_tw.ptr,
                            f->log2n, (long)n_frames, o);
         GR4_LAUNCH_CHECK();
+        f->last_path[0] = 2, f->last_path[1] = (int)ceil_div(n_frames, fpb), f->last_path[2] = (int)fpb, f->last_path[3] = (int)lds;
         return GR4HIP_OK;
     }
     const size_t lds = f->N * sizeof(double2);
@@ -865,6 +892,14 @@ int gr4hip_fft64_process(gr4hip_fft64_t* f, const double* d_in, size_t n_frames,
     hipLaunchKernelGGL(fft64_kernel, dim3((unsigned)n_frames), dim3(256), lds, st, d_in, f->windowed ? (const double*)f->d_win.ptr : nullptr, (const double2*)f->d_tw.ptr, f->log2n,
                        (long)n_frames, o);
     GR4_LAUNCH_CHECK();
+    f->last_path[0] = 1, f->last_path[1] = (int)n_frames, f->last_path[2] = 1, f->last_path[3] = (int)lds;
+    return GR4HIP_OK;
+}
+// test hook (not in include/gr4hip.h; tests/test_gpu_float64_paths.py): what the last gr4hip_fft64_process call of this handle enqueued -- the fields of
+// gr4hip_fft64::last_path
+int gr4hip_internal_fft64_last_path(const gr4hip_fft64_t* f, int* rec /*[4]*/) {
+    GR4_REQUIRE(f && rec, "fft64_last_path: bad argument");
+    std::memcpy(rec, f->last_path, sizeof(f->last_path));
     return GR4HIP_OK;
 }
 int gr4hip_fft64_destroy(gr4hip_fft64_t* f) { delete f; return GR4HIP_OK; }
