@@ -472,6 +472,98 @@ class FFT(_Handle):
         return integrator._run(lib().gr4hip_fft_mag2_integrate, self._h, x, frames, out, "FFT.power_integrated")
 
 
+class STFT(_Handle):
+    """The FFT block with the reference's `stride` setting (Block.hpp:711), stated for a stream (OVERLAPPED_FFT.md): frame m covers the samples
+    [m stride, m stride + fftSize) and leaves once its last sample has arrived -- stride < fftSize overlaps frames (spectrograms, Welch averaging), stride > fftSize
+    skips samples, 0 means fftSize.  The last fftSize - 1 samples are carried across calls, so the values do not depend on how a stream is cut; every frame's outputs
+    are those of FFT(fftSize, window, ...) on that frame."""
+    _destroy = "gr4hip_stft_destroy"
+
+    def __init__(self, fftSize: int = 1024, stride: int = 0, window="Hann", outputInDb=False, outputInDeg=False, unwrapPhase=False, dtype=torch.complex64,
+                 sample_rate: float = 1.0):
+        super().__init__()
+        if dtype not in (torch.complex64, torch.float32):
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "STFT", f"complex64 or float32 frames (got {dtype})")
+        self.fftSize, self.stride, self.window, self.dtype, self.sample_rate = int(fftSize), int(stride) or int(fftSize), window, dtype, sample_rate
+        self.outputInDb, self.outputInDeg, self.unwrapPhase = outputInDb, outputInDeg, unwrapPhase
+        flags = (capi.FFT_OUTPUT_IN_DB if outputInDb else 0) | (capi.FFT_OUTPUT_IN_DEG if outputInDeg else 0) | (capi.FFT_UNWRAP_PHASE if unwrapPhase else 0)
+        self.n_out = self.fftSize if dtype == torch.complex64 else self.fftSize // 2
+        self._frames_out = 0  # frames emitted since create / reset: the index of the next one
+        check(lib().gr4hip_stft_create(C.byref(self._h), _DTYPE_ID[dtype], self.fftSize, self.stride, _window_id(window), flags), "STFT")
+
+    def reset(self):
+        """the next sample starts a new stream"""
+        check(lib().gr4hip_stft_reset(self._h), "STFT.reset")
+        self._frames_out = 0
+
+    def pending(self, n: int) -> int:
+        """frames the next call of n samples emits (host only)"""
+        k = C.c_size_t(0)
+        check(lib().gr4hip_stft_pending(self._h, int(n), C.byref(k)), "STFT.pending")
+        return int(k.value)
+
+    def _in(self, x):
+        x = _dev(x, "STFT").reshape(-1)
+        if x.dtype != self.dtype:
+            raise capi.Gr4HipError(capi.INVALID_ARGUMENT, "STFT", f"expected {self.dtype}, got {x.dtype}")
+        return x, self.pending(x.numel())
+
+    def _done(self, got, k, what="STFT"):
+        if got.value != k:
+            raise capi.Gr4HipError(capi.RUNTIME_ERROR, what, f"the call emitted {got.value} frames, pending() said {k}")
+        self._frames_out += k
+
+    def process_bulk(self, x: torch.Tensor, ranges: bool = True) -> dict:
+        """FFT.process_bulk's dict for the frames this call completes, plus `time`: their start times"""
+        x, k = self._in(x)
+        rows = max(k, 1)  # (a call too short for a frame still names its outputs: the library refuses a call whose outputs are all null)
+        mk = lambda: torch.empty((rows, self.n_out), dtype=torch.float32, device=x.device)
+        full = {"magnitude": mk(), "phase": mk(), "re": mk(), "im": mk()}
+        rg = torch.empty((rows, 4, 2), dtype=torch.float32, device=x.device) if ranges else None
+        got = C.c_size_t(0)
+        first = self._frames_out
+        check(lib().gr4hip_stft_process(self._h, x.data_ptr(), x.numel(), full["magnitude"].data_ptr(), full["phase"].data_ptr(), full["re"].data_ptr(),
+                                        full["im"].data_ptr(), rg.data_ptr() if ranges else None, C.byref(got), _stream()), "STFT.process")
+        self._done(got, k, "STFT.process")
+        out = {key: v[:k] for key, v in full.items()}
+        if ranges:
+            out["ranges"] = rg[:k]
+        n = self.n_out
+        fw = self.sample_rate / self.fftSize
+        out["frequency"] = (np.arange(n) * fw - (n // 2) * fw) if self.dtype == torch.complex64 else np.arange(n) * fw
+        out["time"] = (first + np.arange(k)) * (self.stride / self.sample_rate)
+        return out
+
+    def _one(self, entry, x, out, dtype, what):
+        x, k = self._in(x)
+        out = _out(out, max(k, 1) * self.fftSize, dtype, x, what, (max(k, 1), self.fftSize))  # (never a null output: see process_bulk)
+        got = C.c_size_t(0)
+        check(entry(self._h, x.data_ptr(), x.numel(), out.data_ptr(), C.byref(got), _stream()), what)
+        self._done(got, k, what)
+        return out.reshape(-1)[:k * self.fftSize].view(k, self.fftSize)
+
+    def spectrum(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """complex64 [frames, fftSize], natural bin order"""
+        return self._one(lib().gr4hip_stft_spectrum, x, out, torch.complex64, "STFT.spectrum")
+
+    def mag2(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """|X|^2, float32 [frames, fftSize]"""
+        return self._one(lib().gr4hip_stft_mag2, x, out, torch.float32, "STFT.mag2")
+
+    def power_integrated(self, x: torch.Tensor, integrator: "SpectrumIntegrator", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Welch: mag2() followed by integrator.process_bulk(), bit for bit, without the frames' |X|^2 in the caller's memory (gr4hip_stft_mag2_integrate)"""
+        x, k = self._in(x)
+        n = integrator.pending(k)
+        out = _out(out, n * self.fftSize, torch.float32, x, "STFT.power_integrated", (n, self.fftSize))
+        got = C.c_size_t(0)
+        check(lib().gr4hip_stft_mag2_integrate(self._h, integrator._h, x.data_ptr(), x.numel(), out.data_ptr() if n else None, C.byref(got), _stream()),
+              "STFT.power_integrated")
+        if got.value != n:
+            raise capi.Gr4HipError(capi.RUNTIME_ERROR, "STFT.power_integrated", f"the call completed {got.value} spectra, pending() said {n}")
+        self._frames_out += k
+        return out.reshape(-1)[:n * self.fftSize].view(n, self.fftSize)
+
+
 def design_pfb(n_channels: int, taps_per_channel: int, window="Hamming", beta: float = 1.6) -> np.ndarray:
     """the bank's windowed-sinc prototype h[j] = w[j] sinc((j - (P N - 1) / 2) / N), float32 [P N] (gr4hip_pfb_design: host code, no device)"""
     h = np.empty(int(n_channels) * int(taps_per_channel), np.float32)

@@ -138,6 +138,14 @@ SIGNATURES = {
     "gr4hip_specint_leaf": (_sz, []),
     "gr4hip_fft_mag2_integrate": (_i, [_vp, _vp, _vp, _sz, _vp, _psz, _vp]),
     "gr4hip_pfb_power_integrate": (_i, [_vp, _vp, _vp, _sz, _vp, _psz, _vp]),
+    "gr4hip_stft_create": (_i, [_pvp, _i, _sz, _sz, _i, _i]),
+    "gr4hip_stft_reset": (_i, [_vp]),
+    "gr4hip_stft_pending": (_i, [_vp, _sz, _psz]),
+    "gr4hip_stft_process": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _psz, _vp]),
+    "gr4hip_stft_spectrum": (_i, [_vp, _vp, _sz, _vp, _psz, _vp]),
+    "gr4hip_stft_mag2": (_i, [_vp, _vp, _sz, _vp, _psz, _vp]),
+    "gr4hip_stft_mag2_integrate": (_i, [_vp, _vp, _vp, _sz, _vp, _psz, _vp]),
+    "gr4hip_stft_destroy": (_i, [_vp]),
     "gr4hip_xcorr_create": (_i, [_pvp, _sz, _sz, _sz, _i]),
     "gr4hip_xcorr_reset": (_i, [_vp]),
     "gr4hip_xcorr_set_length": (_i, [_vp, _sz]),

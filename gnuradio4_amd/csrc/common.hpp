@@ -39,6 +39,7 @@ enum DevSwitch {
     kDevSiggenGaussPermille,  // GR4HIP_SIGGEN_GAUSS_PERMILLE: an integer; non-zero: the Gaussian signal generator launches this many attempts per 1000 needed pairs (0: its own formula); the tests reach the tail kernel with it
     kDevInterpNoMfma,         // GR4HIP_INTERP_NO_MFMA: the interpolating FIR's register-window / generic kernels also on the long spans that the matrix-pipe kernel takes (the tests compare them)
     kDevInterpSpw,            // GR4HIP_INTERP_SPW: an integer; 1 .. 4: the interpolating FIR's matrix-pipe kernel gives every workgroup this many segments (0: clamp(segments / 2048, 1, 4)); the tests reach the multi-segment loop at spans of a few segments with it
+    kDevStftGather,           // GR4HIP_STFT_GATHER: an integer; 1: overlapped FFT frames are gathered into contiguous frames for the FFT block's kernels also where the hop front end reads them in place, 2: the hop front end also for the short calls with a seam that the default sends to the gather path (the tests compare them)
     kDevSwitchCount
 };
 int dev_switch(DevSwitch s);

@@ -18,6 +18,7 @@
 #include "fft_kernels.hpp"
 #include "fft_smooth.hpp"
 #include "specint_kernels.hpp"
+#include "stft_kernels.hpp"
 
 namespace gr4 {
 
@@ -767,10 +768,13 @@ static int fft_run_multi(gr4hip_fft_t* f, const float* d_in, long n_frames, cons
     return GR4HIP_OK;
 }
 
-static int fft_run(gr4hip_fft_t* f, const void* d_in, size_t n_frames, FftOutputs o, float* d_phase_final, float* d_ranges, gr4hip_stream_t stream) {
+// front: another first-pass load in front of fft_fast_kernel's passes and epilogue (gr4::fft_block_run below) -- it enqueues the transform of the call's frames
+// in place of fft_launch, everything around it (flags, the unwrap scratch, unwrap and ranges) is this function's
+static int fft_run(gr4hip_fft_t* f, const void* d_in, size_t n_frames, FftOutputs o, float* d_phase_final, float* d_ranges, gr4hip_stream_t stream,
+                   gr4::FftFrontLaunch front = nullptr, void* front_ctx = nullptr) {
     GR4_REQUIRE(f, "fft: null handle");
     if (n_frames == 0) return GR4HIP_OK;
-    GR4_REQUIRE(d_in, "fft: null input");
+    GR4_REQUIRE(d_in || front, "fft: null input");
     hipStream_t st   = as_stream(stream);
     o.real_input     = f->in_dtype == GR4HIP_F32;
     o.in_db          = (f->flags & GR4HIP_FFT_OUTPUT_IN_DB) != 0;
@@ -794,8 +798,8 @@ static int fft_run(gr4hip_fft_t* f, const void* d_in, size_t n_frames, FftOutput
     const bool fast         = f->N >= 256 && f->N <= 8192 && !f->plan.smooth; // fft_fast_kernel sizes (powers of two; the mixed-radix kernel leaves the ranges to ranges_kernel)
     const bool fused_ranges = d_ranges && fast && !unwrap;  // the unwrapped phase only exists after unwrap_kernel
     o.ranges                = fused_ranges ? d_ranges : nullptr;
-    int rc = fft_launch(f->plan, static_cast<const float*>(d_in), static_cast<const float*>(f->d_window.ptr), static_cast<const float2*>(f->d_tw.ptr), o,
-                        (long)n_frames, st);
+    int rc = front ? front(front_ctx, o, (long)n_frames, st)
+                   : fft_launch(f->plan, static_cast<const float*>(d_in), static_cast<const float*>(f->d_window.ptr), static_cast<const float2*>(f->d_tw.ptr), o, (long)n_frames, st);
     if (rc) return rc;
     return fft_finish(f, o, d_phase_final, d_ranges, n_frames, nout, unwrap, fused_ranges, st);
 }
@@ -903,6 +907,22 @@ int gr4hip_fft_mag2_integrate(gr4hip_fft_t* f, gr4hip_specint_t* si, const void*
 }
 
 int gr4hip_fft_destroy(gr4hip_fft_t* f) { delete f; return GR4HIP_OK; }
+
+} // extern "C"
+
+namespace gr4 { // the FFT block as a building block of the overlapped-frame handle (stft.hip; declared in stft_kernels.hpp)
+FftBlockView fft_block_view(const gr4hip_fft* f) {
+    return {f->N, f->in_dtype, f->kind, f->plan.smooth, static_cast<const float*>(f->d_window.ptr), static_cast<const float2*>(f->d_tw.ptr)};
+}
+// every output of gr4hip_fft_process / _spectrum / _mag2 (those `o` names) on the block kernels, never the 8192-point frame pipeline: the values do not depend on
+// the call's frame count.  front != null (complex frames of 256 .. 8192 points, kind 0): the frames come from its launches, d_in is not read
+int fft_block_run(gr4hip_fft* f, const void* d_in, size_t n_frames, const FftOutputs& o, float* d_phase, float* d_ranges, FftFrontLaunch front, void* ctx, gr4hip_stream_t stream) {
+    if (front && !(f->kind == 0 && !f->plan.smooth && f->N >= 256 && f->in_dtype == GR4HIP_C32)) { set_error("fft: internal: no front end for this transform"); return GR4HIP_RUNTIME_ERROR; }
+    return fft_run(f, d_in, n_frames, o, d_phase, d_ranges, stream, front, ctx);
+}
+} // namespace gr4
+
+extern "C" {
 
 int gr4hip_fft_plan(size_t fft_size, int* kind, int* radices, int* n_passes) {
     GR4_REQUIRE(kind && radices && n_passes, "fft_plan: null argument");

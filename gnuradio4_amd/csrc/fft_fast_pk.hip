@@ -9,6 +9,7 @@
 #endif
 #include "specint_kernels.hpp"
 #include "ifft_kernels.hpp"
+#include "stft_kernels.hpp"
 
 namespace gr4 {
 int fft_fast_launch_256(const float* d_in, const float* d_window, const float2* d_tw, const FftOutputs& o, long n_frames, hipStream_t st) {
@@ -28,6 +29,9 @@ int pfb_run_launch_8192(int P, const float* x, const float* hist, const float* t
     default: *taken = false; return GR4HIP_OK;
     }
 }
+// the overlapped-frame kernels of the same two sizes (OVERLAPPED_FFT.md): the same passes behind the hop front end
+int hop_fast_launch_256(const HopFront& front, const float* d_window, const float2* d_tw, const FftOutputs& o, long n_frames, hipStream_t st) { return hop_fast_launch<8>(front, d_window, d_tw, o, n_frames, st); }
+int hop_fast_launch_8192(const HopFront& front, const float* d_window, const float2* d_tw, const FftOutputs& o, long n_frames, hipStream_t st) { return hop_fast_launch<13>(front, d_window, d_tw, o, n_frames, st); }
 // the spectrum integrator's sinks of the same two sizes (SPECTRUM_INTEGRATOR.md): their values have to equal these kernels' bit for bit.  8192 points: the 16
 // accumulators do not fit beside the transform's 116 registers, so that size has 256 registers per lane and one workgroup per CU
 int fft_sink_launch_256(const float* x, const float* window, const float2* tw, const SpecintLaunch& L, hipStream_t st) { return fft_sink_launch<8, 2>(x, window, tw, L, st); }

@@ -44,6 +44,7 @@ if stale $OUT/test_host_electrical tests/test_host_electrical.cpp; then $CXX -O2
 if stale $OUT/test_host_savitzky_golay tests/test_host_savitzky_golay.cpp; then $CXX -O2 tests/test_host_savitzky_golay.cpp -o $OUT/test_host_savitzky_golay $LINK -ldl & pids+=($!); fi
 if stale $OUT/test_host_complex_fir tests/test_host_complex_fir.cpp; then $CXX -O2 tests/test_host_complex_fir.cpp -o $OUT/test_host_complex_fir $LINK -ldl & pids+=($!); fi
 if stale $OUT/test_host_pfb tests/test_host_pfb.cpp; then $CXX -O2 tests/test_host_pfb.cpp -o $OUT/test_host_pfb $LINK -ldl & pids+=($!); fi
+if stale $OUT/test_host_stft tests/test_host_stft.cpp; then $CXX -O2 tests/test_host_stft.cpp -o $OUT/test_host_stft $LINK -ldl & pids+=($!); fi
 if stale $OUT/test_host_ifft tests/test_host_ifft.cpp; then $CXX -O2 tests/test_host_ifft.cpp -o $OUT/test_host_ifft $LINK -ldl & pids+=($!); fi
 if stale $OUT/test_host_rational_resampler tests/test_host_rational_resampler.cpp; then $CXX -O2 tests/test_host_rational_resampler.cpp -o $OUT/test_host_rational_resampler $LINK -ldl & pids+=($!); fi
 if stale $OUT/test_host_spectrum_integrator tests/test_host_spectrum_integrator.cpp; then $CXX -O2 tests/test_host_spectrum_integrator.cpp -o $OUT/test_host_spectrum_integrator $LINK -ldl & pids+=($!); fi

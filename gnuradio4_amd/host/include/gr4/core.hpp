@@ -774,6 +774,8 @@ struct BlockModel {
     virtual std::shared_ptr<void> make_device_stage() { return nullptr; }
     // settings-by-tag for a block that is driven from outside its own work loop (a member of a fused device run)
     virtual bool apply_tag_settings(const property_map&) { return false; }
+    // the block's `stride` setting is active (Block.hpp:1548): its frames overlap or skip samples, so it runs through its own work loop, not as a member of a fused run
+    virtual bool stride_active() const { return false; }
 };
 
 // ---------------------------------------------------------------------------------------------- Block<Derived, Args...> (Block.hpp)
@@ -782,6 +784,8 @@ template <typename Derived>
 struct Kernel; // device implementation of a block type, specialised in gr4/hip.hpp; primary template is intentionally undefined
 template <typename Derived>
 concept HasKernel = requires { sizeof(Kernel<Derived>); };
+template <typename Derived>
+concept HasStrideKernel = HasKernel<Derived> && requires { Kernel<Derived>::kStride; }; // its stage takes (k - 1) stride + chunk samples and emits k chunks (gr4hip_stft_*)
 } // namespace hip
 
 template <typename Derived, typename... Args>
@@ -791,6 +795,9 @@ struct Block {
     std::string   name = "block";
     std::string   compute_domain = "host"; // Block.hpp:713
     Size_t        input_chunk_size = static_cast<Size_t>(ResamplingControl::kIn), output_chunk_size = static_cast<Size_t>(ResamplingControl::kOut);
+    Size_t        stride = 0;        // Block.hpp:711: samples between the starts of two chunks; 0 or input_chunk_size: back to back (inactive)
+    Size_t        strideCounter = 0; // Block.hpp: samples of the current stride still to be skipped before the next chunk (stride > chunk)
+    [[nodiscard]] bool strideActive() const { return stride != 0 && stride != input_chunk_size; } // isStrideActiveAndNotDefault, Block.hpp:1548
     ComputeDomain _domain{};
     bool          _warned_device_fallback = false;
     std::function<void(std::string_view)> _log = [](std::string_view) {};
@@ -805,7 +812,7 @@ struct Block {
         if constexpr (requires(Derived& d) { d.hasSettingOverride(key); }) {
             if (self().hasSettingOverride(key)) return true;
         }
-        bool found = false;
+        bool found = key == "stride";
         detail::for_each_member(self(), [&](std::string_view mname, auto& member) {
             using M = std::decay_t<decltype(member)>;
             if constexpr (!detail::is_port<M>::value && !detail::is_port_vector<M>::value) {
@@ -822,6 +829,12 @@ struct Block {
         for (const auto& [key, value] : newSettings) {
             if (key == "name") { detail::assign_from(name, value); continue; }
             if (key == "compute_domain") { detail::assign_from(compute_domain, value); _domain = ComputeDomain::parse(compute_domain); continue; }
+            if (key == "stride") { // every block's (Block.hpp:711); a new stride starts at the next sample, and a device stage built for the old one is stale
+                if (!detail::assign_from(stride, value)) throw std::invalid_argument("setting 'stride': incompatible value type");
+                strideCounter = 0;
+                ++_settings_generation;
+                continue;
+            }
             bool found = false;
             detail::for_each_member(self(), [&](std::string_view mname, auto& member) {
                 using M = std::decay_t<decltype(member)>;
@@ -933,6 +946,7 @@ private:
         });
         each_out([&](auto& p) { if (p.connected()) space = std::min(space, p.buffer->free_space()); });
         if (!any_in) return {requested, 0, work::Status::ERROR};
+        if (strideActive()) return strideWork(requested, avail, space, maxIn, upstream_done);
         const std::size_t ic = std::max<std::size_t>(1, input_chunk_size), oc = std::max<std::size_t>(1, output_chunk_size);
         // a chunk ends where the next tag starts, so that every tag sits on the first sample of a chunk (Block.hpp:1511-1530, 1961-1971);
         // never below one input chunk (ensureMinimalDecimation): tags inside such a forced chunk are merged into the chunk's own tag below
@@ -998,6 +1012,55 @@ private:
         return {requested, nIn, work::Status::OK};
     }
 
+    // The work loop with an active stride (stride != 0 && stride != input_chunk_size): chunk m of the stream covers the samples [m stride, m stride + chunk).
+    //   1. skip what is left of the last stride (inputSamplesToSkipBeforeNextChunk, Block.hpp:1546-1557);
+    //   2. take ONE chunk (computeResampling, Block.hpp:1611-1616) -- behind a device seam that knows strides (hip::HasStrideKernel) all k whole chunks that are
+    //      visible: (k - 1) stride + chunk samples in, k chunks out, the stream of the one-chunk loop;
+    //   3. consume min(k stride, what was read) and note the rest in strideCounter (inputSamplesToConsumeAdjustedWithStride, Block.hpp:1563-1574).
+    // Tags on the samples that leave the buffer are applied as settings and forwarded at the first output sample, like those of a forced chunk above.
+    work::Result strideWork(std::size_t requested, std::size_t avail, std::size_t space, std::size_t maxIn, bool upstream_done) {
+        const std::size_t ic = std::max<std::size_t>(1, input_chunk_size), oc = std::max<std::size_t>(1, output_chunk_size), S = stride;
+        std::size_t       skipped = 0;
+        if (strideCounter > 0) {
+            skipped = std::min<std::size_t>(strideCounter, avail);
+            each_in([&](auto& p) { if (p.connected()) p.buffer->consume(skipped); });
+            strideCounter -= static_cast<Size_t>(skipped);
+            avail -= skipped;
+        }
+        if (strideCounter > 0 || avail < ic) {
+            if (upstream_done) { // the trailing partial chunk is dropped
+                each_in([&](auto& p) { if (p.connected()) p.buffer->consume(p.buffer->available()); });
+                each_out([&](auto& p) { if (p.connected()) p.buffer->producer_done = true; });
+                return {requested, skipped, work::Status::DONE};
+            }
+            return {requested, skipped, skipped ? work::Status::OK : work::Status::INSUFFICIENT_INPUT_ITEMS};
+        }
+        const std::size_t lim  = std::min({avail, maxIn, requested});
+        std::size_t       k    = lim < ic ? 0 : std::min((lim - ic) / S + 1, space / oc);
+        bool              many = false;
+        if constexpr (hip::HasStrideKernel<Derived>) many = _domain.is_device();
+        if (!many) k = std::min<std::size_t>(k, 1);
+        if (k == 0) return {requested, skipped, skipped ? work::Status::OK : work::Status::INSUFFICIENT_OUTPUT_ITEMS};
+        const std::size_t nRead = (k - 1) * S + ic, nOut = k * oc, nConsume = std::min(k * S, nRead);
+        property_map      chunkTags;
+        each_in([&](auto& p) {
+            if (!p.connected()) return;
+            for (auto& kv : p.buffer->mergedTags(nConsume)) chunkTags.insert_or_assign(kv.first, std::move(kv.second));
+        });
+        if (!chunkTags.empty() && applyTagSettings(chunkTags) && (!strideActive() || input_chunk_size != ic || output_chunk_size != oc || stride != S))
+            return {requested, skipped, work::Status::OK}; // the tag changed the chunking: the next call sizes the chunk anew (the tag's values are then the active ones)
+        const work::Status st = dispatch(nRead, nOut);
+        if (st == work::Status::ERROR) return {requested, 0, st};
+        if (!chunkTags.empty() && !(std::is_same_v<Args, NoTagPropagation> || ...)) {
+            const property_map fwd = toOutputTags(chunkTags);
+            each_out([&](auto& p) { if (p.connected()) p.buffer->publishTag(fwd, 0); });
+        }
+        each_out([&](auto& p) { if (p.connected()) p.buffer->publish(nOut); });
+        each_in([&](auto& p) { p.buffer->consume(nConsume); });
+        strideCounter = static_cast<Size_t>(k * S - nConsume);
+        return {requested, skipped + nConsume, work::Status::OK};
+    }
+
     // dispatchProcessing (Block.hpp:1848-1917) for the 1-in/1-out and N-in/1-out shapes on the hot path
     work::Status dispatch(std::size_t nIn, std::size_t nOut) {
         if (_domain.is_device()) { // the device seam (Block.hpp:1855-1862)
@@ -1052,6 +1115,7 @@ struct BlockWrapper final : BlockModel {
     std::string_view     name() const override { return block.name; }
     std::string_view     type_name() const override { return _type; }
     const ComputeDomain& compute_domain() const override { return block._domain; }
+    bool                 stride_active() const override { return block.strideActive(); }
     void*                raw() override { return &block; }
 
     template <typename F>

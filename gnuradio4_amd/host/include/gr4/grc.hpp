@@ -7,6 +7,7 @@
 //           name: lowpass
 //           b: [0.5, 0.25, 0.25]
 //           compute_domain: "gpu:hip:0"
+//           stride: 512                     # every block's (Block.hpp:711): samples between chunk starts; 0 or the chunk size: back to back
 //     connections:
 //       - [source, 0, lowpass, 0]            # [source block, output port, destination block, input port]
 //       - [lowpass, out, sink, in]           # ports by index, by [index, sub-index] (vector ports) or by name

@@ -365,6 +365,26 @@ struct PowerSpectrumStage final : Stage {
     }
 };
 
+// PowerSpectrum with an active `stride` (gr4hip_stft_*, OVERLAPPED_FFT.md): a call hands over the (k - 1) stride + N samples of k whole frames, frame m at m stride,
+// and gets k N values.  The block's work loop owns the stream position (it consumes k stride samples and presents the overlap again), so the handle starts every
+// call at a frame start: reset, then one call.
+struct StftPowerStage final : Stage {
+    Handle<gr4hip_stft_t, gr4hip_stft_destroy> h;
+    std::size_t N, S;
+    StftPowerStage(std::size_t fftSize, std::size_t stride, int win) : N(fftSize), S(stride) {
+        in_bytes = 8; out_bytes = 4; in_chunk = out_chunk = fftSize;
+        check(gr4hip_stft_create(h.out(), GR4HIP_C32, fftSize, stride, win, 0), "gr4hip_stft_create");
+    }
+    std::string_view kind() const override { return "power_spectrum_c32[stride]"; }
+    int enqueue(const void* in, std::size_t n, void* out, std::size_t* n_out, gr4hip_stream_t s) override {
+        if (const int rc = gr4hip_stft_reset(h)) return rc;
+        std::size_t k  = 0;
+        const int   rc = gr4hip_stft_mag2(h, in, n, static_cast<float*>(out), &k, s);
+        *n_out = k * N;
+        return rc;
+    }
+};
+
 // polyphase filter bank (gr4hip_pfb_*): PfbPowerSpectrum (|X|^2, float out) and PfbChannelizer (the spectrum, complex out); whole frames of N samples
 struct PfbStage final : Stage {
     Handle<gr4hip_pfb_t, gr4hip_pfb_destroy> h;
@@ -1017,7 +1037,11 @@ struct Kernel<gr::blocks::math::MathOpImpl<T, op>> {
 template <>
 struct Kernel<gr::blocks::fft::PowerSpectrum<std::complex<float>>> {
     using B = gr::blocks::fft::PowerSpectrum<std::complex<float>>;
-    static std::unique_ptr<Stage> make_stage(B& b) { return std::make_unique<PowerSpectrumStage>(b.fftSize, window_id(b.window)); }
+    static constexpr bool kStride = true; // with an active stride the work loop hands over all whole frames in sight (core.hpp strideWork)
+    static std::unique_ptr<Stage> make_stage(B& b) {
+        if (b.strideActive()) return std::make_unique<StftPowerStage>(b.fftSize, b.stride, window_id(b.window));
+        return std::make_unique<PowerSpectrumStage>(b.fftSize, window_id(b.window));
+    }
     static work::Status           work(B& b, std::size_t nIn, std::size_t nOut) { return offload_work(b, nIn, nOut, make_stage); }
 };
 
@@ -2903,7 +2927,7 @@ inline std::vector<DeviceRun*> plan(Graph& g, std::size_t min_blocks = 2, std::s
     const auto eligible = [](BlockModel& b) {
         const auto& d = b.compute_domain();
         return d.is_device() && (d.backend.empty() || d.backend == "hip") && b.input_edges().size() == 1 && b.output_edges().size() == 1 &&
-               b.input_edges()[0] && b.output_edges()[0];
+               b.input_edges()[0] && b.output_edges()[0] && !b.stride_active(); // (a block with an active stride runs through its own seam: a run moves whole chunks)
     };
     const auto readers = [&](const std::shared_ptr<EdgeBufferBase>& e) {
         std::size_t n = 0;

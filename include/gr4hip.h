@@ -122,7 +122,9 @@ const char* gr4hip_last_error(void); /* thread-local text of the last failure */
  * Names: GR4HIP_FIR_NO_BF16X3, GR4HIP_FIR_NO_DECIM_FD, GR4HIP_IIR_THREE_PASS, GR4HIP_IIR_LOOKBACK, GR4HIP_IIR_NO_SPLIT, GR4HIP_IIR_SEQ_SLOTS (an integer), GR4HIP_FFT_BLUESTEIN_PIPELINE,
  * GR4HIP_FFT_NO_PIPELINE, GR4HIP_ROTATOR_LEAP, GR4HIP_ROTATOR_WALK, GR4HIP_CHAIN16, GR4HIP_FFT_SMOOTH_RUNTIME, GR4HIP_EWISE_NO_DIV_RCP, GR4HIP_SIGGEN_GAUSS_PERMILLE (an integer:
  * the attempts the Gaussian signal generator launches per 1000 needed pairs, 0 = its own formula; whatever it launches, the values are the same), GR4HIP_INTERP_NO_MFMA (the
- * interpolating FIR stays off the matrix pipe), GR4HIP_INTERP_SPW (an integer: 1 .. 4 segments per workgroup of the interpolating FIR's matrix-pipe kernel, 0 = its own formula). */
+ * interpolating FIR stays off the matrix pipe), GR4HIP_INTERP_SPW (an integer: 1 .. 4 segments per workgroup of the interpolating FIR's matrix-pipe kernel, 0 = its own formula),
+ * GR4HIP_STFT_GATHER (an integer: 1 = overlapped FFT frames take the gather path also where the hop kernels read them in place, 2 = the hop kernels also for the short
+ * calls with a seam that the default sends to the gather path). */
 int gr4hip_developer_switch(const char* name, int value);
 const char* gr4hip_status_string(int status);
 int         gr4hip_device_count(int* count);
@@ -479,6 +481,31 @@ int    gr4hip_specint_destroy(gr4hip_specint_t* si);
 size_t gr4hip_specint_leaf(void);
 int    gr4hip_fft_mag2_integrate(gr4hip_fft_t* fft, gr4hip_specint_t* si, const void* d_in, size_t n_frames, float* d_out, size_t* n_out, gr4hip_stream_t stream);
 int    gr4hip_pfb_power_integrate(gr4hip_pfb_t* pfb, gr4hip_specint_t* si, const void* d_in, size_t n_frames, float* d_out, size_t* n_out, gr4hip_stream_t stream);
+
+/* Overlapped and skipped FFT frames: STFT and Welch (OVERLAPPED_FFT.md) -- the reference's `stride` setting (Block.hpp:711, 1546-1574, 1611-1616) on the FFT block,
+ * stated for a stream.  N = fft_size, S = stride (0 means N).  Frame m of a stream covers the samples [m S, m S + N) and is emitted once its last sample has arrived;
+ * nothing synthetic is transformed (no zeros in front of the stream, no trailing partial frame).  Each frame's outputs are exactly those of the FFT block above for
+ * that frame, under the same window and flags; S < N overlaps frames, S > N skips samples.  The handle keeps `off`, the start of the next frame relative to the next
+ * call's first sample (0 after create / reset, never below -(N - 1)), and carries the last N - 1 samples.  A call of n_in samples emits k = 0 frames if
+ * n_in - off < N, else k = (n_in - N - off) / S + 1; afterwards off += k S - n_in.  The values do not depend on how a stream is cut into calls, nor on a call's frame
+ * count: the 8192-point frame pipeline of gr4hip_fft_spectrum / _mag2 is never used.  Non-finite samples reach exactly the frames that hold them.
+ * *n_frames = k, known on the host without a device sync; gr4hip_stft_pending (host only) says it beforehand: output capacity is the caller's duty.  Output layouts per
+ * frame are the FFT block's.  gr4hip_stft_mag2_integrate is gr4hip_stft_mag2 followed by gr4hip_specint_process, bit for bit, in pieces through the integrator's
+ * bounded scratch.  gr4hip_stft_reset (off = 0, history dropped) is stream-ordered (LIFECYCLE CALLS above).
+ * Supported: every fft_size gr4hip_fft_create takes; strides 1 .. 2^20 -- GR4HIP_UNSUPPORTED from create beyond (the caller keeps its CPU path).
+ * GR4HIP_INVALID_ARGUMENT before any device work: a NULL handle or n_frames, a NULL input with n_in > 0, every output NULL, an input not aligned to its element (8 bytes
+ * C32, 4 bytes F32), d_spectrum not aligned to 8 bytes or a float output not to 4, an output that overlaps the input, more than 2^40 samples in or values per output
+ * in one call.  n_in == 0 is a no-op with *n_frames = 0. */
+typedef struct gr4hip_stft gr4hip_stft_t;
+int gr4hip_stft_create(gr4hip_stft_t** stft, int in_dtype, size_t fft_size, size_t stride, int window, int flags);
+int gr4hip_stft_reset(gr4hip_stft_t* stft);
+int gr4hip_stft_pending(const gr4hip_stft_t* stft, size_t n_in, size_t* n_frames);
+int gr4hip_stft_process(gr4hip_stft_t* stft, const void* d_in, size_t n_in, float* d_mag, float* d_phase, float* d_re, float* d_im, float* d_ranges, size_t* n_frames,
+                        gr4hip_stream_t stream);
+int gr4hip_stft_spectrum(gr4hip_stft_t* stft, const void* d_in, size_t n_in, float* d_spectrum, size_t* n_frames, gr4hip_stream_t stream);
+int gr4hip_stft_mag2(gr4hip_stft_t* stft, const void* d_in, size_t n_in, float* d_mag2, size_t* n_frames, gr4hip_stream_t stream);
+int gr4hip_stft_mag2_integrate(gr4hip_stft_t* stft, gr4hip_specint_t* si, const void* d_in, size_t n_in, float* d_out, size_t* n_out, gr4hip_stream_t stream);
+int gr4hip_stft_destroy(gr4hip_stft_t* stft);
 
 /* Cross-spectrum correlator (X-engine) behind the spectra above: the averaged cross-spectral matrix of S streams, 1 < S <= 32 (CROSS_SPECTRUM.md).  The reference
  * has no such block: the definition is the project's, tests/cross_spectrum_oracle.py pins it.  Each stream is a sequence of frames X_s[f][c], c < n_bins,
